@@ -103,6 +103,9 @@ def parse():
     ap.add_argument("--allow-degraded", action="store_true",
                     help="N > 1: accept the host-staged transport / in-stream exchanges when RCCL is unavailable (the line then says degraded: true)")
     ap.add_argument("--rhs", choices=["lin", "rand"], default="lin")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline leg's last timed solve returned (solution x, residual history) "
+                         "as DIR/<name>.npy (float64, <= 64 MB in all: a seeded sample of x beyond that)")
     args = ap.parse_args()
     if args.cells is None:
         args.cells = 128 if args.gpus == 1 else WS_CELLS
@@ -451,8 +454,30 @@ def emit(out):
     os.write(_REAL_STDOUT if _REAL_STDOUT is not None else 1, (txt + "\n").encode())
 
 
+DUMP_LIMIT = 64 << 20      # bytes, all --dump-outputs files together
+
+
+def dump_outputs(dirname, x, residuals):
+    """--dump-outputs: the arrays a caller of the timed solve receives -- x and the residual history (float64).  An x larger than the
+    budget is written as a fixed, seeded sample x[idx] with its indices (x_index.npy, exact in float64), the same on every run."""
+    os.makedirs(dirname, exist_ok=True)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    res = np.ascontiguousarray(residuals, dtype=np.float64)
+    arrays = {"residuals": res}
+    room = (DUMP_LIMIT - res.nbytes - 3 * 4096) // 8            # (4 KB per .npy header, generously)
+    if x.size <= room:
+        arrays["x"] = x
+    else:
+        idx = np.sort(np.random.default_rng(20240601).choice(x.size, size=room // 2, replace=False))
+        arrays["x"], arrays["x_index"] = x[idx], idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     args = parse()
+    if args.dump_outputs and args.gpus > 1:
+        raise SystemExit("--dump-outputs: single-GPU runs only (--gpus 1)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
     claim_stdout()
@@ -643,6 +668,8 @@ def main():
     nlev = args.levels
     R = q1_pair(args.cells, nlev, args.steps, args.warmup, "generic" in legs, "host_io" in legs, "")
     D, H, b, n, x, ns = R["D"], R["H"], R["b"], R["n"], R["x"], R["D"]["ns"]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, x, D["hist"])       # x and the history as the last timed solve left them
     vbytes, cgbytes = R["model_bytes"]
     # the same sweep kernel on the coarser levels (report per level; these fit the Infinity Cache)
     per_level = []

@@ -727,4 +727,8 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if os.environ.get("GMG_TEST_THREAD_RANKS"):          # every rank a thread of this process (thread_ranks.py)
+        import thread_ranks
+        thread_ranks.run(int(os.environ["WORLD_SIZE"]), lambda r: main())
+    else:
+        main()
