@@ -320,6 +320,17 @@ struct DevCSR {
     std::vsnprintf(sweep_sig, sizeof(sweep_sig), fmt, ap);
     va_end(ap);
   }
+  // the wide-row operator kernel first launched on this matrix: gmg_sweep_signature's answer on a level that runs no row sweep
+  // (patch-smoothed Q2 levels), so that the kernel family of their operator applications can be asserted
+  mutable char op_sig[80] = {0};
+  void note_op(const char *fmt, ...) const __attribute__((format(printf, 2, 3)))
+  {
+    if (op_sig[0]) return;
+    va_list ap;
+    va_start(ap, fmt);
+    std::vsnprintf(op_sig, sizeof(op_sig), fmt, ap);
+    va_end(ap);
+  }
   bool present() const { return rowptr != nullptr; }
 };
 
@@ -1732,6 +1743,7 @@ struct gmg_solver {
             HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sellw_zwalk_kernel<EPI, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
             attr_z[device & 63] = true;
           }
+          M.note_op("sellw_zwalk_kernel<EPI=%d,FM=%d> wgs=%d", (int)EPI, pat_fma ? 1 : 0, nwz);
           if (pat_fma) hipLaunchKernelGGL((sellw_zwalk_kernel<EPI, true>), dim3((unsigned)nwz), dim3(256), ldsz, stream, a, M.wz_geo);
           else
           hipLaunchKernelGGL((sellw_zwalk_kernel<EPI, false>), dim3((unsigned)nwz), dim3(256), ldsz, stream, a, M.wz_geo);
@@ -6895,7 +6907,8 @@ int gmg_sweep_signature(gmg_handle_t h, int lev, char *buf, int cap)
     check_level(h, lev, false);
     REQUIRE(!h->inactive(lev), GMG_ERR_STATE, "this rank holds no part of that level (it lives on a rank subset, gmg_set_redistribution)");
     REQUIRE(buf && cap > 0, GMG_ERR_INVALID, "null buffer");
-    std::snprintf(buf, (size_t)cap, "%s", h->lev[lev].A.sweep_sig);
+    const DevCSR &A = h->lev[lev].A;
+    std::snprintf(buf, (size_t)cap, "%s", A.sweep_sig[0] ? A.sweep_sig : A.op_sig);
   });
 }
 

@@ -67,10 +67,12 @@ class StreamedCSR:
     gmg_set_operator_rows and drops it, so the host never holds more than one block -- the driver-side counterpart of an
     assembler that emits the matrix slab by slab."""
 
-    def __init__(self, shape, blocks_fn, plan_fn=None):
+    def __init__(self, shape, blocks_fn, plan_fn=None, plane_fn=None):
         self.shape = (int(shape[0]), int(shape[1]))
         self._fn = blocks_fn
         self._plan = plan_fn
+        self._plane_fn = plane_fn
+        self._plane = None
 
     def row_blocks(self):
         return self._fn()
@@ -81,6 +83,19 @@ class StreamedCSR:
         if self._plan is not None:
             return self._plan()
         return (("block", row0, B) for row0, B in self._fn())
+
+    def plane_rows(self, z):
+        """(row0, CSR block) of node plane z -- the very block `row_blocks()` yields for it (same generator, same bits), built by
+        random access: any plane of a streamed operator can be checked without generating the planes before it.  Nothing but the
+        1-D axis tables is kept between calls."""
+        if self._plane_fn is None:
+            raise TypeError("this stream has no random access to its planes")
+        if self._plane is None:
+            self._plane, self._plane_nrows = self._plane_fn()
+        if not 0 <= z < self.shape[0] // self._plane_nrows:
+            raise IndexError(f"plane {z} out of range")
+        ptr, idx, val = self._plane(z)
+        return z * self._plane_nrows, CSR((self._plane_nrows, self.shape[1]), ptr, idx, val)
 
     def materialize(self):
         """the whole operator as one CSR (tests / small sizes)"""
@@ -197,7 +212,7 @@ def _tensor_csr(axes, terms, ncols_axes):
     return CSR((nx * ny * nz, ncx * ncy * ncz), ptr, idx, val)
 
 
-def _plane_maker(axes, terms, ncols_axes):
+def _plane_maker(axes, terms, ncols_axes, cache_max=12):
     """plane(z) -> (ptr, idx, val) of one z-plane of rows of  sum_t Z_t (x) Y_t (x) X_t  (random access).  Values are formed by the
     same products and sums as one big tensor product would.  Planes whose 1-D z-rows agree up to a shift of the column index
     (all interior planes of a uniform mesh, period `order`) reuse the first such plane's arrays: the columns get a constant
@@ -225,12 +240,18 @@ def _plane_maker(axes, terms, ncols_axes):
             np.cumsum(mask.reshape(ny * nx, -1).sum(axis=1), out=ptr[1:])
             hit = (first, ptr, col[mask].astype(np.int64), np.ascontiguousarray(v[mask]))
             del mask, col, v
-            if len(cache) < 12:
+            if len(cache) < cache_max:
                 cache[key] = hit
         f0, ptr, idx0, val = hit
         idx = idx0 + (first - f0) * (ncy * ncx) if first != f0 else idx0
         return ptr, idx, val
     return plane
+
+
+def _plane_access(axes, terms, ncols_axes):
+    """(plane(z), rows per plane) for StreamedCSR.plane_rows: no plane cache (a plane of the finest Q2 256^3 operator is ~0.5 GB;
+    what the caller keeps is the caller's)"""
+    return _plane_maker(axes, terms, ncols_axes, cache_max=0), axes[0].shape[0] * axes[1].shape[0]
 
 
 def _tensor_csr_blocks(axes, terms, ncols_axes, raw=False):
@@ -455,7 +476,8 @@ def poisson_matrix_stream(ncells, order=1, lengths=None) -> StreamedCSR:
             terms.append((M[0], M[1], K[2]))
         return [t[1] for t in tabs], terms, [t[0] for t in tabs]
     n = level_sizes(ncells, order)
-    return StreamedCSR((n, n), lambda: _tensor_csr_blocks(*blocks()), lambda: _tensor_csr_plan(*blocks()))
+    return StreamedCSR((n, n), lambda: _tensor_csr_blocks(*blocks()), lambda: _tensor_csr_plan(*blocks()),
+                       lambda: _plane_access(*blocks()))
 
 
 def _interp_1d(nc_coarse, order):
@@ -531,7 +553,7 @@ def prolongation_stream(ncells_coarse, order=1) -> StreamedCSR:
         cols, vals, ncols = _transfer_tables(nc, order, False)
         return cols, [tuple(vals)], ncols
     return StreamedCSR((level_sizes(tuple(2 * c for c in nc), order), level_sizes(nc, order)), lambda: _tensor_csr_blocks(*args()),
-                       lambda: _tensor_csr_plan(*args()))
+                       lambda: _tensor_csr_plan(*args()), lambda: _plane_access(*args()))
 
 
 def restriction_stream(ncells_coarse, order=1) -> StreamedCSR:
@@ -543,7 +565,7 @@ def restriction_stream(ncells_coarse, order=1) -> StreamedCSR:
         cols, vals, ncols = _transfer_tables(nc, order, True)
         return cols, [tuple(vals)], ncols
     return StreamedCSR((level_sizes(nc, order), level_sizes(tuple(2 * c for c in nc), order)), lambda: _tensor_csr_blocks(*args()),
-                       lambda: _tensor_csr_plan(*args()))
+                       lambda: _tensor_csr_plan(*args()), lambda: _plane_access(*args()))
 
 
 def _apply_axes(G, mats):

@@ -485,7 +485,9 @@ GMG_API int gmg_model_bytes(gmg_handle_t h, double *vcycle_bytes, double *cg_ite
 GMG_API int gmg_level_format(gmg_handle_t h, int lev, int *sell, int *vdict, int *idx16,
                              double *stream_bytes_per_nnz, double *padding);
 /* Kernel + template arguments + launch geometry of the fused sweep last launched on level lev ("" before the first sweep):
- * committed counter measurements (profiles/traffic_latest.json) are only attached to a bench line whose sweep has this signature. */
+ * committed counter measurements (profiles/traffic_latest.json) are only attached to a bench line whose sweep has this signature.
+ * A level that has run no row sweep (patch-smoothed wide-row levels) reports the wide-row operator kernel its matrix first ran
+ * (sellw_zwalk_kernel<...>), or "" if none. */
 GMG_API int gmg_sweep_signature(gmg_handle_t h, int lev, char *buf, int cap);
 /* Measured streaming ceiling: a 16 B/lane copy kernel over nbytes (read) + nbytes (write), reps launches timed with HIP
  * events on the handle's stream; *gbytes_per_s = moved bytes / time.  Reported by bench.py beside the 8 TB/s spec. */

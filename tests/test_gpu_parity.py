@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import fullsize_reference as fr
 from conftest import max_rel, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -368,11 +369,19 @@ def test_maxiter_and_tolerance_flags(S, po, orc, hierarchy):
 
 
 # ---------------------------------------------------------------- BASELINE config 2 at full size: properties
-def test_config2_full_size_properties(S, po, hierarchy):
+# the sweep kernel family the default options pick for level 0 of 128^3 (include/gmg_amd.h gates): below pat_tile_rows (3.5e6)
+# and pat_zwalk_rows (9e6) -> the pair sweep.  (The smaller levels run one-launch passes, which note no per-sweep signature.)
+CONFIG2_FAMILIES = {0: "sells_r2sweep_kernel"}
+
+
+def test_config2_full_size_properties(S, po, orc, hierarchy):
     """3-D Q1 128^3, 4 levels (2 048 383 dofs, 54.4 M nnz): size-independent checks --
     analytic solution reached within the reference's criterion, iteration count equal to the
     oracle's count at every smaller size (3), residual history within 5% of BASELINE.md's
-    survey-time values, linearity of the V-cycle, and an exact-residual check."""
+    survey-time values, linearity of the V-cycle, and an exact-residual check.  Then every kernel
+    of every level with the default options against the oracle and the exact row reference
+    (tests/fullsize_reference.py), the dot at the level-0 length against the exact dot, and the
+    whole solve against the sequential oracle (iterations, flag, history, solution)."""
     import torch
     nc, nlev = (128, 128, 128), 4
     H = hierarchy(nc, nlev)
@@ -406,6 +415,16 @@ def test_config2_full_size_properties(S, po, hierarchy):
     # symmetry of the preconditioner (needed by CG): <M r1, r2> == <r1, M r2>
     a12, a21 = torch.dot(z1, r2).item(), torch.dot(r1, z2).item()
     assert abs(a12 - a21) <= 1e-10 * max(abs(a12), abs(a21))
+    # every kernel of every level against the oracle and the exact reference
+    go = orc.GMG(H["mats"], H["prolongations"], H["restrictions"], maxiter=1)
+    report = fr.check_q1_levels(g, H, go, orc, CONFIG2_FAMILIES, seed=128)
+    report.append(f"dot n={b.size}: |d - exact| <= {fr.check_dot(g, b.size, 128):.3g} of the bound")
+    # the whole solve against the sequential oracle
+    xo, nit, flag, hist = orc.cg_solve(A, b, Pl=go, maxiter=20, atol=1e-14, rtol=1e-6)
+    assert (solver.log.num_iters, solver.log.flag) == (nit, flag)
+    np.testing.assert_allclose(solver.log.residuals[: nit + 1], hist, rtol=TOL_HIST)
+    assert rel_err(x, xo) <= 1e-10
+    print("\n".join(["config2 128^3:"] + report))
 
 
 # ---------------------------------------------------------------- storage formats of the operator stream

@@ -6,11 +6,13 @@ size-independent properties.  Same bar as tests/test_gpu_parity.py: the HIP path
 import numpy as np
 import pytest
 
+import fullsize_reference as fr
 from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
 
 TOL_KERNEL = 1e-13   # per-kernel max|y - y_ref| / max|y_ref|
+TOL_HIST = 1e-8      # residual histories against the oracle's, relative per entry (tests/test_gpu_parity.py)
 
 
 def jac(S, nlev, niter=10, omega=2.0 / 3.0):
@@ -206,14 +208,23 @@ def test_big_level_matvecs_are_bitwise_the_single_row_kernels_and_the_oracle(S, 
 
 
 # ---------------------------------------------------------------- the per-GPU problem of BASELINE configs[3] on its own workload
+# the sweep kernel family the default options pick per level of 288^3 (include/gmg_amd.h gates): level 0 (2.4e7 rows) is above
+# pat_zwalk_rows (9e6) -> the walk; level 1 (2.9e6) is below pat_tile_rows (3.5e6; the eight-wave OCC=2 shape starts there) and above
+# the one-launch pass (~5e5 rows) -> the pair sweep, four waves per workgroup; levels 2.. run one-launch passes (no sweep signature)
+WEAK_FAMILIES = {0: "sells_zsweep_kernel", 1: ("sells_r2sweep_kernel<", "OCC=1")}
+
+
 @pytest.mark.child_process
-def test_weak_anchor_288cubed_properties(S, po):
+def test_weak_anchor_288cubed_properties(S, po, orc):
     """288^3 cells Q1, 6 levels (2.37e7 dofs): what every GPU of BASELINE configs[3] (576^3 on 2x2x2) holds and what bench.py reports as
     `weak_anchor_value`.  Beyond the oracle's reach in test time, so: the finest level runs the OCC=2 kernels the tests above pin;
     the finest level runs the big-level kernels (sells_zsweep_kernel, or sells_r2sweep_kernel<OCC=2> with pat_zwalk = 0); CG takes 3 iterations (as the oracle does at every size it reaches with this rhs: 16^3 ... 64^3) with flag = rtol; the
     reference's own L2 criterion (< 1e-8, GMGTests.jl / SmoothersTests.jl:43); the true residual through the device operator;
     and the default (row-pattern) layout reproduces the generic 12 B/nnz layout BIT FOR BIT (every layout sums a row in CSR
-    order) -- a checksum over 2.4e7 entries and the residual history, both exact."""
+    order) -- a checksum over 2.4e7 entries and the residual history, both exact.  With the default options also every kernel of
+    every level against the oracle and the exact row reference (tests/fullsize_reference.py), the dot at the level-0 length, and
+    the whole solve against the sequential oracle (iterations, flag, history, solution; its time is printed)."""
+    import time
     import torch
     from gridapsolvers_jl_amd import abi
     nc, nlev = (288, 288, 288), 6
@@ -241,6 +252,18 @@ def test_weak_anchor_288cubed_properties(S, po):
         if key == "default":
             assert fmt["layout"] == "SELL-P" and ("sells_zsweep_kernel" in sig or ("sells_r2sweep_kernel" in sig and "OCC=2" in sig)), (fmt, sig)
             assert ns.P_ns.device_bytes() < 4e9
+            go = orc.GMG(H["mats"], H["prolongations"], H["restrictions"], maxiter=1)
+            report = fr.check_q1_levels(ns.P_ns, H, go, orc, WEAK_FAMILIES, seed=288, post_levels=())
+            report.append(f"dot n={n}: |d - exact| <= {fr.check_dot(ns.P_ns, n, 288):.3g} of the bound")
+            t0 = time.time()
+            xo, nit, flag_o, hist_o = orc.cg_solve(H["mats"][0], b, Pl=go, maxiter=20, atol=1e-14, rtol=1e-6)
+            report.append(f"oracle CG + GMG at 288^3: {time.time() - t0:.1f} s")
+            del go
+            assert (solver.log.num_iters, solver.log.flag) == (nit, flag_o), (sig, nit, flag_o)
+            np.testing.assert_allclose(hist, hist_o, rtol=TOL_HIST)
+            assert rel_err(xd.cpu().numpy(), xo) <= 1e-10
+            del xo
+            print("\n".join(["weak anchor 288^3:"] + report))
         else:
             assert fmt["layout"] == "SELL-64", fmt
         got[key] = (xd.cpu().numpy(), hist)
@@ -255,7 +278,7 @@ def test_weak_anchor_288cubed_properties(S, po):
 
 # ---------------------------------------------------------------- BASELINE configs[2] at its stated size
 @pytest.mark.child_process
-def test_config3_q2_256cubed_properties(S, po):
+def test_config3_q2_256cubed_properties(S, po, orc):
     """BASELINE configs[2] as stated: 3-D Poisson Q2 on 256^3 cells (1.33e8 dofs, 8.5e9 stored nonzeros, 1.7e7 vertex-star patches on
     the finest level), 5-level GMG, Richardson(PatchSolver,10,0.2) pre = post, FGMRES(5), rtol 1e-6
     (test/LinearSolvers/GMGTests.jl:18-47,119-123).  The three finest operators are streamed (nobody holds their CSR: 102 GB).
@@ -268,10 +291,13 @@ def test_config3_q2_256cubed_properties(S, po):
     nc, nlev, order = (256, 256, 256), 5, 2
     H = po.build_hierarchy(nc, nlev, order, stream_min_rows=1000000)
     assert [hasattr(M, "row_blocks") for M in H["mats"]] == [True, True, True, False, False]
-    sm = []
+    sm, patches = [], {}
     for l in range(nlev - 1):
         pp, pd = po.vertex_star_patches(H["ncells"][l], order)
         sm.append(S.RichardsonSmoother(S.PatchSolver(pp, pd), 10, 0.2))
+        if l in (0, nlev - 2):
+            patches[l] = (pp, pd)                         # kept for the patch-operator checks below
+    del pp, pd
     b = po.dirichlet_lift_rhs(nc, order)
     gmg = S.GMGLinearSolver(H["mats"], H["prolongations"], H["restrictions"], pre_smoothers=sm, post_smoothers=sm, maxiter=1)
     solver = S.FGMRESSolver(5, gmg, maxiter=20, atol=1e-14, rtol=1e-6)
@@ -296,6 +322,75 @@ def test_config3_q2_256cubed_properties(S, po):
     assert po.l2_error_sq(nc, order, x) < 1e-8
     assert np.max(np.abs(x - po.nodal_values(nc, order))) < 1e-5
     assert t_setup < 120.0, t_setup
+    # every operator application of every level with the default options: on the three streamed levels sampled rows of seven
+    # node planes (first / last two, and two interior planes the device only receives as "repeat" items) against
+    # StreamedCSR.plane_rows and the exact row reference; on the materialised levels 3 and 4 the whole vector against the oracle.
+    # The streamed levels (>= pat_zwalk_wide_rows = 1e6 rows, include/gmg_amd.h) apply their operator with the wide-row walk; they
+    # run no row sweep (patch smoothers), so their signature is that operator kernel's.
+    g = ns.P_ns
+    report = []
+    rng = np.random.default_rng(256)
+    for l in range(nlev - 1):
+        sig = g.sweep_signature(l)
+        if l < 3:
+            assert "sellw_zwalk_kernel" in sig, f"Q2 level {l}: the default for >= 1e6 wide rows is sellw_zwalk_kernel, got [{sig}]"
+        M, P, R = H["mats"][l], H["prolongations"][l], H["restrictions"][l]
+        nz, nzc = 2 * H["ncells"][l][2] - 1, 2 * H["ncells"][l + 1][2] - 1
+        planes = lambda m: sorted({0, 1, 2, m // 2, m // 2 + 1, m - 2, m - 1})
+        xl = rng.uniform(-1, 1, M.shape[0])
+        xc = rng.uniform(-1, 1, P.shape[1])
+        fr_ = []
+        for op, Mx, v, pl, name in ((abi.OP_A, M, xl, planes(nz), "OP_A"), (abi.OP_P, P, xc, planes(nz), "OP_P"),
+                                    (abi.OP_R, R, xl, planes(nzc), "OP_R")):
+            y = fr.device_op(g, l, op, v, Mx.shape[0])
+            what = f"Q2 level {l} ({M.shape[0]} rows) {name}"
+            if hasattr(Mx, "plane_rows"):
+                fr_.append(fr.check_stream_rows(y, Mx, pl, v, sig, what, seed=l))
+            else:
+                assert np.array_equal(y, orc.spmv(Mx, v)), (what, sig)
+                fr_.append(fr.check_csr_rows(y, Mx, np.arange(0, Mx.shape[0], 97), v, sig, what))
+            del y
+        report.append(f"level {l}: {M.shape[0]} rows [{sig}] |y - exact| <= {max(f[0] for f in fr_):.3g} of the bound ({max(f[1] for f in fr_):.2f} ulp)")
+    A4 = H["mats"][-1]
+    x4 = rng.uniform(-1, 1, A4.shape[0])
+    assert np.array_equal(fr.device_op(g, nlev - 1, abi.OP_A, x4, A4.shape[0]), orc.spmv(A4, x4))
+    # the coarsest level (29 791 dofs >= coarse_auto_cg_min) is served by the device CG-Jacobi solver to rtol 1e-10: gate the
+    # relative residual it promises
+    xc4 = np.zeros_like(x4)
+    g.coarse_solve(x4, xc4)
+    crel = np.linalg.norm(x4 - orc.spmv(A4, xc4)) / np.linalg.norm(x4)
+    assert crel <= 1.5e-10, (crel, g.coarse_log())
+    report.append(f"level {nlev - 1}: {A4.shape[0]} dofs, coarse CG-Jacobi |r - A x| / |r| = {crel:.3g}")
+    # one application of the additive vertex-star patch operator on level 0 (1.7e7 patches), sampled: dofs of the first, a middle
+    # and the last node plane against per-patch LU solves of blocks read from plane_rows
+    n0, per0 = H["mats"][0].shape[0], (2 * H["ncells"][0][0] - 1) * (2 * H["ncells"][0][1] - 1)
+    nz0 = 2 * H["ncells"][0][2] - 1
+    r0 = rng.uniform(-1, 1, n0)
+    dx0 = np.zeros(n0)
+    g.precond(0, r0, dx0)
+    sample = np.concatenate([z * per0 + np.concatenate([np.arange(40), per0 - 1 - np.arange(40), rng.integers(0, per0, 40)])
+                             for z in (0, nz0 // 2, nz0 - 1)])
+    dofs, ref = fr.patch_precond_reference(H["mats"][0], *patches.pop(0), sample, r0)
+    dev = fr.max_rel(dx0[dofs], ref)
+    assert dev <= 1e-11, f"Q2 level 0 patch precond on {dofs.size} sampled dofs: max_rel {dev:.3g}"
+    report.append(f"level 0 patch precond: {dofs.size} sampled dofs, max_rel vs per-patch LU {dev:.3g}")
+    del dx0, r0
+    # levels 3..4 (materialised): smooth (PRE / POST) and precond of the patch smoother against the oracle's
+    l3 = nlev - 2
+    A3 = H["mats"][l3]
+    go = orc.GMG(H["mats"][l3:], H["prolongations"][l3:], H["restrictions"][l3:],
+                 pre_smoothers=[orc.Smoother(orc.PATCH, 10, 0.2, *patches[l3])], maxiter=1)
+    x3, r3 = rng.uniform(-1, 1, A3.shape[0]), rng.uniform(-1, 1, A3.shape[0])
+    for which, post in ((abi.PRE, False), (abi.POST, True)):
+        x, r = x3.copy(), r3.copy()
+        g.smooth(l3, x, r, which=which)
+        xo, ro = go.smooth(0, x3, r3, post=post)
+        assert fr.max_rel(x, xo) <= TOL_KERNEL and fr.max_rel(r, ro) <= TOL_KERNEL, (l3, which, fr.max_rel(x, xo), fr.max_rel(r, ro))
+    dx = np.zeros_like(r3)
+    g.precond(l3, r3, dx)
+    assert fr.max_rel(dx, go.precond(0, r3)) <= 1e-12, (l3, fr.max_rel(dx, go.precond(0, r3)))
+    report.append(f"level {l3}: patch smooth PRE / POST and precond vs the oracle: precond max_rel {fr.max_rel(dx, go.precond(0, r3)):.3g}")
+    print("\n".join(["config3 Q2 256^3:"] + report))
     ns.P_ns.close()
 
 
