@@ -94,6 +94,8 @@ SYMBOLS = {
                          C.c_double, C.c_double, C.c_int, C.POINTER(Result), C.c_void_p, C.c_int],
     "gmg_fgmres_solve_pl": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                             C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Result), C.c_void_p, C.c_int],
+    "gmg_minres_solve": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                         C.POINTER(Result), C.c_void_p, C.c_int],
     "gmg_richardson_solve": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int,
                              C.POINTER(Result), C.c_void_p, C.c_int],
     "gmg_op_apply": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int],
@@ -150,6 +152,8 @@ SYMBOLS = {
                                C.c_double, C.c_double, C.c_int, C.POINTER(Result), C.c_void_p, C.c_int],
     "gmg_block_cg_solve": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
                            C.POINTER(Result), C.c_void_p, C.c_int],
+    "gmg_block_minres_solve": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                               C.POINTER(Result), C.c_void_p, C.c_int],
     "gmg_block_diag_log": [C.c_void_p, C.c_int, C.POINTER(Result)],
 }
 

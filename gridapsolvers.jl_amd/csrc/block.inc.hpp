@@ -563,6 +563,26 @@ int gmg_block_cg_solve(gmg_block_handle_t h, const double *b, double *x, int mem
   });
 }
 
+int gmg_block_minres_solve(gmg_block_handle_t h, const double *b, double *x, int memspace, int maxiter, double atol, double rtol,
+                           int use_precond, gmg_result *res, double *hist, int hist_cap)
+{
+  return guarded_b(h, [&] {
+    check_block_ready(h);
+    REQUIRE(b && x, GMG_ERR_INVALID, "null vector");
+    REQUIRE(maxiter >= 0, GMG_ERR_INVALID, "maxiter < 0");
+    const int64_t n = h->N();
+    const double *db = h->eng.in_vec(b, n, memspace, h->st_b);
+    double *dx = (memspace == GMG_MEM_DEVICE) ? x : h->st_x;
+    if (memspace == GMG_MEM_HOST) h->eng.h2d(dx, x, n);
+    ConvLog log;
+    log.configure(maxiter, atol, rtol);
+    KrylovOps ops = h->ops(use_precond != 0);
+    const double beta_r = minres_core(h->eng, n, n, db, dx, h->eng.minres_work(n), h->eng.mr_parts, ops, log);
+    h->eng.out_vec(x, dx, n, memspace);
+    log.export_to(res, hist, hist_cap, beta_r);
+  });
+}
+
 int gmg_block_diag_log(gmg_block_handle_t h, int i, gmg_result *res)
 {
   return guarded_b(h, [&] {

@@ -542,6 +542,8 @@ struct gmg_block_solver;
 static void block_forget(gmg_block_solver *B, gmg_solver *g);   // block.inc.hpp
 static double cg_core(gmg_solver &S, int64_t n, const double *db, double *dx, double *w, double *p, double *z, double *r,
                       const KrylovOps &ops, bool flexible, ConvLog &log);
+static double minres_core(gmg_solver &S, int64_t n, int64_t nv, const double *db, double *dx, double *const vec[9], double *parts,
+                          const KrylovOps &ops, ConvLog &log);
 
 struct gmg_solver {
   gmg_block_solver *attached_to = nullptr;   // block preconditioner that borrowed this handle (gmg_block_set_diag_gmg + setup)
@@ -652,6 +654,21 @@ struct gmg_solver {
   // Krylov work vectors (CGSolvers.jl:42-48 ; FGMRESSolvers.jl:58-70)
   double *cg_w = nullptr, *cg_p = nullptr, *cg_z = nullptr, *cg_r = nullptr;
   std::vector<double *> fg_V, fg_Z;
+  // MINRESSolvers.jl:39-44 (Vnew, V, Vold, Wnew, W, Wold, Znew, Z, Zold), allocated by the first MINRES solve, + the partials of
+  // its two reductions (2 kRedBlocks doubles no preconditioner touches)
+  std::vector<double *> mr_vec;
+  double *mr_parts = nullptr;
+  int64_t mr_nv = 0;
+  double *const *minres_work(int64_t nv)
+  {
+    if (mr_vec.empty() || mr_nv != nv) {
+      mr_vec.clear();
+      for (int i = 0; i < 9; ++i) mr_vec.push_back(dvec(nv));
+      if (!mr_parts) mr_parts = dvec(2 * kRedBlocks);
+      mr_nv = nv;
+    }
+    return mr_vec.data();
+  }
   // staging buffers for host-memory callers
   double *st_b = nullptr, *st_x = nullptr;
   std::vector<double *> st_extra;
@@ -845,6 +862,7 @@ struct gmg_solver {
     for (auto &L : lev) { L.halo.d_snd_idx = nullptr; L.halo.d_sendbuf = nullptr; L.halo.d_recvbuf = nullptr; L.halo.d_pk_ptr = nullptr; L.halo.d_pk_slot = nullptr; }
     cg_w = cg_p = cg_z = cg_r = st_b = st_x = nullptr;
     fg_V.clear(); fg_Z.clear(); st_extra.clear();
+    mr_vec.clear(); mr_parts = nullptr; mr_nv = 0;
     setup_done = false;
   }
 
@@ -4042,6 +4060,81 @@ static double fgmres_core(gmg_solver &S, int64_t n, int64_t nv, const double *db
   return beta;
 }
 
+// solve!(x,ns::MINRESNumericalSetup,b), Krylov/MINRESSolvers.jl:75-148.  vec = the caches of :39-44 in the order Vnew, V, Vold,
+// Wnew, W, Wold, Znew, Z, Zold, nv entries each (A Z needs ghost space); parts = 2 kRedBlocks doubles that no preconditioner writes.
+// The scalars stay on the device (state block, kernels.hpp: MinresState): an iteration is A Z (+ the first stage of delta), Pl,
+// minres_lanczos_kernel and minres_update_kernel -- the Givens rotation is formed by every workgroup of the latter -- and ONE host
+// round trip, for beta_r (the stopping rule).
+static double minres_core(gmg_solver &S, int64_t n, int64_t nv, const double *db, double *dx, double *const vec[9], double *parts,
+                          const KrylovOps &ops, ConvLog &log)
+{
+  double *Vnew = vec[0], *V = vec[1], *Vold = vec[2], *Wnew = vec[3], *W = vec[4], *Wold = vec[5], *Znew = vec[6], *Z = vec[7], *Zold = vec[8];
+  (void)nv;
+  // Scalar slots: FGMRES's basis range (MINRES never runs inside FGMRES, nor FGMRES inside MINRES).  A cg_core nested in the
+  // preconditioner keeps kScalarSlots - 8*depth, the reduction helpers (norm / dot) slot 0.
+  constexpr int kBase = 16;
+  const int kDelta = kBase, kBetaP = kBase + 1, kSt = kBase + 8;
+  static_assert(kBase + 8 + 2 * kMinresState < kScalarSlots - 8 * 4, "MINRES slots overlap the nested CG slots");
+  double *st[2] = {S.d_scalars + kSt, S.d_scalars + kSt + kMinresState};   // state halves: read `cur`, minres_update_kernel writes the other
+  int cur = 0;
+  S.zero(W, n); S.zero(Wold, n); S.zero(Vold, n); S.zero(Zold, n);       // :85-88
+  ops.resid(dx, db, Vnew);                                               // :90-91  Vnew = b - A x
+  S.zero(Znew, n);                                                       // :92
+  if (ops.precond) ops.precond(Znew, Vnew, -1.0); else S.copy(Znew, Vnew, n);   // :93
+  double beta_r = S.norm(n, Znew);                                       // :95
+  const double beta_p = S.dot(n, Znew, Vnew);                            // :96
+  REQUIRE(beta_p > 0.0, GMG_ERR_INVALID, "MINRES: dot(Pl(r), r) <= 0 at start-up -- the preconditioner is not positive definite "
+                                         "(MINRESSolvers.jl:97)");
+  const double gamma = std::sqrt(beta_p);                                // :99
+  const int grid = gmg_solver::grid_for(n);
+  S.copy(V, Vnew, n); S.copy(Z, Znew, n);
+  hipLaunchKernelGGL(div_kernel, dim3(grid), dim3(256), 0, S.stream, n, gamma, V);   // :103  V .= Vnew ./ gamma
+  hipLaunchKernelGGL(div_kernel, dim3(grid), dim3(256), 0, S.stream, n, gamma, Z);   // :104
+  hipLaunchKernelGGL(minres_init_kernel, dim3(1), dim3(1), 0, S.stream, st[cur], gamma, beta_r);   // :99-101,106
+  HIP_CHECK(hipGetLastError());
+  bool done = log.init(beta_r);                                          // :107
+  const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(kRedBlocks, (n + kBlock - 1) / kBlock));
+  const bool fuse = S.fuse_reductions();
+  const bool dist = S.comm.nranks > 1 && !S.reduce_local;
+  const bool post = !dist && S.red_fused && S.opt_int("GMG_HOST_POLL", 1);
+  double *bparts = parts + kRedBlocks;
+  while (!done) {
+    int nd = 0;                                                          // delta still in partials?
+    if (fuse && ops.apply_dot) nd = ops.apply_dot(Z, Vnew, parts);       // :110 + first stage of :112 in one kernel (> 0), or :110 alone (-1)
+    if (nd <= 0) {
+      if (nd == 0) ops.apply(Z, Vnew);                                   // :110
+      if (fuse) nd = S.dot_partials(n, Vnew, Z, parts); else { S.dot_async(n, Vnew, Z, kDelta, false); nd = 0; }   // :112
+    }
+    // :111 (delta = dot(Vnew, Z) does not depend on Znew: its partials are taken before Pl runs).  The norm of Vnew is not formed
+    // (the reference never needs it): the GMG preconditioner is told so with +Inf, see gmg_minres_solve.
+    if (ops.precond) ops.precond(Znew, Vnew, HUGE_VAL); else S.copy(Znew, Vnew, n);
+    hipLaunchKernelGGL(minres_lanczos_kernel, dim3(nb), dim3(kBlock), 0, S.stream, n, Vnew, V, Vold, Znew, Z, Zold, st[cur],
+                       S.d_scalars + kDelta, nd ? parts : nullptr, nd, bparts);   // :112-115
+    HIP_CHECK(hipGetLastError());
+    if (!fuse) S.finish_reduction(nb, kBetaP, false, bparts);           // :115 (all-reduced)
+    S.posted = 0;
+    double *pv = nullptr;
+    unsigned long long *ps = nullptr, want = 0;
+    if (post) { S.need_mail(); want = ++S.mail_seq; pv = &S.d_mail->value; ps = &S.d_mail->seq; }
+    hipLaunchKernelGGL(minres_update_kernel, dim3(nb), dim3(kBlock), 0, S.stream, n, Vnew, Znew, Z, W, Wold, Wnew, dx, st[cur],
+                       st[cur ^ 1], S.d_scalars + kDelta, S.d_scalars + kBetaP, fuse ? bparts : nullptr, fuse ? nb : 0, pv, ps,
+                       want);                                            // :116-133
+    HIP_CHECK(hipGetLastError());
+    S.posted = want;
+    cur ^= 1;
+    beta_r = S.fetch_scalar(kSt + cur * kMinresState + MR_BETA_R);
+    REQUIRE(!(beta_r < 0.0), GMG_ERR_INVALID, "MINRES: sqrt of a negative dot(z, v) -- the preconditioner is not positive definite "
+                                              "(MINRESSolvers.jl:116)");
+    // :137-139 swap3: pointers only (the scalar triples were rotated by minres_update_kernel into the other state half)
+    double *t;
+    t = Vold; Vold = V; V = Vnew; Vnew = t;
+    t = Wold; Wold = W; W = Wnew; Wnew = t;
+    t = Zold; Zold = Z; Z = Znew; Znew = t;
+    done = log.update(beta_r);                                           // :144
+  }
+  return beta_r;                                                         // :147
+}
+
 // ----------------------------------------------------------------------------
 // patch smoother: setup + application
 // ----------------------------------------------------------------------------
@@ -6345,6 +6438,38 @@ int gmg_fgmres_solve_pl(gmg_handle_t h, const double *b, double *x, int memspace
       const double beta = fgmres_core(S, n, nv, db, dx, S.fg_V, S.fg_Z, ops, m0, restart != 0, m_add, log);
       S.out_vec(x, dx, n, memspace);
       log.export_to(res, hist, hist_cap, beta);              // :197
+    });
+  });
+}
+
+int gmg_minres_solve(gmg_handle_t h, const double *b, double *x, int memspace, int maxiter, double atol, double rtol,
+                     int use_precond, gmg_result *res, double *hist, int hist_cap)
+{
+  return guarded(h, [&] {
+    check_ready(h);
+    REQUIRE(b && x, GMG_ERR_INVALID, "null vector");
+    REQUIRE(maxiter >= 0, GMG_ERR_INVALID, "maxiter < 0");
+    REQUIRE(use_precond >= 0 && use_precond <= 3, GMG_ERR_INVALID, "use_precond must be 0, 1, 2 or 3");
+    h->with_persist_retry(x, h->user_n(), memspace, false, [&] {
+      gmg_solver &S = *h;
+      Level &L0 = S.lev[S.kl()];
+      const int64_t n = L0.n;
+      const double *db = S.in_vec(b, n, memspace, S.st_b);
+      const bool dist = S.comm.nranks > 1;
+      double *dx = dist ? S.cg_x : ((memspace == GMG_MEM_DEVICE) ? x : S.st_x);
+      S.in_guess(dx, x, n, memspace);                        // x = initial guess on entry (MINRESSolvers.jl:90)
+      ConvLog log;
+      log.configure(maxiter, atol, rtol);
+      KrylovOps ops = S.level0_ops(use_precond);
+      if (use_precond == 1 && S.log.maxiter != 1) {
+        // minres_core hands the GMG +Inf for the norm of its right-hand side it does not form: with maxiter = 1 that value only
+        // opens the GMG's log (one cycle is run whatever it is); a GMG running several cycles needs the true norm
+        auto pc = ops.precond;
+        ops.precond = [pc](double *z, const double *r, double known) { pc(z, r, std::isinf(known) ? -1.0 : known); };
+      }
+      const double beta_r = minres_core(S, n, L0.nvec, db, dx, S.minres_work(L0.nvec), S.mr_parts, ops, log);
+      S.out_vec(x, dx, n, memspace);
+      log.export_to(res, hist, hist_cap, beta_r);            // :147
     });
   });
 }

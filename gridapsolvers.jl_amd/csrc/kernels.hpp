@@ -3783,6 +3783,128 @@ __global__ void div_dev_kernel(int64_t n, const double *__restrict__ s, double *
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     x[i] = x[i] / d;
 }
+// ---------------------------------------------------------------------------
+// K11: MINRES (Krylov/MINRESSolvers.jl:75-148).  The solver state lives in device memory, so an iteration needs one host
+// round trip (the residual norm of the stopping rule); the Givens rotation is formed by every workgroup from that state.
+// ---------------------------------------------------------------------------
+// LinearAlgebra.givensAlgorithm(f, g) -> (c, s, r): the LAPACK dlartg form Julia ships (safmn2 rescaling, r scaled back, the sign
+// rule flipping c, s and r together).  jl_max is Julia's max (NaN if either is NaN), not fmax.
+__host__ __device__ inline double jl_max(double a, double b) { return (a != a || b != b) ? a + b : (a > b ? a : b); }
+__host__ __device__ inline void givens_lapack(double f, double g, double &cs, double &sn, double &r)
+{
+  const double safmn2 = 0x1p-485, safmx2 = 1.0 / safmn2;        // floatmin2(Float64) = reinterpret(Float64, 0x21a0000000000000)
+  if (g == 0.0) { cs = 1.0; sn = 0.0; r = f; return; }
+  if (f == 0.0) { cs = 0.0; sn = 1.0; r = g; return; }
+  double f1 = f, g1 = g, scale = jl_max(fabs(f1), fabs(g1));
+  if (scale >= safmx2) {
+    int count = 0;
+    do { ++count; f1 *= safmn2; g1 *= safmn2; scale = jl_max(fabs(f1), fabs(g1)); } while (!(scale < safmx2 || count >= 20));
+    r = sqrt(f1 * f1 + g1 * g1); cs = f1 / r; sn = g1 / r;
+    for (int i = 0; i < count; ++i) r *= safmx2;
+  } else if (scale <= safmn2) {
+    int count = 0;
+    do { ++count; f1 *= safmx2; g1 *= safmx2; scale = jl_max(fabs(f1), fabs(g1)); } while (!(scale > safmn2));
+    r = sqrt(f1 * f1 + g1 * g1); cs = f1 / r; sn = g1 / r;
+    for (int i = 0; i < count; ++i) r *= safmn2;
+  } else {
+    r = sqrt(f1 * f1 + g1 * g1); cs = f1 / r; sn = g1 / r;
+  }
+  if (fabs(f) > fabs(g) && cs < 0.0) { cs = -cs; sn = -sn; r = -r; }
+}
+
+// The MINRES state block: two halves of kMinresState doubles, the kernels read half `cur` and minres_update_kernel writes the other
+// (its other workgroups are still reading `cur`).  beta_r < 0 marks a breakdown (sqrt of a negative beta_p: DomainError in Julia).
+enum MinresState : int { MR_GAMMA = 0, MR_GAMMA_OLD, MR_C, MR_C_OLD, MR_S, MR_S_OLD, MR_ETA, MR_BETA_R, kMinresState };
+
+// :113-115  Vnew .= Vnew .- delta .* V .- gamma .* Vold ; Znew .= Znew .- delta .* Z .- gamma .* Zold ; partials of dot(Znew, Vnew)
+// dparts != nullptr: delta = dot(Vnew, Z) (:112) is still in the producer's partials: every workgroup sums them (sum_partials_all),
+// workgroup 0 stores it into *delta; otherwise *delta holds it (all-reduced slot).  `partials` must differ from dparts.
+__global__ __launch_bounds__(kBlock) void minres_lanczos_kernel(int64_t n, double *__restrict__ Vnew, const double *__restrict__ V,
+                                                                const double *__restrict__ Vold, double *__restrict__ Znew,
+                                                                const double *__restrict__ Z, const double *__restrict__ Zold,
+                                                                const double *__restrict__ st, double *__restrict__ delta,
+                                                                const double *__restrict__ dparts, int ndparts,
+                                                                double *__restrict__ partials)
+{
+  __shared__ double sh[5];
+  double d;
+  if (dparts) {
+    d = sum_partials_all(dparts, ndparts, sh);
+    if (blockIdx.x == 0 && threadIdx.x == 0) delta[0] = d;
+    __syncthreads();                                         // sh is reused below
+  } else d = delta[0];
+  const double g = st[MR_GAMMA];
+  double s = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+    const double vn = (Vnew[i] - d * V[i]) - g * Vold[i];
+    const double zn = (Znew[i] - d * Z[i]) - g * Zold[i];
+    Vnew[i] = vn;
+    Znew[i] = zn;
+    s += zn * vn;
+  }
+  const double t = block_sum(s, sh);
+  if (threadIdx.x == 0) partials[blockIdx.x] = t;
+}
+
+// :116-133 with the state in `st` (read) and `st_next` (written by workgroup 0, already rotated as swap3 does, :140-142):
+//   gamma_new = sqrt(beta_p) ; Vnew ./= gamma_new ; Znew ./= gamma_new
+//   alpha0 = c delta - cold s gamma ; (c_new, s_new, alpha1) = givensAlgorithm(alpha0, gamma_new) ; alpha2 = s delta + cold c gamma
+//   alpha3 = sold gamma ; Wnew .= (Z .- alpha2 W .- alpha3 Wold) ./ alpha1 ; x .+= (c_new eta) Wnew ; eta = -s_new eta ;
+//   beta_r = |s_new| beta_r
+// bparts != nullptr: beta_p is still in minres_lanczos_kernel's partials (summed here, stored by workgroup 0 into *beta_p).
+// value != nullptr: workgroup 0 also posts beta_r into host-mapped memory (as reduce_post_kernel does).
+__global__ __launch_bounds__(kBlock) void minres_update_kernel(int64_t n, double *__restrict__ Vnew, double *__restrict__ Znew,
+                                                               const double *__restrict__ Z, const double *__restrict__ W,
+                                                               const double *__restrict__ Wold, double *__restrict__ Wnew,
+                                                               double *__restrict__ x, const double *__restrict__ st,
+                                                               double *__restrict__ st_next, const double *__restrict__ delta,
+                                                               double *__restrict__ beta_p, const double *__restrict__ bparts,
+                                                               int nbparts, double *value, unsigned long long *seq,
+                                                               unsigned long long want)
+{
+  __shared__ double sh[5];
+  double bp;
+  if (bparts) {
+    bp = sum_partials_all(bparts, nbparts, sh);
+    if (blockIdx.x == 0 && threadIdx.x == 0) beta_p[0] = bp;
+  } else bp = beta_p[0];
+  const double d = delta[0];
+  const double g = st[MR_GAMMA], c = st[MR_C], cold = st[MR_C_OLD];
+  const double s = st[MR_S], sold = st[MR_S_OLD], eta = st[MR_ETA], br = st[MR_BETA_R];
+  const double gnew = sqrt(bp);                                                       // :116
+  const double a0 = c * d - cold * s * g;                                             // :122
+  double cnew, snew, a1;
+  givens_lapack(a0, gnew, cnew, snew, a1);                                            // :123
+  const double a2 = s * d + cold * c * g;                                             // :124
+  const double a3 = sold * g;                                                         // :125
+  const double step = cnew * eta;                                                     // :129
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+    Vnew[i] = Vnew[i] / gnew;                                                         // :118
+    Znew[i] = Znew[i] / gnew;                                                         // :119
+    const double w = ((Z[i] - a2 * W[i]) - a3 * Wold[i]) / a1;                        // :128
+    Wnew[i] = w;
+    x[i] = x[i] + step * w;                                                           // :129
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const double br_new = bp < 0.0 ? -1.0 : fabs(snew) * br;                          // :116 DomainError ; :133
+    st_next[MR_GAMMA] = gnew;      st_next[MR_GAMMA_OLD] = g;                         // :140 swap3(gamma_new, gamma, gamma_old)
+    st_next[MR_C] = cnew;          st_next[MR_C_OLD] = c;                             // :141
+    st_next[MR_S] = snew;          st_next[MR_S_OLD] = s;                             // :142
+    st_next[MR_ETA] = -snew * eta;                                                    // :130
+    st_next[MR_BETA_R] = br_new;
+    if (value) {
+      __hip_atomic_store(value, br_new, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(seq, want, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+// minres start-up state (:99-106): gamma = sqrt(beta_p), gamma_old = 1, c = cold = 1, s = sold = 0, eta = gamma, beta_r
+__global__ void minres_init_kernel(double *__restrict__ st, double gamma, double beta_r)
+{
+  st[MR_GAMMA] = gamma; st[MR_GAMMA_OLD] = 1.0; st[MR_C] = 1.0; st[MR_C_OLD] = 1.0;
+  st[MR_S] = 0.0; st[MR_S_OLD] = 0.0; st[MR_ETA] = gamma; st[MR_BETA_R] = beta_r;
+}
+
 // dx = omega*(dinv.*r) ; optionally x += dx     (unfused Jacobi apply, gmg_precond_apply)
 __global__ void jacobi_apply_kernel(int64_t n, const double *__restrict__ dinv, const double *__restrict__ r,
                                     double *__restrict__ dx)

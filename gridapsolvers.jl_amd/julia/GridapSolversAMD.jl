@@ -34,8 +34,9 @@ using GridapSolvers
 using GridapSolvers.SolverInterfaces: ConvergenceLog, SolverTolerances
 using GridapSolvers.LinearSolvers: RichardsonSmoother, JacobiLinearSolver
 
-export HipGMGLinearSolver, HipCGSolver, HipFGMRESSolver, PatchTable, HipPatchProlongation
+export HipGMGLinearSolver, HipCGSolver, HipFGMRESSolver, HipMINRESSolver, PatchTable, HipPatchProlongation
 export HipRichardsonLinearSolver, HipBlockTriangularSolver, HipBlockDiagonalSolver, HipBlockFGMRESSolver, block_mul!, block_cg_solve!
+export block_minres_solve!
 
 const libgmgamd = get(ENV, "LIBGMGAMD", joinpath(@__DIR__, "..", "libgmgamd.so"))
 
@@ -440,10 +441,20 @@ function HipFGMRESSolver(m, Pr::HipGMGLinearSolver; restart=false, m_add=1, maxi
   return HipFGMRESSolver(m, restart, m_add, Pr, ConvergenceLog(name,tols,verbose=verbose))
 end
 
+# MINRESSolver(;Pl=gmg) on the device: MINRESSolvers.jl:16-20 (defaults), :75-148 (solve!).  Pl must be symmetric positive definite.
+struct HipMINRESSolver{A} <: Gridap.Algebra.LinearSolver
+  Pl  :: A
+  log :: ConvergenceLog{Float64}
+end
+function HipMINRESSolver(; Pl::HipGMGLinearSolver, maxiter=1000, atol=1e-12, rtol=1.e-6, verbose=false, name="MINRES-MI355X")
+  tols = SolverTolerances{Float64}(maxiter=maxiter,atol=atol,rtol=rtol)      # MINRESSolvers.jl:16-20
+  return HipMINRESSolver(Pl, ConvergenceLog(name,tols,verbose=verbose))
+end
+
 struct HipKrylovSymbolicSetup{A} <: Gridap.Algebra.SymbolicSetup
   solver :: A
 end
-Gridap.Algebra.symbolic_setup(s::Union{HipCGSolver,HipFGMRESSolver}, ::AbstractMatrix) = HipKrylovSymbolicSetup(s)
+Gridap.Algebra.symbolic_setup(s::Union{HipCGSolver,HipFGMRESSolver,HipMINRESSolver}, ::AbstractMatrix) = HipKrylovSymbolicSetup(s)
 
 mutable struct HipKrylovNumericalSetup{A,B} <: Gridap.Algebra.NumericalSetup
   solver :: A
@@ -484,6 +495,21 @@ function Gridap.Algebra.solve!(x::Vector{Float64}, ns::HipKrylovNumericalSetup{<
     check(h, ccall((:gmg_fgmres_solve, libgmgamd), Cint,
       (Ptr{Cvoid},Ptr{Float64},Ptr{Float64},Cint,Cint,Cint,Cint,Cint,Float64,Float64,Cint,Ref{GmgResult},Ptr{Float64},Cint),
       h, b, x, GMG_MEM_HOST, s.m, s.restart ? 1 : 0, s.m_add, tols.maxiter, tols.atol, tols.rtol, 1, res, hist, length(hist)))
+  end
+  _fill_log!(s.log, res[], hist)
+  return x
+end
+
+function Gridap.Algebra.solve!(x::Vector{Float64}, ns::HipKrylovNumericalSetup{<:HipMINRESSolver}, b::Vector{Float64})
+  s, h = ns.solver, ns.P_ns.handle
+  tols = s.log.tols
+  res  = Ref(GmgResult(0,0,0.0,0.0))
+  hist = zeros(tols.maxiter+1)
+  _maybe_pin!(ns.P_ns, x, b)
+  GC.@preserve x b hist begin
+    check(h, ccall((:gmg_minres_solve, libgmgamd), Cint,
+      (Ptr{Cvoid},Ptr{Float64},Ptr{Float64},Cint,Cint,Float64,Float64,Cint,Ref{GmgResult},Ptr{Float64},Cint),
+      h, b, x, GMG_MEM_HOST, tols.maxiter, tols.atol, tols.rtol, 1, res, hist, length(hist)))
   end
   _fill_log!(s.log, res[], hist)
   return x
@@ -686,6 +712,18 @@ function block_cg_solve!(x::AbstractVector, ns::HipBlockNumericalSetup, b::Abstr
   GC.@preserve xf bf hist check_block(ns.handle, ccall((:gmg_block_cg_solve, libgmgamd), Cint,
     (Ptr{Cvoid},Ptr{Float64},Ptr{Float64},Cint,Cint,Float64,Float64,Cint,Cint,Ref{GmgResult},Ptr{Float64},Cint),
     ns.handle, bf, xf, GMG_MEM_HOST, tols.maxiter, tols.atol, tols.rtol, flexible ? 1 : 0, 1, res, hist, length(hist)))
+  _fill_log!(log, res[], hist)
+  return x
+end
+
+# MINRESSolver(;Pl=P) on a symmetric block system with an SPD block preconditioner (BlockDiagonalSolver with SPD blocks)
+function block_minres_solve!(x::AbstractVector, ns::HipBlockNumericalSetup, b::AbstractVector, log::ConvergenceLog)
+  tols = log.tols
+  res  = Ref(GmgResult(0,0,0.0,0.0)); hist = zeros(tols.maxiter+1)
+  xf, bf = _flat(x), _flat(b)
+  GC.@preserve xf bf hist check_block(ns.handle, ccall((:gmg_block_minres_solve, libgmgamd), Cint,
+    (Ptr{Cvoid},Ptr{Float64},Ptr{Float64},Cint,Cint,Float64,Float64,Cint,Ref{GmgResult},Ptr{Float64},Cint),
+    ns.handle, bf, xf, GMG_MEM_HOST, tols.maxiter, tols.atol, tols.rtol, 1, res, hist, length(hist)))
   _fill_log!(log, res[], hist)
   return x
 end
@@ -990,12 +1028,20 @@ function Gridap.Algebra.solve!(x::PA.PVector, ns::HipKrylovNumericalSetup{<:HipC
   PA.consistent!(x) |> wait
   return x
 end
+function Gridap.Algebra.solve!(x::PA.PVector, ns::HipKrylovNumericalSetup{<:HipMINRESSolver,<:HipDistributedGMGNumericalSetup}, b::PA.PVector)
+  xo = PA.getany(PA.own_values(x)); bo = PA.getany(PA.own_values(b))
+  xv, bv = Vector{Float64}(xo), Vector{Float64}(bo)
+  solve!(xv, HipKrylovNumericalSetup(ns.solver, ns.P_ns.inner), bv)          # gmg_minres_solve: dots are all-reduced in the library
+  copyto!(xo, xv)
+  PA.consistent!(x) |> wait
+  return x
+end
 function Gridap.Algebra.numerical_setup(ss::HipKrylovSymbolicSetup, A::PA.PSparseMatrix; kwargs...)
   P = ss.solver isa HipFGMRESSolver ? ss.solver.Pr : ss.solver.Pl
   return HipKrylovNumericalSetup(ss.solver, numerical_setup(symbolic_setup(P,A),A; kwargs...))
 end
 Gridap.Algebra.symbolic_setup(s::HipGMGLinearSolver, ::PA.PSparseMatrix) = HipGMGSymbolicSetup(s)
-Gridap.Algebra.symbolic_setup(s::Union{HipCGSolver,HipFGMRESSolver}, ::PA.PSparseMatrix) = HipKrylovSymbolicSetup(s)
+Gridap.Algebra.symbolic_setup(s::Union{HipCGSolver,HipFGMRESSolver,HipMINRESSolver}, ::PA.PSparseMatrix) = HipKrylovSymbolicSetup(s)
 
 # Distributed block systems (BlockPMatrix / BlockPVector): the block handle gets its own communicator and one exchange plan
 # per block; blocks are passed as local rows with [own | ghost] columns (_local_operator), vectors as owned values.

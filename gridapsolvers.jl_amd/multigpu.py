@@ -382,6 +382,19 @@ class DistributedGMG:
         log._fill(res, hist)
         return log
 
+    def minres_solve(self, b, x, maxiter=20, atol=1e-14, rtol=1e-6):
+        """MINRESSolver(;Pl=this GMG) on the partitioned system (MINRESSolvers.jl:75-148)"""
+        log = ConvergenceLog("MINRES", maxiter, atol, rtol)
+        pb, ms, _kb = _vec(b, self.n_own)
+        px, ms2, _kx = _vec(x, self.n_own, writable=True)
+        assert ms == ms2
+        res = abi.Result()
+        hist = np.zeros(maxiter + 1)
+        abi.check(self.h, self._lib.gmg_minres_solve(self.h, pb, px, ms, maxiter, atol, rtol, 1,
+                                                     C.byref(res), C.c_void_p(hist.ctypes.data), hist.size))
+        log._fill(res, hist)
+        return log
+
     def set_stream(self, stream=None):
         """gmg_set_stream: the handle's work on the caller's HIP stream (torch.cuda.Stream, integer hipStream_t, None = its own)"""
         abi.check(self.h, self._lib.gmg_set_stream(self.h, abi.stream_arg(stream)))
@@ -851,6 +864,18 @@ class DistributedBlockSolver:
         res = abi.Result()
         hist = np.zeros(maxiter + 1)
         abi.check_block(self.h, self._lib.gmg_block_fgmres_solve(self.h, pb, px, ms, m, 0, 1, maxiter, atol, rtol, 1, C.byref(res),
+                                                                 C.c_void_p(hist.ctypes.data), hist.size))
+        log._fill(res, hist)
+        return log
+
+    def minres_solve(self, b, x, maxiter=100, atol=1e-10, rtol=1e-12):
+        """MINRESSolver(;Pl=this block preconditioner) on the partitioned block system (MINRESSolvers.jl:75-148)"""
+        log = ConvergenceLog("MINRES", maxiter, atol, rtol)
+        pb, ms, _k1 = _vec(b, self.n)
+        px, ms2, _k2 = _vec(x, self.n, writable=True)
+        res = abi.Result()
+        hist = np.zeros(maxiter + 1)
+        abi.check_block(self.h, self._lib.gmg_block_minres_solve(self.h, pb, px, ms, maxiter, atol, rtol, 1, C.byref(res),
                                                                  C.c_void_p(hist.ctypes.data), hist.size))
         log._fill(res, hist)
         return log

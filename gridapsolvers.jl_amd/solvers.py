@@ -14,6 +14,7 @@ julia/GridapSolversAMD.jl.
     GMGLinearSolver(mats,P,R;...)   GMGLinearSolvers.jl:48-69       GMGLinearSolver
     CGSolver(Pl;...)                Krylov/CGSolvers.jl:19          CGSolver
     FGMRESSolver(m,Pr;...)          Krylov/FGMRESSolvers.jl:26      FGMRESSolver
+    MINRESSolver(;Pl,...)           Krylov/MINRESSolvers.jl:16      MINRESSolver
     BlockDiagonalSolver(blocks,solvers)   BlockSolvers/BlockDiagonalSolvers.jl:20-45     BlockDiagonalSolver
     BlockTriangularSolver(blocks,solvers,coeffs,half)  BlockTriangularSolvers.jl:55-85    BlockTriangularSolver
     LinearSystemBlock / MatrixBlock BlockSolvers/BlockSolverInterfaces.jl            same names
@@ -34,7 +35,7 @@ from . import abi
 
 __all__ = [
     "JacobiLinearSolver", "RichardsonSmoother", "PatchSolver", "BlockJacobiSolver", "LUSolver",
-    "GMGLinearSolver", "CGSolver", "FGMRESSolver", "ConvergenceLog", "PatchProlongationOperator",
+    "GMGLinearSolver", "CGSolver", "FGMRESSolver", "MINRESSolver", "ConvergenceLog", "PatchProlongationOperator",
     "RichardsonLinearSolver", "BlockDiagonalSolver", "BlockTriangularSolver", "LinearSystemBlock", "MatrixBlock", "LinearSolverFromSmoother",
     "symbolic_setup", "numerical_setup", "numerical_setup_", "solve_", "mul_",
     "SOLVER_CONVERGED_ATOL", "SOLVER_CONVERGED_RTOL", "SOLVER_DIVERGED_MAXITER", "SOLVER_DIVERGED_BREAKDOWN",
@@ -223,6 +224,17 @@ class FGMRESSolver:
             raise NotImplementedError("FGMRES Pl on the device: JacobiLinearSolver() or LinearSolverFromSmoother(...)")
         self.Pl = Pl
         self.m, self.Pr, self.restart, self.m_add = int(m), Pr, bool(restart), int(m_add)
+        self.log = ConvergenceLog(name, maxiter, atol, rtol)
+
+
+class MINRESSolver:
+    """MINRESSolver(; Pl=nothing, maxiter=1000, atol=1e-12, rtol=1e-6) -- MINRESSolvers.jl:16.  Pl must be symmetric positive
+    definite (the reference's docstring): a GMGLinearSolver, (None | JacobiLinearSolver() | LinearSolverFromSmoother, gmg) as for
+    CGSolver, or a BlockDiagonalSolver (a BlockTriangularSolver is accepted, as by the reference, but is outside MINRES's
+    assumptions)."""
+
+    def __init__(self, Pl=None, maxiter=1000, atol=1e-12, rtol=1.0e-6, verbose=0, name="MINRES"):
+        self.Pl = Pl
         self.log = ConvergenceLog(name, maxiter, atol, rtol)
 
 
@@ -795,7 +807,7 @@ class _KrylovSymbolicSetup:
 
 
 class _KrylovNumericalSetup:
-    """CGNumericalSetup / FGMRESNumericalSetup: holds the preconditioner's numerical
+    """CGNumericalSetup / FGMRESNumericalSetup / MINRESNumericalSetup: holds the preconditioner's numerical
     setup (CGSolvers.jl:50-55, FGMRESSolvers.jl:96-102)."""
 
     def __init__(self, solver, A, device_id=None):
@@ -829,7 +841,7 @@ def symbolic_setup(solver, A=None):
     """Gridap.Algebra.symbolic_setup(solver, A)."""
     if isinstance(solver, GMGLinearSolver):
         return GMGSymbolicSetup(solver)
-    if isinstance(solver, (CGSolver, FGMRESSolver, RichardsonLinearSolver)):
+    if isinstance(solver, (CGSolver, FGMRESSolver, MINRESSolver, RichardsonLinearSolver)):
         return _KrylovSymbolicSetup(solver)
     if isinstance(solver, (BlockDiagonalSolver, BlockTriangularSolver)):
         return BlockSymbolicSetup(solver)
@@ -892,6 +904,9 @@ def solve_(x, ns, b):
         if isinstance(s, CGSolver):
             abi.check_block(g.h, g._lib.gmg_block_cg_solve(g.h, pb, px, ms, log.maxiter, log.atol, log.rtol, int(s.flexible),
                                                            ns.pc_kind, C.byref(res), C.c_void_p(hist.ctypes.data), hist.size))
+        elif isinstance(s, MINRESSolver):
+            abi.check_block(g.h, g._lib.gmg_block_minres_solve(g.h, pb, px, ms, log.maxiter, log.atol, log.rtol, ns.pc_kind,
+                                                               C.byref(res), C.c_void_p(hist.ctypes.data), hist.size))
         else:
             abi.check_block(g.h, g._lib.gmg_block_fgmres_solve(g.h, pb, px, ms, s.m, int(s.restart), s.m_add, log.maxiter,
                                                                log.atol, log.rtol, ns.pc_kind, C.byref(res),
@@ -913,6 +928,9 @@ def solve_(x, ns, b):
         if isinstance(s, CGSolver):
             abi.check(g.h, g._lib.gmg_cg_solve(g.h, pb, px, ms, log.maxiter, log.atol, log.rtol, int(s.flexible), ns.pc_kind,
                                                C.byref(res), C.c_void_p(hist.ctypes.data), hist.size))
+        elif isinstance(s, MINRESSolver):
+            abi.check(g.h, g._lib.gmg_minres_solve(g.h, pb, px, ms, log.maxiter, log.atol, log.rtol, ns.pc_kind,
+                                                   C.byref(res), C.c_void_p(hist.ctypes.data), hist.size))
         elif isinstance(s, RichardsonLinearSolver):
             abi.check(g.h, g._lib.gmg_richardson_solve(g.h, pb, px, ms, s.omega, log.maxiter, log.atol, log.rtol, ns.pc_kind,
                                                        C.byref(res), C.c_void_p(hist.ctypes.data), hist.size))

@@ -317,6 +317,13 @@ GMG_API int gmg_fgmres_solve(gmg_handle_t h, const double *b, double *x, int mem
 GMG_API int gmg_fgmres_solve_pl(gmg_handle_t h, const double *b, double *x, int memspace,
                                 int m, int restart, int m_add, int maxiter, double atol, double rtol,
                                 int use_precond, int use_precond_left, gmg_result *res, double *hist, int hist_cap);
+/* solve!(x,ns::MINRESNumericalSetup,b): Krylov/MINRESSolvers.jl:75-148 (MINRESSolver(;Pl,maxiter,atol,rtol), :16).
+ * use_precond as in gmg_cg_solve (Pl = nothing / this GMG / Jacobi / the finest pre-smoother).  The preconditioner must be
+ * symmetric positive definite (the reference's docstring, :8-9): dot(Pl(r), r) <= 0 at start-up (:97) or < 0 inside the loop
+ * (sqrt, :116) returns GMG_ERR_INVALID.  x = initial guess on entry; the history holds the 2-norm of the preconditioned
+ * residual.  Nine work vectors are allocated on the handle by the first call. */
+GMG_API int gmg_minres_solve(gmg_handle_t h, const double *b, double *x, int memspace, int maxiter, double atol, double rtol,
+                             int use_precond, gmg_result *res, double *hist, int hist_cap);
 /* solve!(x,ns::RichardsonLinearNumericalSetup,b): RichardsonLinearSolvers.jl:79-106, scalar omega;
  * use_precond as in gmg_cg_solve (Pl = nothing / this GMG / Jacobi / the finest pre-smoother). */
 GMG_API int gmg_richardson_solve(gmg_handle_t h, const double *b, double *x, int memspace, double omega,
@@ -564,6 +571,11 @@ GMG_API int gmg_block_fgmres_solve(gmg_block_handle_t h, const double *b, double
                                    gmg_result *res, double *hist, int hist_cap);
 GMG_API int gmg_block_cg_solve(gmg_block_handle_t h, const double *b, double *x, int memspace, int maxiter, double atol,
                                double rtol, int flexible, int use_precond, gmg_result *res, double *hist, int hist_cap);
+/* MINRESSolver(;Pl=P) on the block system with P = this block preconditioner (use_precond=1) or nothing (0):
+ * MINRESSolvers.jl:75-148.  MINRES assumes a symmetric positive definite P (BlockDiagonalSolver with SPD blocks); a
+ * block-triangular P is not rejected -- the reference does not reject it -- but lies outside those assumptions. */
+GMG_API int gmg_block_minres_solve(gmg_block_handle_t h, const double *b, double *x, int memspace, int maxiter, double atol,
+                                   double rtol, int use_precond, gmg_result *res, double *hist, int hist_cap);
 /* ConvergenceLog of the last solve of diagonal block i (GMG / CG blocks) */
 GMG_API int gmg_block_diag_log(gmg_block_handle_t h, int i, gmg_result *res);
 
