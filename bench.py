@@ -12,7 +12,7 @@ The JSON line has the SAME shape at every --gpus N (key <-> leg):
     cpu_baseline                              the CPU oracle (oracle/, a cited port of the reference algorithm) on the host cores
 N = 1  BASELINE configs[1]: 128^3 cells, Q1, 4 levels, Richardson(Jacobi,10,2/3) pre = post, exact coarse solve,
        CG(maxiter=20, atol=1e-14, rtol=1e-6), rhs = the reference test problem u = x1 + x2
-       (test/LinearSolvers/GMGTests.jl:52,109-124,204-213).  Further legs of the same run:
+       (test/LinearSolvers/GMGTests.jl:52,109-124,204-213).  Further legs of a --full run:
          variable_coefficient   kappa(x) grad u . grad v: every row's values distinct (SELL-O: 8 B/nnz)
          weak_scaling_ref       the per-GPU problem of the N > 1 runs (288^3, 6 levels) on this one GPU; its value is also the
                                 top-level `weak_anchor_value` -- what value / N of an N > 1 line is to be held against
@@ -27,14 +27,19 @@ N = 1  BASELINE configs[1]: 128^3 cells, Q1, 4 levels, Richardson(Jacobi,10,2/3)
 N > 1  BASELINE configs[3]: 288^3 cells per GPU (576^3 on 2x2x2), 6 levels, box row partition, halo exchange and
        scalar all-reduces over RCCL; launched by torch.distributed.run, or by bench.py itself when WORLD_SIZE is unset.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--legs default,generic,varcoef,weak_ref,host_io,config3,config5,rccl_loopback,cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                    [--full [--legs default,generic,varcoef,weak_ref,host_io,config3,config5,rccl_loopback,cpu]]
                     [--allow-degraded]   (N > 1 only: without it a run whose transport is not RCCL on all N ranks exits non-zero)
+
+A plain run sets up the default leg, warms up, times the steps and prints the line: nothing else.  --full adds everything beyond
+the headline figure: the further legs (all of them unless --legs / --no-* pick), the CPU baseline and the oracle checks, the
+default leg's per-level sweep profiles, the streaming-ceiling probes and its l2 error.
 
          rccl_loopback          functional: the 2x2x2 partition of a Q1 problem folded onto this GPU, solved through the product's halo
                                 exchange and all-reduces over RCCL (one real rank, self messages); bitwise against the host transport
 
-Prints ONE JSON line (rank 0) of <= 4 KB -- value, ms_per_step and roofline all describe the default leg -- and writes everything
-else the run measured to profiles/bench_legs_latest.json (GMG_BENCH_DETAILS=<file> redirects it)."""
+Prints ONE JSON line (rank 0) of <= 4 KB -- value, ms_per_step and roofline all describe the default leg.  Everything else the run
+measured goes to GMG_BENCH_DETAILS=<file> if set, and a --full run without it writes profiles/bench_legs_latest.json."""
 from __future__ import annotations
 
 import argparse
@@ -83,7 +88,10 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--cells", type=int, default=None, help="cells per direction per GPU (default: 128 at N=1, 288 at N>1)")
     ap.add_argument("--levels", type=int, default=None, help="GMG levels (default: 4 at N=1, 6 at N>1)")
-    ap.add_argument("--legs", default="all", help="comma list of " + ",".join(ALL_LEGS) + " (default: all; `default` always runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="run everything beyond the headline figure too: the further legs (--legs, --no-*), the CPU baseline and oracle checks, "
+                         "the per-level sweep profiles, the streaming-ceiling probes, the l2 error and the details file in profiles/")
+    ap.add_argument("--legs", default="all", help="with --full: comma list of " + ",".join(ALL_LEGS) + " (default: all; `default` always runs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-varcoef", action="store_true", help="skip the variable-coefficient leg")
     ap.add_argument("--no-weak-ref", action="store_true", help="skip the weak-scaling reference leg (the N > 1 per-GPU problem on one GPU)")
@@ -119,6 +127,11 @@ def parse():
                       ("no_host_io", "host_io"), ("no_config3", "config3"), ("no_config5", "config5")):
         if getattr(args, flag):
             legs.discard(leg)
+    if not args.full:
+        # a plain run times the headline leg and nothing else; the --no-* flags have nothing left to drop
+        if args.legs != "all" and legs - {"default"}:
+            raise SystemExit(f"--legs {args.legs}: the legs beyond `default` run with --full only")
+        legs = set()
     legs.add("default")
     args.legset = legs
     args.no_generic = "generic" not in legs          # (multigpu.run_bench reads this)
@@ -390,12 +403,13 @@ def _short(s, n):
     return s if len(s) <= n else s[: n - 3] + "..."
 
 
-def emit(out):
+def emit(out, full_run):
     """Rank 0: write EVERYTHING this run measured (all legs, notes, per-level and per-form tables) to profiles/bench_legs_latest.json (and a
     copy under gpurun_out/, the directory gpurun brings back), then print ONE line of <= 4 KB whose value / ms_per_step / roofline all
     describe the SAME leg -- the default leg: the product as shipped, storage layout chosen by gmg_setup.  Its roofline prices the dominant
     kernel with the bytes that layout moves per launch (every operand once, no cache credit) next to the PMC-measured HBM traffic; the
-    generic leg (the 12 B/nnz stream SURVEY 8(d)'s model is written for) rides along as one small object of its own."""
+    generic leg (the 12 B/nnz stream SURVEY 8(d)'s model is written for) rides along as one small object of its own.
+    A plain run (no --full) writes the details only where GMG_BENCH_DETAILS points."""
     full = dict(out)
     rc, rg = full.pop("roofline_compressed", None), full.pop("roofline", None)
     compressed = bool(rc) and rc.get("speedup_vs_12B_per_nnz_model", 2.0) > 1.0 + 1e-9
@@ -405,6 +419,8 @@ def emit(out):
     # GMG_BENCH_DETAILS=<file>: the details go there and nowhere else (tests: keeps the tracked profiles/ copy out of their way)
     targets = [os.environ["GMG_BENCH_DETAILS"]] if os.environ.get("GMG_BENCH_DETAILS") else \
         [os.path.join(ROOT, d, "bench_legs_latest.json") for d in ("profiles", "gpurun_out")]
+    if not full_run and not os.environ.get("GMG_BENCH_DETAILS"):
+        targets = []
     for t in targets:
         try:
             os.makedirs(os.path.dirname(t) or ".", exist_ok=True)
@@ -585,7 +601,7 @@ def main():
         D = leg(H, b, nlev, steps, warmup)
         ns = D["ns"]
         x = D["xd"].cpu().numpy()
-        R = dict(H=H, b=b, D=D, x=x, n=n, nc=nc, t_asm=t_asm, l2=po.l2_error_sq(nc, 1, x) if args.rhs == "lin" else None)
+        R = dict(H=H, b=b, D=D, x=x, n=n, nc=nc, t_asm=t_asm, l2=po.l2_error_sq(nc, 1, x) if args.rhs == "lin" and args.full else None)
         R["model_bytes"] = ns.P_ns.model_bytes()
         R["device_bytes"] = ns.P_ns.device_bytes()
         compressed = D["fmt"]["row_patterns"] or D["fmt"]["value_dictionary"] or D["fmt"]["idx16"]
@@ -633,6 +649,8 @@ def main():
     if world > 1:
         from gridapsolvers_jl_amd import multigpu
         out = multigpu.run_bench(args, rank, world, local_rank)
+        if not args.full:
+            out["roofline"] = {"leg": "generic", "skipped": "runs with --full"}
         if rank == 0:
             if "cpu" in legs:
                 # the per-GPU problem of this run (args.cells^3 cells, args.levels levels) on the host cores: a bounded number of solves
@@ -660,7 +678,7 @@ def main():
                 out["weak_anchor_value"] = None
         dist.barrier()
         if rank == 0:
-            emit(out)
+            emit(out, args.full)
         dist.destroy_process_group()
         return
 
@@ -671,33 +689,35 @@ def main():
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, x, D["hist"])       # x and the history as the last timed solve left them
     vbytes, cgbytes = R["model_bytes"]
-    # the same sweep kernel on the coarser levels (report per level; these fit the Infinity Cache)
-    per_level = []
-    ns.P_ns.set_option("prof_stride", 7)     # (untimed runs: dense sampling)
-    for lv in range(1, nlev - 1):
-        ns.P_ns.profile(lv, True)
-        for _ in range(2):
-            D["step"]()
-        torch.cuda.synchronize()
-        stl = ns.P_ns.kernel_stats()
-        ns.P_ns.profile(lv, False)
-        if stl["launches"]:
-            avg_l = stl["total_ms"] / stl["launches"]
-            fused = int(stl.get("fused_passes", 0))
-            rec = {"level": lv, "rows": int(stl["rows"]), "nnz": int(stl["nnz"]), "avg_sweep_ms": avg_l,
-                   "one_launch_per_pass": bool(fused), "model_12B_nnz_GBs": stl["alg_bytes"] / (avg_l * 1e-3) / 1e9}
-            if fused:
-                # sells_smooth_kernel: r, x, 1/diag stay in registers for the whole pass -- only s (8 B/row written, gathered
-                # back through L2/MALL) moves per sweep, so a bytes-per-sweep rate would be meaningless here
-                rec["avg_pass_ms"] = stl["total_ms"] / fused
-                rec["note"] = "whole smoothing pass in one launch; time per sweep = pass time / sweeps"
-            else:
-                rec["layout_GBs"] = stl["layout_bytes"] / (avg_l * 1e-3) / 1e9
-            per_level.append(rec)
-    copy_GBs = ns.P_ns.stream_probe(1 << 30, 10)    # measured streaming ceiling of this box, same run, library's own copy kernel
-    read_GBs = ns.P_ns.stream_probe_read(1 << 30, 10)   # ... and of a read-only stream (the sweeps read far more than they write)
-    R["roofline_compressed"]["coarser_levels"] = per_level
-    R["roofline_compressed"]["frac_of_copy_ceiling"] = (R["roofline_compressed"]["achieved"] / copy_GBs) if R["roofline_compressed"]["achieved"] else None
+    copy_GBs = read_GBs = None
+    if args.full:
+        # the same sweep kernel on the coarser levels (report per level; these fit the Infinity Cache)
+        per_level = []
+        ns.P_ns.set_option("prof_stride", 7)     # (untimed runs: dense sampling)
+        for lv in range(1, nlev - 1):
+            ns.P_ns.profile(lv, True)
+            for _ in range(2):
+                D["step"]()
+            torch.cuda.synchronize()
+            stl = ns.P_ns.kernel_stats()
+            ns.P_ns.profile(lv, False)
+            if stl["launches"]:
+                avg_l = stl["total_ms"] / stl["launches"]
+                fused = int(stl.get("fused_passes", 0))
+                rec = {"level": lv, "rows": int(stl["rows"]), "nnz": int(stl["nnz"]), "avg_sweep_ms": avg_l,
+                       "one_launch_per_pass": bool(fused), "model_12B_nnz_GBs": stl["alg_bytes"] / (avg_l * 1e-3) / 1e9}
+                if fused:
+                    # sells_smooth_kernel: r, x, 1/diag stay in registers for the whole pass -- only s (8 B/row written, gathered
+                    # back through L2/MALL) moves per sweep, so a bytes-per-sweep rate would be meaningless here
+                    rec["avg_pass_ms"] = stl["total_ms"] / fused
+                    rec["note"] = "whole smoothing pass in one launch; time per sweep = pass time / sweeps"
+                else:
+                    rec["layout_GBs"] = stl["layout_bytes"] / (avg_l * 1e-3) / 1e9
+                per_level.append(rec)
+        copy_GBs = ns.P_ns.stream_probe(1 << 30, 10)    # measured streaming ceiling of this box, same run, library's own copy kernel
+        read_GBs = ns.P_ns.stream_probe_read(1 << 30, 10)   # ... and of a read-only stream (the sweeps read far more than they write)
+        R["roofline_compressed"]["coarser_levels"] = per_level
+        R["roofline_compressed"]["frac_of_copy_ceiling"] = (R["roofline_compressed"]["achieved"] / copy_GBs) if R["roofline_compressed"]["achieved"] else None
 
     out = {
         "metric": "DoFs/sec, CG+GMG V-cycle on 3D Poisson Q1",
@@ -748,7 +768,7 @@ def main():
         roofline = roof(D, "alg_bytes", "SURVEY 8(d): B_sweep = 12 Z + 68 N", leg="default (no structure found: the generic layout)")
         roofline["pairs_with"] = "value / ms_per_step"
     else:
-        roofline = {"leg": "generic", "skipped": "--no-generic / --legs"}
+        roofline = {"leg": "generic", "skipped": "--no-generic / --legs" if args.full else "runs with --full"}
     if G is not None:
         roofline["measured_copy_ceiling_GBs"] = copy_GBs
         roofline["frac_of_copy_ceiling"] = roofline["achieved"] / copy_GBs if roofline.get("achieved") else None
@@ -875,7 +895,7 @@ def main():
                 out["config3"]["cpu_baseline"] = {"error": str(e)[-300:]}
     if isinstance(out.get("config3"), dict) and isinstance(out["config3"].get("cpu_check"), dict):
         out["config3"]["cpu_check"].pop("gpu_x", None)
-    emit(out)
+    emit(out, args.full)
 
 
 def config3_leg(torch, pkg, args):

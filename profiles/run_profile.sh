@@ -14,7 +14,7 @@ ROOTDIR=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOTDIR/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 5 --warmup 2 $*"
+ARGS="--full --steps 5 --warmup 2 $*"   # (--full: the legs picked by --legs, and the stream probe the counters are calibrated on)
 # (the printed line is a <= 4 KB extract since round 6: the sweep signatures summarize.py needs are in the details file of the trace pass)
 export GMG_BENCH_DETAILS=$OUT/legs_trace.json
 timeout -k 5 1500 rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench -- python3 $ROOTDIR/bench.py $ARGS > $OUT/trace.log 2>&1

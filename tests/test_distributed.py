@@ -433,7 +433,7 @@ def test_bench_multi_rank_path_with_overlapping_levels(finest, tmp_path):
     root = os.path.dirname(HERE)
     out = _run_with_fresh_port(lambda port: [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                                              "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--cells", "32", "--levels", "4",
-                                             "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], env=env, cwd=root, capture_output=True, text=True, timeout=600)
+                                             "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"], env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-1500:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][0]
     assert len(line) <= 4096 and json.loads(line)["details"] == str(tmp_path / "legs.json")
@@ -454,7 +454,7 @@ def test_bench_multi_rank_path_runs_end_to_end_on_one_gpu(tmp_path):
     root = os.path.dirname(HERE)
     out = _run_with_fresh_port(lambda port: [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                                              "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--cells", "32", "--levels", "3",
-                                             "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], env=env, cwd=root, capture_output=True, text=True, timeout=600)
+                                             "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"], env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-1500:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-1500:]

@@ -105,3 +105,29 @@ def test_stokes_inputs_by_stencil_replication_equal_the_assembly(pkg):
         for key in ("star_patches", "interior_patches"):
             for (p1, d1), (p2, d2) in zip(H1[key], H2[key]):
                 assert np.array_equal(p1, p2) and np.array_equal(d1, d2)
+
+
+def _bench_args(monkeypatch, *argv):
+    import importlib.util
+    import os
+    import sys
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
+    spec = importlib.util.spec_from_file_location("_bench_under_test", path)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+    return bench, bench.parse()
+
+
+def test_bench_plain_run_times_the_default_leg_only(monkeypatch):
+    """A plain `bench.py` runs the headline leg alone; --full runs every leg, or those --legs / --no-* pick; legs beyond the default one
+    without --full are refused rather than dropped."""
+    bench, a = _bench_args(monkeypatch, "--steps", "3", "--warmup", "1")
+    assert not a.full and a.legset == {"default"} and a.no_generic and (a.steps, a.warmup) == (3, 1)
+    assert _bench_args(monkeypatch, "--legs", "default", "--no-cpu-baseline", "--no-generic")[1].legset == {"default"}
+    assert _bench_args(monkeypatch, "--full")[1].legset == set(bench.ALL_LEGS)
+    a = _bench_args(monkeypatch, "--full", "--legs", "default,config3,cpu", "--no-cpu-baseline")[1]
+    assert a.legset == {"default", "config3"} and a.no_generic
+    assert not _bench_args(monkeypatch, "--full", "--no-varcoef")[1].no_generic
+    with pytest.raises(SystemExit):
+        _bench_args(monkeypatch, "--legs", "default,config3")

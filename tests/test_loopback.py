@@ -150,7 +150,7 @@ def test_bench_prints_exactly_one_line_on_stdout_even_when_rccl_prints_its_banne
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, NCCL_DEBUG="VERSION", GMG_BENCH_DETAILS=str(tmp_path / "legs.json"), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--legs", "default,rccl_loopback", "--cells", "32", "--levels", "3",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--legs", "default,rccl_loopback", "--cells", "32", "--levels", "3",
                           "--loopback-cells", "16", "--loopback-levels", "3", "--steps", "2", "--warmup", "1"],
                          env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-1500:]
@@ -160,6 +160,31 @@ def test_bench_prints_exactly_one_line_on_stdout_even_when_rccl_prints_its_banne
     lb = d["rccl_loopback"]
     assert lb["rccl_ranks"] == 1 and lb["virtual_ranks"] == 8 and lb["bitwise_equal_host_transport"] is True and lb["exchanges_per_solve"] > 20
     assert "RCCL version" in out.stderr          # (the banner exists -- and went to stderr)
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_measures_the_headline_leg_alone(tmp_path):
+    """`bench.py` without --full: set-up, warm-up and timed steps of the default leg, --dump-outputs, the line -- and nothing else: no
+    further leg, CPU baseline, per-level profile or streaming probe; the details file only where GMG_BENCH_DETAILS points."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, GMG_BENCH_DETAILS=str(tmp_path / "legs.json"))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--cells", "32", "--levels", "3", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "dump")], env=env, cwd=root, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-1500:]
+    lines = out.stdout.splitlines()
+    assert len(lines) == 1 and len(lines[0]) <= 4096, out.stdout[-800:]
+    ln = json.loads(lines[0])
+    assert (ln["steps"], ln["warmup"], ln["unit"], ln["dtype"], ln["higher_is_better"]) == (3, 1, "DoFs/s", "f64", True)
+    assert ln["value"] == pytest.approx(ln["config"]["dofs"] / (ln["ms_per_step"] * 1e-3), rel=1e-12) and "cpu_baseline" not in ln
+    d = json.load(open(tmp_path / "legs.json"))
+    assert not set(d) & {"value_generic", "variable_coefficient", "weak_scaling_ref", "host_io", "config3", "config5", "rccl_loopback", "cpu_baseline"}
+    assert d["roofline"]["leg"] == "default" and "coarser_levels" not in d["roofline"] and "skipped" in d["roofline_generic"]
+    assert d["config"]["measured_copy_ceiling_GBs"] is None and d["config"]["l2_error_sq"] is None
+    x, res = np.load(tmp_path / "dump" / "x.npy"), np.load(tmp_path / "dump" / "residuals.npy")
+    assert x.size == ln["config"]["dofs"] and res.size == ln["config"]["cg_iterations"] + 1
 
 
 @pytest.mark.gpu

@@ -4,7 +4,7 @@
 CELLS=$1; LEVELS=$2; shift; shift
 for e in "$@"; do
   echo "== ${e:-defaults}"
-  env $e python3 bench.py --cells $CELLS --levels $LEVELS --legs default,generic,varcoef --steps 4 --warmup 1 2>/dev/null | python3 -c "
+  env $e python3 bench.py --cells $CELLS --levels $LEVELS --full --legs default,generic,varcoef --steps 4 --warmup 1 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; v=d['variable_coefficient']
 print('  generic: ms %.2f sweep us %.1f frac %.3f it %d %s' % (d['ms_per_step_generic'], r['avg_launch_ms']*1e3, r['frac'], d['config']['cg_iterations_generic'], r['sweep_signature']))

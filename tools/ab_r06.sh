@@ -2,12 +2,13 @@
 # Round 6: A/B of environment variants on the default legs (128^3, 288^3) and the config-3 leg (Q2 256^3) of bench.py, one box.
 # Usage (GPU box, repo root): LEGS=default,weak_ref,config3 bash tools/ab_r06.sh "VAR=1" "" ...  (each argument = one variant; "" = defaults)
 LEGS=${LEGS:-default,weak_ref,config3}
+OUT=${OUT:-$(mktemp -d)}; echo "records in $OUT"
 i=0
 for e in "$@"; do
   i=$((i+1))
   echo "== ${e:-defaults}"
-  env $e GMG_BENCH_DETAILS=gpurun_out/ab_r06_$i.json python3 bench.py --legs $LEGS --steps ${STEPS:-6} --warmup 2 > /dev/null 2>gpurun_out/ab_r06_$i.err
-  python3 - gpurun_out/ab_r06_$i.json <<'PY'
+  env $e GMG_BENCH_DETAILS=$OUT/ab_r06_$i.json python3 bench.py --full --legs $LEGS --steps ${STEPS:-6} --warmup 2 > /dev/null 2>$OUT/ab_r06_$i.err
+  python3 - $OUT/ab_r06_$i.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
 r = d['roofline']

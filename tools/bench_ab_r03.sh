@@ -5,7 +5,7 @@ C=${1:-256}; L=${2:-5}; OUT=${3:-gpurun_out/r03e}
 mkdir -p $OUT
 for rep in 1 2; do for cfg in "new:GMG_NONE=0" "old:GMG_NT_ROWWISE=0 GMG_XCD_REMAP_BIG=1 GMG_SELL_DEFER=0"; do
   tag=${cfg%%:*}; envs=${cfg#*:}
-  env $envs timeout 900 python bench.py --cells $C --levels $L --no-cpu-baseline --steps 4 --warmup 1 2>$OUT/ab_${C}_${tag}_$rep.err > $OUT/ab_${C}_${tag}_$rep.json < /dev/null
+  env $envs timeout 900 python bench.py --full --cells $C --levels $L --no-cpu-baseline --steps 4 --warmup 1 2>$OUT/ab_${C}_${tag}_$rep.err > $OUT/ab_${C}_${tag}_$rep.json < /dev/null
   python - <<PY
 import json
 try:

@@ -4,7 +4,7 @@ OUT=$1; shift
 mkdir -p $OUT
 for cl in "$@"; do
   set -- $cl
-  timeout 1500 python bench.py --cells $1 --levels $2 --no-cpu-baseline --no-varcoef --no-weak-ref --steps 6 --warmup 2 2>$OUT/sz_$1.err > $OUT/sz_$1.json < /dev/null
+  timeout 1500 python bench.py --full --cells $1 --levels $2 --no-cpu-baseline --no-varcoef --no-weak-ref --steps 6 --warmup 2 2>$OUT/sz_$1.err > $OUT/sz_$1.json < /dev/null
   python - <<PY
 import json
 try:
