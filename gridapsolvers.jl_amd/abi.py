@@ -96,6 +96,8 @@ SYMBOLS = {
                             C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Result), C.c_void_p, C.c_int],
     "gmg_minres_solve": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
                          C.POINTER(Result), C.c_void_p, C.c_int],
+    "gmg_gmres_solve": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                        C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Result), C.c_void_p, C.c_int],
     "gmg_richardson_solve": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int,
                              C.POINTER(Result), C.c_void_p, C.c_int],
     "gmg_op_apply": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int],
@@ -154,6 +156,8 @@ SYMBOLS = {
                            C.POINTER(Result), C.c_void_p, C.c_int],
     "gmg_block_minres_solve": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
                                C.POINTER(Result), C.c_void_p, C.c_int],
+    "gmg_block_gmres_solve": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                              C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Result), C.c_void_p, C.c_int],
     "gmg_block_diag_log": [C.c_void_p, C.c_int, C.POINTER(Result)],
 }
 

@@ -367,6 +367,7 @@ int gmg_block_destroy(gmg_block_handle_t h)
   if (h->eng.comm_stream) (void)hipStreamDestroy(h->eng.comm_stream);
   if (h->eng.h_rep_full) (void)hipHostFree(h->eng.h_rep_full);
   if (h->eng.h_scalars) (void)hipHostFree(h->eng.h_scalars);
+  if (h->eng.h_mail_col) (void)hipHostFree(h->eng.h_mail_col);
   if (h->eng.own_stream) (void)hipStreamDestroy(h->eng.own_stream);
   delete h;
   return GMG_OK;
@@ -580,6 +581,32 @@ int gmg_block_minres_solve(gmg_block_handle_t h, const double *b, double *x, int
     const double beta_r = minres_core(h->eng, n, n, db, dx, h->eng.minres_work(n), h->eng.mr_parts, ops, log);
     h->eng.out_vec(x, dx, n, memspace);
     log.export_to(res, hist, hist_cap, beta_r);
+  });
+}
+
+int gmg_block_gmres_solve(gmg_block_handle_t h, const double *b, double *x, int memspace, int m0, int restart, int m_add,
+                          int maxiter, double atol, double rtol, int use_precond_right, int use_precond_left, gmg_result *res,
+                          double *hist, int hist_cap)
+{
+  return guarded_b(h, [&] {
+    REQUIRE((use_precond_right == 0 || use_precond_right == 1) && (use_precond_left == 0 || use_precond_left == 1), GMG_ERR_INVALID,
+            "use_precond_right / use_precond_left must be 0 or 1");
+    REQUIRE(!(use_precond_right == 1 && use_precond_left == 1), GMG_ERR_INVALID,
+            "the block preconditioner can be Pr or Pl of GMRES, not both (its work vectors are in use)");
+    check_block_ready(h);
+    REQUIRE(b && x, GMG_ERR_INVALID, "null vector");
+    REQUIRE(m0 >= 1 && m_add >= 1 && maxiter >= 0, GMG_ERR_INVALID, "bad GMRES sizes");
+    const int64_t n = h->N();
+    const double *db = h->eng.in_vec(b, n, memspace, h->st_b);
+    double *dx = (memspace == GMG_MEM_DEVICE) ? x : h->st_x;
+    if (memspace == GMG_MEM_HOST) h->eng.h2d(dx, x, n);
+    ConvLog log;
+    log.configure(maxiter, atol, rtol);
+    KrylovOps ops = h->ops(use_precond_right != 0);
+    if (use_precond_left) ops.precond_left = [h](double *z, const double *r) { h->precond_apply(z, r); };
+    const double beta = gmres_core(h->eng, n, n, db, dx, ops, m0, restart != 0, m_add, log);
+    h->eng.out_vec(x, dx, n, memspace);
+    log.export_to(res, hist, hist_cap, beta);
   });
 }
 

@@ -534,7 +534,7 @@ struct KrylovOps {
   std::function<void(double *x, double *y)> apply;                           // y = A x
   std::function<int(double *x, double *y, double *parts)> apply_dot;         // optional: y = A x + first stage of dot(x, y) -> #partials (0: not done)
   std::function<void(double *z, const double *r, double known_res)> precond; // empty: Pl === nothing (CG) / Pr === nothing (FGMRES)
-  std::function<void(double *z, const double *r)> precond_left;              // FGMRES only: Pl of KrylovUtils.jl:14-18,46-50
+  std::function<void(double *z, const double *r)> precond_left;              // FGMRES / GMRES: Pl of KrylovUtils.jl:14-18,46-50
   double *zl = nullptr;                                                      // its work vector (FGMRESSolvers.jl:66)
 };
 
@@ -544,6 +544,8 @@ static double cg_core(gmg_solver &S, int64_t n, const double *db, double *dx, do
                       const KrylovOps &ops, bool flexible, ConvLog &log);
 static double minres_core(gmg_solver &S, int64_t n, int64_t nv, const double *db, double *dx, double *const vec[9], double *parts,
                           const KrylovOps &ops, ConvLog &log);
+static double gmres_core(gmg_solver &S, int64_t n, int64_t nv, const double *db, double *dx, const KrylovOps &ops, int m0,
+                         bool restart, int m_add, ConvLog &log);
 
 struct gmg_solver {
   gmg_block_solver *attached_to = nullptr;   // block preconditioner that borrowed this handle (gmg_block_set_diag_gmg + setup)
@@ -668,6 +670,41 @@ struct gmg_solver {
       mr_nv = nv;
     }
     return mr_vec.data();
+  }
+  // GMRESSolvers.jl:57-69: V (m + 1 vectors, growing by m_add), zl, and zr only once a right preconditioner is selected; allocated by
+  // the first GMRES solve and kept (FGMRES's fg_V / fg_Z are separate: a handle may run both solvers in turn).  gm_tab is the device
+  // table of the basis pointers gmres_combine_kernel loops over (its coefficients travel in the scalar slots).
+  std::vector<double *> gm_V;
+  double *gm_zl = nullptr, *gm_zr = nullptr;
+  const double **gm_tab = nullptr;
+  int gm_tab_cap = 0, gm_tab_n = 0;
+  int64_t gm_nv = 0;
+  void gmres_work(int64_t nv, int m, bool need_zr)
+  {
+    if (gm_nv != nv) {                                     // another vector length without a new setup: give the old caches back
+      if (!gm_V.empty() || gm_zl || gm_zr) HIP_CHECK(hipStreamSynchronize(stream));
+      for (double *&v : gm_V) release(v, (size_t)gm_nv);
+      gm_V.clear();
+      release(gm_zl, (size_t)gm_nv); release(gm_zr, (size_t)gm_nv);
+      gm_tab_n = 0; gm_nv = nv;
+    }
+    while ((int)gm_V.size() < m + 1) gm_V.push_back(dvec(nv));
+    if (!gm_zl) gm_zl = dvec(nv);
+    if (need_zr && !gm_zr) gm_zr = dvec(nv);
+  }
+  const double *const *gmres_table()
+  {
+    const int nvec = (int)gm_V.size();
+    if (gm_tab_n == nvec) return gm_tab;
+    HIP_CHECK(hipStreamSynchronize(stream));                 // (no launch may still be reading the table that is replaced)
+    if (nvec > gm_tab_cap) {
+      if (gm_tab) release(gm_tab, (size_t)gm_tab_cap);
+      gm_tab_cap = std::max(2 * gm_tab_cap, nvec + 7);
+      gm_tab = dalloc<const double *>((size_t)gm_tab_cap);
+    }
+    HIP_CHECK(hipMemcpy(gm_tab, gm_V.data(), sizeof(double *) * (size_t)nvec, hipMemcpyHostToDevice));
+    gm_tab_n = nvec;
+    return gm_tab;
   }
   // staging buffers for host-memory callers
   double *st_b = nullptr, *st_x = nullptr;
@@ -863,6 +900,7 @@ struct gmg_solver {
     cg_w = cg_p = cg_z = cg_r = st_b = st_x = nullptr;
     fg_V.clear(); fg_Z.clear(); st_extra.clear();
     mr_vec.clear(); mr_parts = nullptr; mr_nv = 0;
+    gm_V.clear(); gm_zl = gm_zr = nullptr; gm_tab = nullptr; gm_tab_cap = gm_tab_n = 0; gm_nv = 0;
     setup_done = false;
   }
 
@@ -2649,9 +2687,10 @@ struct gmg_solver {
   // dot -> device scalar slot (no host sync)
   // first stage only: partial sums into `parts` (kRedBlocks doubles); returns how many.  The second stage is either
   // finish_reduction or the consumer kernel itself (sum_partials_all).
+  static int dot_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(kRedBlocks, (n / 2 + kBlock - 1) / kBlock)); }
   int dot_partials(int64_t n, const double *a, const double *b, double *parts)
   {
-    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(kRedBlocks, (n / 2 + kBlock - 1) / kBlock));
+    const int nb = dot_grid(n);
     const bool aligned = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
     hipLaunchKernelGGL(dot_partial_kernel, dim3(nb), dim3(kBlock), 0, stream, n, a, b, parts, aligned ? 1 : 0);
     HIP_CHECK(hipGetLastError());
@@ -2983,6 +3022,15 @@ struct gmg_solver {
   struct Mail { double value; unsigned long long seq; };
   Mail *h_mail = nullptr, *d_mail = nullptr;
   unsigned long long mail_seq = 0;
+  // GMRES posts a whole Hessenberg column per iteration: kScalarSlots doubles of the same kind of memory, released by the same number
+  double *h_mail_col = nullptr, *d_mail_col = nullptr;
+  void need_mail_col()
+  {
+    need_mail();
+    if (h_mail_col) return;
+    HIP_CHECK(hipHostMalloc((void **)&h_mail_col, sizeof(double) * kScalarSlots, hipHostMallocMapped));
+    HIP_CHECK(hipHostGetDevicePointer((void **)&d_mail_col, h_mail_col, 0));
+  }
   void need_mail()
   {
     if (h_mail) return;
@@ -4058,6 +4106,154 @@ static double fgmres_core(gmg_solver &S, int64_t n, int64_t nv, const double *db
     residual(V[0]);                                      // :194
   }
   return beta;
+}
+
+// solve!(x,ns::GMRESNumericalSetup,b), Krylov/GMRESSolvers.jl:132-210.  ops.precond = Pr, ops.precond_left = Pl (either may be
+// empty: the four krylov_mul! methods and the two krylov_residual! methods of KrylovUtils.jl:17-54).  The caches of :57-69 are the
+// handle's (S.gm_V, S.gm_zl, S.gm_zr; nv = allocation length of a vector); V, H, g, c and s grow by m_add when the basis outgrows
+// them (:76-92).  Fused path (option gmres_fused, one rank or rank-local reductions): column j is one dot_partial_kernel launch, j
+// gmres_mgs_kernel launches and gmres_normalize_kernel, which posts the column to the host; the solution update is one
+// gmres_combine_kernel.  Otherwise the sequence of fgmres_core: dot_async (all-reduced), axmy_dev_kernel, axpy_kernel.  Both perform
+// the same floating-point operations in the same order.
+static double gmres_core(gmg_solver &S, int64_t n, int64_t nv, const double *db, double *dx, const KrylovOps &ops, int m0,
+                         bool restart, int m_add, ConvLog &log)
+{
+  const bool has_pr = (bool)ops.precond, has_pl = (bool)ops.precond_left;
+  S.gmres_work(nv, m0, has_pr);                          // :57-62 (an earlier solve may have left a larger basis)
+  std::vector<double *> &V = S.gm_V;
+  double *zl = S.gm_zl, *zr = S.gm_zr;
+  int m = (int)V.size() - 1;                             // krylov_cache_length, :71-74
+  int hcap = m + 1;                                      // rows of H = columns + 1 (:64-67)
+  int ldh = hcap + 1;
+  std::vector<double> H((size_t)ldh * hcap, 0.0), g((size_t)hcap + 1, 0.0), c((size_t)hcap, 0.0), s((size_t)hcap, 0.0);
+  auto Hm = [&](int i, int j) -> double & { return H[(size_t)(i - 1) + (size_t)(j - 1) * ldh]; };
+  auto grow_small = [&](int newcap) {                    // expand_krylov_caches!, :86-89
+    const int nld = newcap + 1;
+    std::vector<double> H2((size_t)nld * newcap, 0.0);
+    for (int jj = 0; jj < hcap; ++jj)
+      for (int ii = 0; ii < ldh; ++ii) H2[(size_t)ii + (size_t)jj * nld] = H[(size_t)ii + (size_t)jj * ldh];
+    H.swap(H2);
+    g.resize((size_t)newcap + 1, 0.0); c.resize((size_t)newcap, 0.0); s.resize((size_t)newcap, 0.0);
+    hcap = newcap; ldh = nld;
+  };
+  const int grid = gmg_solver::grid_for(n);
+  const bool fuse = S.opt_int("GMG_GMRES_FUSED", 1) != 0 && S.fuse_reductions();
+  const bool post = fuse && S.opt_int("GMG_HOST_POLL", 1) != 0;
+  auto aligned16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+
+  // krylov_residual!(V[1],x,A,b,Pl,zl): KrylovUtils.jl:46-54
+  auto residual = [&](double *out) {
+    if (has_pl) { ops.resid(dx, db, zl); ops.precond_left(out, zl); }
+    else ops.resid(dx, db, out);
+  };
+  // krylov_mul!(y,A,x,Pr,Pl,zr,zl): KrylovUtils.jl:17-32
+  auto kmul = [&](double *y, double *x) {
+    if (has_pr) ops.precond(zr, x, -1.0);                // solve!(wr,Pr,x)
+    double *ax = has_pr ? zr : x;
+    if (has_pl) { ops.apply(ax, zl); ops.precond_left(y, zl); }   // mul!(wl,A,.) ; solve!(y,Pl,wl)
+    else ops.apply(ax, y);                               // mul!(y,A,.)
+  };
+  residual(V[0]);                                        // :143
+  double beta = S.norm(n, V[0]);                         // :144
+  bool done = log.init(beta);                            // :145
+  while (!done) {                                        // :146
+    int j = 1;                                           // :148
+    hipLaunchKernelGGL(div_kernel, dim3(grid), dim3(256), 0, S.stream, n, beta, V[0]); // :149
+    HIP_CHECK(hipGetLastError());
+    std::fill(H.begin(), H.end(), 0.0);                  // :150
+    std::fill(g.begin(), g.end(), 0.0); g[0] = beta;     // :151
+    while (!done && !(restart && j > m0)) {              // :152 ; restart(solver,j), :31-37
+      if (j > m) {                                       // :154-157
+        for (int q = 0; q < m_add; ++q) V.push_back(S.dvec(nv));
+        m += m_add;
+      }
+      if (j + 1 > hcap) grow_small(m + 1);
+      REQUIRE(j + 3 < kScalarSlots - 40, GMG_ERR_UNSUPPORTED, "Krylov basis larger than the scalar buffer (use restart=true)");
+      double *Vn = V[j];
+      kmul(Vn, V[j - 1]);                                // :160-161 (every entry of V[j+1] is written: no fill!)
+      // (the fused kernels take dot_partial_kernel's order for 16-byte aligned operands: the basis is dvec's, aligned by hipMalloc)
+      bool al = aligned16(Vn);
+      for (int i = 0; i < j; ++i) al = al && aligned16(V[i]);
+      if (fuse && al) {
+        double *pin = S.d_partials, *pout = S.d_partials2;
+        int np = S.dot_partials(n, Vn, V[0], pin);       // first stage of H[1,j] (:163)
+        const int nbd = gmg_solver::dot_grid(n);
+        for (int i = 1; i <= j; ++i) {                   // :162-165 ; the last launch leaves the partials of norm(V[j+1])^2 (:166)
+          hipLaunchKernelGGL(gmres_mgs_kernel, dim3(nbd), dim3(kBlock), 0, S.stream, n, Vn, V[i - 1],
+                             i < j ? (const double *)V[i] : (const double *)nullptr, i < j ? 0 : 1, pin, np, S.d_scalars + i, pout);
+          HIP_CHECK(hipGetLastError());
+          std::swap(pin, pout);
+          np = nbd;
+        }
+        unsigned long long want = 0;
+        if (post) { S.need_mail_col(); want = ++S.mail_seq; }
+        hipLaunchKernelGGL(gmres_normalize_kernel, dim3(grid), dim3(kBlock), 0, S.stream, n, Vn, pin, np, S.d_scalars + 1, j + 1,
+                           S.d_mail_col, post ? &S.d_mail->value : nullptr, post ? &S.d_mail->seq : nullptr, want);   // :166-167
+        HIP_CHECK(hipGetLastError());
+        if (post) {
+          S.posted = want;
+          (void)S.fetch_scalar(j + 1);                   // waits for the number: the column is in the mailbox
+          for (int i = 1; i <= j + 1; ++i) Hm(i, j) = S.h_mail_col[i - 1];
+        }
+      } else {
+        for (int i = 1; i <= j; ++i) {                   // :162-165 modified Gram-Schmidt
+          S.dot_async(n, Vn, V[i - 1], i, false);
+          hipLaunchKernelGGL(axmy_dev_kernel, dim3(grid), dim3(256), 0, S.stream, n, S.d_scalars + i, V[i - 1], Vn);
+          HIP_CHECK(hipGetLastError());
+        }
+        S.dot_async(n, Vn, Vn, j + 1, true);             // :166
+        hipLaunchKernelGGL(div_dev_kernel, dim3(grid), dim3(256), 0, S.stream, n, S.d_scalars + (j + 1), Vn); // :167
+        HIP_CHECK(hipGetLastError());
+      }
+      if (!(fuse && al && post)) {
+        HIP_CHECK(hipMemcpyAsync(S.h_scalars + 1, S.d_scalars + 1, sizeof(double) * (size_t)(j + 1), hipMemcpyDeviceToHost, S.stream));
+        HIP_CHECK(hipStreamSynchronize(S.stream));
+        for (int i = 1; i <= j + 1; ++i) Hm(i, j) = S.h_scalars[i];
+      }
+      for (int i = 1; i <= j - 1; ++i) {                 // :170-174
+        const double gm = c[i - 1] * Hm(i, j) + s[i - 1] * Hm(i + 1, j);
+        Hm(i + 1, j) = -s[i - 1] * Hm(i, j) + c[i - 1] * Hm(i + 1, j);
+        Hm(i, j) = gm;
+      }
+      double rr;
+      givens_lapack(Hm(j, j), Hm(j + 1, j), c[j - 1], s[j - 1], rr);               // :177 LinearAlgebra.givensAlgorithm
+      Hm(j, j) = c[j - 1] * Hm(j, j) + s[j - 1] * Hm(j + 1, j); Hm(j + 1, j) = 0.0; // :178
+      g[j] = -s[j - 1] * g[j - 1]; g[j - 1] = c[j - 1] * g[j - 1];                  // :179
+      beta = std::fabs(g[j]);                            // :181
+      j += 1;                                            // :182
+      done = log.update(beta);                           // :183
+    }
+    j = j - 1;                                           // :185
+    for (int i = j; i >= 1; --i) {                       // :188-190
+      double acc = 0.0;
+      for (int k = i + 1; k <= j; ++k) acc += Hm(i, k) * g[k - 1];
+      g[i - 1] = (g[i - 1] - acc) / Hm(i, i);
+    }
+    double *y = has_pr ? zl : dx;                        // :193-196 x .+= g[i] .* V[i] ; :198-201 the same into zl = 0
+    if (fuse && j > 0) {
+      bool vec = aligned16(y);
+      for (int i = 0; i < j; ++i) vec = vec && aligned16(V[i]);
+      const double *const *tab = S.gmres_table();
+      for (int i = 1; i <= j; ++i) S.h_scalars[i] = g[i - 1];
+      HIP_CHECK(hipMemcpyAsync(S.d_scalars + 1, S.h_scalars + 1, sizeof(double) * (size_t)j, hipMemcpyHostToDevice, S.stream));
+      hipLaunchKernelGGL(gmres_combine_kernel, dim3(grid), dim3(kBlock), 0, S.stream, n, y, has_pr ? (const double *)nullptr : dx, tab,
+                         S.d_scalars + 1, j, vec ? 1 : 0);
+      HIP_CHECK(hipGetLastError());
+    } else {
+      if (has_pr) S.zero(zl, n);                         // :198
+      for (int i = 1; i <= j; ++i) {
+        hipLaunchKernelGGL(axpy_kernel, dim3(grid), dim3(256), 0, S.stream, n, g[i - 1], V[i - 1], y);
+        HIP_CHECK(hipGetLastError());
+      }
+    }
+    if (has_pr) {
+      ops.precond(zr, zl, -1.0);                         // :202 solve!(zr,Pr,zl)
+      hipLaunchKernelGGL(axpy_kernel, dim3(grid), dim3(256), 0, S.stream, n, 1.0, zr, dx);   // :203 x .+= zr
+      HIP_CHECK(hipGetLastError());
+    }
+    residual(V[0]);                                      // :205
+  }
+  return beta;                                           // :208 finalize!(log,β)
 }
 
 // solve!(x,ns::MINRESNumericalSetup,b), Krylov/MINRESSolvers.jl:75-148.  vec = the caches of :39-44 in the order Vnew, V, Vold,
@@ -5729,6 +5925,7 @@ int gmg_destroy(gmg_handle_t h)
   if (h->h_scalars) (void)hipHostFree(h->h_scalars);
   if (h->h_perr) (void)hipHostFree(h->h_perr);
   if (h->h_mail) (void)hipHostFree(h->h_mail);
+  if (h->h_mail_col) (void)hipHostFree(h->h_mail_col);
   for (const auto &r : h->host_regs)
     if (r.ours) (void)hipHostUnregister(const_cast<char *>(r.base));   // the caller's pages are unpinned, never freed
   for (int i = 0; i < 2; ++i) {
@@ -6197,7 +6394,7 @@ const OptionKey kOptionKeys[] = {
   {"GMG_PAT_WIDE_ROUNDS", false}, {"GMG_PERSIST", false}, {"GMG_PERSIST_FENCED", false}, {"GMG_PERSIST_MAX_SLICES", false},
   {"GMG_PERSIST_SHARED", false}, {"GMG_PROF_STRIDE", true}, {"GMG_REFRESH", true}, {"GMG_SELL", false}, {"GMG_SELL_BLOCK", false},
   {"GMG_SELL_DEFER", false}, {"GMG_SELL_MAXPAD", false}, {"GMG_SELL_UN", false}, {"GMG_SETUP_TIMING", true}, {"GMG_VDICT", false},
-  {"GMG_XCD_REMAP", false}, {"GMG_XCD_REMAP_BIG", false}, {"GMG_X0_ZERO", true}, {"GMG_HOST_POLL", true}, {"GMG_HOST_CHUNK_BYTES", true}, {"GMG_PAT_FMA", false}, {"GMG_PAT_R2", false}, {"GMG_RED_FUSED", false}, {"GMG_PAT_R2MV", false}, {"GMG_PAT_R2_OCC", false}, {"GMG_PAT_PAIR_P", false}, {"GMG_PAT_R2MV_DOT", false}, {"GMG_PERSIST_WPB", false}, {"GMG_HOST_TIMELINE", true}, {"GMG_PAT_R2MV_MIN", false}, {"GMG_PAT_BCAST", false}, {"GMG_PAT_R2_WGS", false}, {"GMG_PAT_ZWALK", false}, {"GMG_PAT_ZWALK_T", false}, {"GMG_PAT_ZWALK_ROWS", false}, {"GMG_PAT_ZWALK_MV", false}, {"GMG_PAT_ZWALK_WIDE", false}, {"GMG_PAT_ZWALK_WIDE_ROWS", false}, {"GMG_PAT_FUSE2", false}, {"GMG_PAT_FUSE2_W", false}, {"GMG_PAT_FUSE2_T", false}, {"GMG_PAT_FUSE2_ROWS", false}, {"GMG_PAT_FUSE2_BOX", false}, {"GMG_PAT_BOX", false}, {"GMG_PAT_WIDE_GRID", false}, {"GMG_PAT_BOX_T", false}, {"GMG_PAT_BOX_MIN_ROWS", false}, {"GMG_PAT_BOX_MAX_ROWS", false},
+  {"GMG_XCD_REMAP", false}, {"GMG_XCD_REMAP_BIG", false}, {"GMG_X0_ZERO", true}, {"GMG_HOST_POLL", true}, {"GMG_HOST_CHUNK_BYTES", true}, {"GMG_PAT_FMA", false}, {"GMG_PAT_R2", false}, {"GMG_RED_FUSED", false}, {"GMG_GMRES_FUSED", true}, {"GMG_PAT_R2MV", false}, {"GMG_PAT_R2_OCC", false}, {"GMG_PAT_PAIR_P", false}, {"GMG_PAT_R2MV_DOT", false}, {"GMG_PERSIST_WPB", false}, {"GMG_HOST_TIMELINE", true}, {"GMG_PAT_R2MV_MIN", false}, {"GMG_PAT_BCAST", false}, {"GMG_PAT_R2_WGS", false}, {"GMG_PAT_ZWALK", false}, {"GMG_PAT_ZWALK_T", false}, {"GMG_PAT_ZWALK_ROWS", false}, {"GMG_PAT_ZWALK_MV", false}, {"GMG_PAT_ZWALK_WIDE", false}, {"GMG_PAT_ZWALK_WIDE_ROWS", false}, {"GMG_PAT_FUSE2", false}, {"GMG_PAT_FUSE2_W", false}, {"GMG_PAT_FUSE2_T", false}, {"GMG_PAT_FUSE2_ROWS", false}, {"GMG_PAT_FUSE2_BOX", false}, {"GMG_PAT_BOX", false}, {"GMG_PAT_WIDE_GRID", false}, {"GMG_PAT_BOX_T", false}, {"GMG_PAT_BOX_MIN_ROWS", false}, {"GMG_PAT_BOX_MAX_ROWS", false},
   {"GMG_PERSIST_FORCE_TIMEOUT", true},
 };
 // "pat_tile", "PAT_TILE" and "GMG_PAT_TILE" name the same option
@@ -6470,6 +6667,37 @@ int gmg_minres_solve(gmg_handle_t h, const double *b, double *x, int memspace, i
       const double beta_r = minres_core(S, n, L0.nvec, db, dx, S.minres_work(L0.nvec), S.mr_parts, ops, log);
       S.out_vec(x, dx, n, memspace);
       log.export_to(res, hist, hist_cap, beta_r);            // :147
+    });
+  });
+}
+
+int gmg_gmres_solve(gmg_handle_t h, const double *b, double *x, int memspace, int m0, int restart, int m_add, int maxiter,
+                    double atol, double rtol, int use_precond_right, int use_precond_left, gmg_result *res, double *hist, int hist_cap)
+{
+  return guarded(h, [&] {
+    REQUIRE(use_precond_right >= 0 && use_precond_right <= 3, GMG_ERR_INVALID, "use_precond_right must be 0, 1, 2 or 3");
+    REQUIRE(use_precond_left >= 0 && use_precond_left <= 3, GMG_ERR_INVALID, "use_precond_left must be 0, 1, 2 or 3");
+    REQUIRE(!(use_precond_right == 1 && use_precond_left == 1), GMG_ERR_INVALID,
+            "one handle holds one GMG: it can be Pr or Pl of GMRES, not both (its work vectors are in use)");
+    check_ready(h);
+    REQUIRE(b && x, GMG_ERR_INVALID, "null vector");
+    REQUIRE(m0 >= 1 && m_add >= 1 && maxiter >= 0, GMG_ERR_INVALID, "bad GMRES sizes");
+    h->with_persist_retry(x, h->user_n(), memspace, false, [&] {
+      gmg_solver &S = *h;
+      Level &L0 = S.lev[S.kl()];
+      const int64_t n = L0.n;
+      const double *db = S.in_vec(b, n, memspace, S.st_b);
+      const bool dist = S.comm.nranks > 1;
+      double *dx = dist ? S.cg_x : ((memspace == GMG_MEM_DEVICE) ? x : S.st_x);
+      S.in_guess(dx, x, n, memspace);                        // x = initial guess on entry (GMRESSolvers.jl:143)
+      ConvLog log;
+      log.configure(maxiter, atol, rtol);
+      KrylovOps ops = S.level0_ops(use_precond_right);
+      if (use_precond_left)
+        ops.precond_left = [&S, use_precond_left](double *z, const double *r) { S.krylov_precond(use_precond_left, z, r, -1.0); };
+      const double beta = gmres_core(S, n, L0.nvec, db, dx, ops, m0, restart != 0, m_add, log);
+      S.out_vec(x, dx, n, memspace);
+      log.export_to(res, hist, hist_cap, beta);              // :208
     });
   });
 }

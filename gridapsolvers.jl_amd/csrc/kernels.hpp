@@ -3905,6 +3905,128 @@ __global__ void minres_init_kernel(double *__restrict__ st, double gamma, double
   st[MR_S] = 0.0; st[MR_S_OLD] = 0.0; st[MR_ETA] = gamma; st[MR_BETA_R] = beta_r;
 }
 
+// ---------------------------------------------------------------------------
+// K12: GMRES (Krylov/GMRESSolvers.jl:132-210): the Arnoldi column and the solution update as streaming passes.  Each kernel performs
+// the floating-point operations of the launches it replaces, in their order, so gmres_fused = 1 and 0 give the same bits.
+// ---------------------------------------------------------------------------
+// Step i of the modified Gram-Schmidt loop of column j (:162-165), one pass over four streams:
+//   H[i,j] = sum of the partials of dot(w, V_i) the previous launch left in `hparts` (summed by every workgroup as
+//            reduce_final_kernel sums them; workgroup 0 stores it into *hslot)
+//   w .= w .- H[i,j] .* V_i                                   (product and difference rounded separately: axmy_dev_kernel)
+//   partials[blockIdx.x] = first stage of dot(w, vnext), vnext = V_{i+1}, or of dot(w, w) for i = j (self != 0, vnext not read)
+// The partials are dot_partial_kernel's on 16-byte aligned vectors: launch it with that kernel's grid; the double2 order with the odd
+// tail on thread 0 of workgroup 0.  w, V_i and vnext must be 16-byte aligned (the basis is the library's own allocation; gmres_core
+// falls back to the unfused sequence otherwise); pass vnext = nullptr with self != 0.  `partials` and `hparts` must be different arrays.
+__global__ __launch_bounds__(kBlock) void gmres_mgs_kernel(int64_t n, double *__restrict__ w, const double *__restrict__ vi,
+                                                           const double *__restrict__ vnext, int self,
+                                                           const double *__restrict__ hparts, int nhparts, double *__restrict__ hslot,
+                                                           double *__restrict__ partials)
+{
+  __shared__ double sh[5];
+  const double h = sum_partials_all(hparts, nhparts, sh);
+  if (blockIdx.x == 0 && threadIdx.x == 0) hslot[0] = h;
+  __syncthreads();                                           // sh is reused below
+  double s = 0.0;
+  const int64_t n2 = n >> 1;
+  double2 *w2 = reinterpret_cast<double2 *>(w);
+  const double2 *v2 = reinterpret_cast<const double2 *>(vi);
+  const double2 *x2 = reinterpret_cast<const double2 *>(vnext);
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n2; i += (int64_t)gridDim.x * kBlock) {
+    double2 u = w2[i];
+    const double2 v = v2[i];
+    u.x = u.x - h * v.x;
+    u.y = u.y - h * v.y;
+    w2[i] = u;
+    const double2 q = self ? u : x2[i];
+    s += u.x * q.x;
+    s += u.y * q.y;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1)) {
+    const double u = w[n - 1] - h * vi[n - 1];
+    w[n - 1] = u;
+    s += u * (self ? u : vnext[n - 1]);
+  }
+  const double t = block_sum(s, sh);
+  if (threadIdx.x == 0) partials[blockIdx.x] = t;
+}
+
+// :166-167  H[j+1,j] = norm(w) from the partials of dot(w, w) ; w ./= H[j+1,j] (true division: div_dev_kernel).  hcol[0 .. ncol-2] hold
+// H[1..j,j] (stored by the gmres_mgs_kernel launches), workgroup 0 stores H[j+1,j] into hcol[ncol-1].  seq != nullptr: workgroup 0
+// then posts the ncol scalars of the column into host-mapped memory (`mail`), the last one into *value as well, and releases the
+// sequence number after them (the store order of reduce_post_kernel); otherwise the host copies the slots.
+__global__ __launch_bounds__(kBlock) void gmres_normalize_kernel(int64_t n, double *__restrict__ w, const double *__restrict__ parts,
+                                                                 int nparts, double *hcol, int ncol, double *mail, double *value,
+                                                                 unsigned long long *seq, unsigned long long want)
+{
+  __shared__ double sh[5];
+  const double hn = sqrt(sum_partials_all(parts, nparts, sh));
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  const int64_t n2 = n >> 1;                                 // w is 16-byte aligned (see gmres_mgs_kernel)
+  double2 *w2 = reinterpret_cast<double2 *>(w);
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n2; i += stride) {
+    double2 u = w2[i];
+    u.x = u.x / hn;
+    u.y = u.y / hn;
+    w2[i] = u;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1)) w[n - 1] = w[n - 1] / hn;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    hcol[ncol - 1] = hn;
+    if (seq) {
+      for (int k = 0; k < ncol - 1; ++k) __hip_atomic_store(mail + k, hcol[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(mail + (ncol - 1), hn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(value, hn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(seq, want, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+
+// :193-201  y = y0 + sum_{k=1..j} g_k V_k in one pass: every element starts from y0's value (y0 == nullptr: from 0.0, the fill!(zl,0)
+// of :198) and adds the terms in the order k = 1..j, each product and each sum rounded on its own -- the operations of j axpy_kernel
+// launches, with j + 1 vector reads and one write instead of 3 j streams.  tab[k] = V_{k+1}, coef[k] = g_{k+1} (device table of the
+// basis, refreshed by gmres_core when the basis grows).  y0 may be y itself (x .+= ...); vec != 0: y, y0 and every V_k 16-byte aligned.
+__global__ __launch_bounds__(kBlock) void gmres_combine_kernel(int64_t n, double *y, const double *y0,
+                                                               const double *const *__restrict__ tab,
+                                                               const double *__restrict__ coef, int j, int vec)
+{
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  if (vec) {
+    const int64_t n2 = n >> 1;
+    double2 *y2 = reinterpret_cast<double2 *>(y);
+    const double2 *y02 = reinterpret_cast<const double2 *>(y0);
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n2; i += stride) {
+      double2 a = y0 ? y02[i] : make_double2(0.0, 0.0);
+      int k = 0;
+      for (; k + 4 <= j; k += 4) {                           // four basis loads in flight, added in order
+        const double2 v0 = reinterpret_cast<const double2 *>(tab[k])[i], v1 = reinterpret_cast<const double2 *>(tab[k + 1])[i];
+        const double2 v2 = reinterpret_cast<const double2 *>(tab[k + 2])[i], v3 = reinterpret_cast<const double2 *>(tab[k + 3])[i];
+        const double c0 = coef[k], c1 = coef[k + 1], c2 = coef[k + 2], c3 = coef[k + 3];
+        a.x = a.x + c0 * v0.x; a.y = a.y + c0 * v0.y;
+        a.x = a.x + c1 * v1.x; a.y = a.y + c1 * v1.y;
+        a.x = a.x + c2 * v2.x; a.y = a.y + c2 * v2.y;
+        a.x = a.x + c3 * v3.x; a.y = a.y + c3 * v3.y;
+      }
+      for (; k < j; ++k) {
+        const double2 v = reinterpret_cast<const double2 *>(tab[k])[i];
+        const double c = coef[k];
+        a.x = a.x + c * v.x; a.y = a.y + c * v.y;
+      }
+      y2[i] = a;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1)) {
+      double a = y0 ? y0[n - 1] : 0.0;
+      for (int k = 0; k < j; ++k) a = a + coef[k] * tab[k][n - 1];
+      y[n - 1] = a;
+    }
+  } else {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+      double a = y0 ? y0[i] : 0.0;
+      for (int k = 0; k < j; ++k) a = a + coef[k] * tab[k][i];
+      y[i] = a;
+    }
+  }
+}
+
 // dx = omega*(dinv.*r) ; optionally x += dx     (unfused Jacobi apply, gmg_precond_apply)
 __global__ void jacobi_apply_kernel(int64_t n, const double *__restrict__ dinv, const double *__restrict__ r,
                                     double *__restrict__ dx)

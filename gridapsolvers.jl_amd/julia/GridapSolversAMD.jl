@@ -37,6 +37,7 @@ using GridapSolvers.LinearSolvers: RichardsonSmoother, JacobiLinearSolver
 export HipGMGLinearSolver, HipCGSolver, HipFGMRESSolver, HipMINRESSolver, PatchTable, HipPatchProlongation
 export HipRichardsonLinearSolver, HipBlockTriangularSolver, HipBlockDiagonalSolver, HipBlockFGMRESSolver, block_mul!, block_cg_solve!
 export block_minres_solve!
+export HipGMRESSolver, HipBlockGMRESSolver
 
 const libgmgamd = get(ENV, "LIBGMGAMD", joinpath(@__DIR__, "..", "libgmgamd.so"))
 
@@ -451,17 +452,47 @@ function HipMINRESSolver(; Pl::HipGMGLinearSolver, maxiter=1000, atol=1e-12, rto
   return HipMINRESSolver(Pl, ConvergenceLog(name,tols,verbose=verbose))
 end
 
+# GMRESSolver(m;Pr,Pl,...) on the device: GMRESSolvers.jl:25-29 (defaults), :132-210 (solve!).  A side is `nothing`, a
+# HipGMGLinearSolver, or (nothing | :jacobi | :smoother, gmg): nothing / JacobiLinearSolver() / LinearSolverFromSmoother(finest
+# pre-smoother) on the matrix of gmg's handle.  Both sides live on one handle and its GMG serves on one side only; at least one side
+# names the handle (Pr=(nothing,gmg): the unpreconditioned solver).
+struct HipGMRESSolver{A} <: Gridap.Algebra.LinearSolver
+  m       :: Int
+  restart :: Bool
+  m_add   :: Int
+  gmg     :: A
+  pr      :: Cint
+  pl      :: Cint
+  log     :: ConvergenceLog{Float64}
+end
+_gmres_side(::Nothing) = (Cint(0), nothing)
+_gmres_side(P::HipGMGLinearSolver) = (Cint(1), P)
+function _gmres_side(P::Tuple{Any,HipGMGLinearSolver})
+  k = P[1] === nothing ? 0 : P[1] === :jacobi ? 2 : P[1] === :smoother ? 3 : error("a GMRES side is nothing, gmg, or (nothing | :jacobi | :smoother, gmg)")
+  return (Cint(k), P[2])
+end
+function HipGMRESSolver(m; Pr=nothing, Pl=nothing, restart=false, m_add=1, maxiter=100, atol=1e-12, rtol=1.e-6, verbose=false, name="GMRES-MI355X")
+  (pr, gr), (pl, gl) = _gmres_side(Pr), _gmres_side(Pl)
+  gmg = gr === nothing ? gl : gr
+  gmg === nothing && error("HipGMRESSolver needs a device handle: pass Pr=(nothing,gmg) for the unpreconditioned solver")
+  (gr === nothing || gl === nothing || gr === gl) || error("Pr and Pl must name the same HipGMGLinearSolver")
+  (pr == 1 && pl == 1) && error("the handle's GMG serves as Pr or as Pl, not both")
+  tols = SolverTolerances{Float64}(maxiter=maxiter,atol=atol,rtol=rtol)      # GMRESSolvers.jl:25-29
+  return HipGMRESSolver(m, restart, m_add, gmg, pr, pl, ConvergenceLog(name,tols,verbose=verbose))
+end
+
 struct HipKrylovSymbolicSetup{A} <: Gridap.Algebra.SymbolicSetup
   solver :: A
 end
-Gridap.Algebra.symbolic_setup(s::Union{HipCGSolver,HipFGMRESSolver,HipMINRESSolver}, ::AbstractMatrix) = HipKrylovSymbolicSetup(s)
+Gridap.Algebra.symbolic_setup(s::Union{HipCGSolver,HipFGMRESSolver,HipMINRESSolver,HipGMRESSolver}, ::AbstractMatrix) = HipKrylovSymbolicSetup(s)
 
 mutable struct HipKrylovNumericalSetup{A,B} <: Gridap.Algebra.NumericalSetup
   solver :: A
   P_ns   :: B
 end
 function Gridap.Algebra.numerical_setup(ss::HipKrylovSymbolicSetup, A::AbstractMatrix)
-  P = ss.solver isa HipFGMRESSolver ? ss.solver.Pr : ss.solver.Pl
+  # (GMRES: one handle holds Pr and Pl, GMRESSolvers.jl:96-97)
+  P = ss.solver isa HipGMRESSolver ? ss.solver.gmg : ss.solver isa HipFGMRESSolver ? ss.solver.Pr : ss.solver.Pl
   P_ns = numerical_setup(symbolic_setup(P,A),A)                              # CGSolvers.jl:52
   return HipKrylovNumericalSetup(ss.solver, P_ns)
 end
@@ -510,6 +541,21 @@ function Gridap.Algebra.solve!(x::Vector{Float64}, ns::HipKrylovNumericalSetup{<
     check(h, ccall((:gmg_minres_solve, libgmgamd), Cint,
       (Ptr{Cvoid},Ptr{Float64},Ptr{Float64},Cint,Cint,Float64,Float64,Cint,Ref{GmgResult},Ptr{Float64},Cint),
       h, b, x, GMG_MEM_HOST, tols.maxiter, tols.atol, tols.rtol, 1, res, hist, length(hist)))
+  end
+  _fill_log!(s.log, res[], hist)
+  return x
+end
+
+function Gridap.Algebra.solve!(x::Vector{Float64}, ns::HipKrylovNumericalSetup{<:HipGMRESSolver}, b::Vector{Float64})
+  s, h = ns.solver, ns.P_ns.handle
+  tols = s.log.tols
+  res  = Ref(GmgResult(0,0,0.0,0.0))
+  hist = zeros(tols.maxiter+1)
+  _maybe_pin!(ns.P_ns, x, b)
+  GC.@preserve x b hist begin
+    check(h, ccall((:gmg_gmres_solve, libgmgamd), Cint,
+      (Ptr{Cvoid},Ptr{Float64},Ptr{Float64},Cint,Cint,Cint,Cint,Cint,Float64,Float64,Cint,Cint,Ref{GmgResult},Ptr{Float64},Cint),
+      h, b, x, GMG_MEM_HOST, s.m, s.restart ? 1 : 0, s.m_add, tols.maxiter, tols.atol, tols.rtol, s.pr, s.pl, res, hist, length(hist)))
   end
   _fill_log!(s.log, res[], hist)
   return x
@@ -588,10 +634,23 @@ HipBlockFGMRESSolver(m, Pr::HipBlockTriangularSolver; restart=false, m_add=1, ma
                      verbose=false, name="FGMRES-MI355X") =
   HipBlockFGMRESSolver(m, restart, m_add, Pr, ConvergenceLog(name, SolverTolerances{Float64}(maxiter=maxiter,atol=atol,rtol=rtol); verbose=verbose))
 
+# GMRESSolver(m; Pr=P) (side = :right), GMRESSolver(m; Pl=P) (:left) or the unpreconditioned solver on P's block system (:none)
+struct HipBlockGMRESSolver <: Gridap.Algebra.LinearSolver
+  m :: Int; restart :: Bool; m_add :: Int
+  P :: HipBlockTriangularSolver
+  side :: Symbol
+  log :: ConvergenceLog{Float64}
+end
+function HipBlockGMRESSolver(m, P::HipBlockTriangularSolver; side::Symbol=:right, restart=false, m_add=1, maxiter=100, atol=1e-12,
+                             rtol=1.e-6, verbose=false, name="GMRES-MI355X")
+  side in (:right, :left, :none) || error("side must be :right, :left or :none")
+  return HipBlockGMRESSolver(m, restart, m_add, P, side, ConvergenceLog(name, SolverTolerances{Float64}(maxiter=maxiter,atol=atol,rtol=rtol); verbose=verbose))
+end
+
 struct HipBlockSymbolicSetup{A} <: Gridap.Algebra.SymbolicSetup
   solver :: A
 end
-Gridap.Algebra.symbolic_setup(s::Union{HipBlockTriangularSolver,HipBlockFGMRESSolver}, ::AbstractMatrix) = HipBlockSymbolicSetup(s)
+Gridap.Algebra.symbolic_setup(s::Union{HipBlockTriangularSolver,HipBlockFGMRESSolver,HipBlockGMRESSolver}, ::AbstractMatrix) = HipBlockSymbolicSetup(s)
 
 mutable struct HipBlockNumericalSetup{A} <: Gridap.Algebra.NumericalSetup
   solver   :: A
@@ -664,6 +723,7 @@ function _block_numerical_setup(P::HipBlockTriangularSolver, mat, owner)
 end
 Gridap.Algebra.numerical_setup(ss::HipBlockSymbolicSetup{HipBlockTriangularSolver}, mat::AbstractMatrix) = _block_numerical_setup(ss.solver, mat, ss.solver)
 Gridap.Algebra.numerical_setup(ss::HipBlockSymbolicSetup{HipBlockFGMRESSolver}, mat::AbstractMatrix) = _block_numerical_setup(ss.solver.Pr, mat, ss.solver)
+Gridap.Algebra.numerical_setup(ss::HipBlockSymbolicSetup{HipBlockGMRESSolver}, mat::AbstractMatrix) = _block_numerical_setup(ss.solver.P, mat, ss.solver)
 
 # block vectors are passed as their contiguous parent (BlockArrays stores a BlockVector's blocks back to back)
 _flat(v::AbstractVector) = v isa Vector{Float64} ? v : parent(v)
@@ -702,6 +762,19 @@ function Gridap.Algebra.solve!(x::AbstractVector, ns::HipBlockNumericalSetup{Hip
     ns.handle, bf, xf, GMG_MEM_HOST, s.m, s.restart ? 1 : 0, s.m_add, tols.maxiter, tols.atol, tols.rtol, 1, res, hist, length(hist)))
   _fill_log!(s.log, res[], hist)
   _fill_block_logs!(ns, s.Pr)
+  return x
+end
+# solve!(x,ns::GMRESNumericalSetup,b) with the block preconditioner on the chosen side
+function Gridap.Algebra.solve!(x::AbstractVector, ns::HipBlockNumericalSetup{HipBlockGMRESSolver}, b::AbstractVector)
+  s = ns.solver; tols = s.log.tols
+  res  = Ref(GmgResult(0,0,0.0,0.0)); hist = zeros(tols.maxiter+1)
+  xf, bf = _flat(x), _flat(b)
+  GC.@preserve xf bf hist check_block(ns.handle, ccall((:gmg_block_gmres_solve, libgmgamd), Cint,
+    (Ptr{Cvoid},Ptr{Float64},Ptr{Float64},Cint,Cint,Cint,Cint,Cint,Float64,Float64,Cint,Cint,Ref{GmgResult},Ptr{Float64},Cint),
+    ns.handle, bf, xf, GMG_MEM_HOST, s.m, s.restart ? 1 : 0, s.m_add, tols.maxiter, tols.atol, tols.rtol,
+    s.side === :right ? 1 : 0, s.side === :left ? 1 : 0, res, hist, length(hist)))
+  _fill_log!(s.log, res[], hist)
+  _fill_block_logs!(ns, s.P)
   return x
 end
 # CGSolver(P) on an SPD block system
@@ -1036,12 +1109,20 @@ function Gridap.Algebra.solve!(x::PA.PVector, ns::HipKrylovNumericalSetup{<:HipM
   PA.consistent!(x) |> wait
   return x
 end
+function Gridap.Algebra.solve!(x::PA.PVector, ns::HipKrylovNumericalSetup{<:HipGMRESSolver,<:HipDistributedGMGNumericalSetup}, b::PA.PVector)
+  xo = PA.getany(PA.own_values(x)); bo = PA.getany(PA.own_values(b))
+  xv, bv = Vector{Float64}(xo), Vector{Float64}(bo)
+  solve!(xv, HipKrylovNumericalSetup(ns.solver, ns.P_ns.inner), bv)          # gmg_gmres_solve: dots are all-reduced in the library
+  copyto!(xo, xv)
+  PA.consistent!(x) |> wait
+  return x
+end
 function Gridap.Algebra.numerical_setup(ss::HipKrylovSymbolicSetup, A::PA.PSparseMatrix; kwargs...)
-  P = ss.solver isa HipFGMRESSolver ? ss.solver.Pr : ss.solver.Pl
+  P = ss.solver isa HipGMRESSolver ? ss.solver.gmg : ss.solver isa HipFGMRESSolver ? ss.solver.Pr : ss.solver.Pl
   return HipKrylovNumericalSetup(ss.solver, numerical_setup(symbolic_setup(P,A),A; kwargs...))
 end
 Gridap.Algebra.symbolic_setup(s::HipGMGLinearSolver, ::PA.PSparseMatrix) = HipGMGSymbolicSetup(s)
-Gridap.Algebra.symbolic_setup(s::Union{HipCGSolver,HipFGMRESSolver,HipMINRESSolver}, ::PA.PSparseMatrix) = HipKrylovSymbolicSetup(s)
+Gridap.Algebra.symbolic_setup(s::Union{HipCGSolver,HipFGMRESSolver,HipMINRESSolver,HipGMRESSolver}, ::PA.PSparseMatrix) = HipKrylovSymbolicSetup(s)
 
 # Distributed block systems (BlockPMatrix / BlockPVector): the block handle gets its own communicator and one exchange plan
 # per block; blocks are passed as local rows with [own | ghost] columns (_local_operator), vectors as owned values.

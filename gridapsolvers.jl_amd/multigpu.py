@@ -395,6 +395,21 @@ class DistributedGMG:
         log._fill(res, hist)
         return log
 
+    def gmres_solve(self, b, x, m=5, maxiter=20, atol=1e-14, rtol=1e-6, restart=False, m_add=1, side="right"):
+        """GMRESSolver(m; Pr=this GMG) (side="right") or GMRESSolver(m; Pl=this GMG) ("left") on the partitioned system
+        (GMRESSolvers.jl:132-210); with a communicator the dots are all-reduced (the unfused Arnoldi sequence)"""
+        log = ConvergenceLog("GMRES", maxiter, atol, rtol)
+        pb, ms, _kb = _vec(b, self.n_own)
+        px, ms2, _kx = _vec(x, self.n_own, writable=True)
+        assert ms == ms2 and side in ("right", "left")
+        res = abi.Result()
+        hist = np.zeros(maxiter + 1)
+        abi.check(self.h, self._lib.gmg_gmres_solve(self.h, pb, px, ms, m, int(restart), m_add, maxiter, atol, rtol,
+                                                    int(side == "right"), int(side == "left"),
+                                                    C.byref(res), C.c_void_p(hist.ctypes.data), hist.size))
+        log._fill(res, hist)
+        return log
+
     def set_stream(self, stream=None):
         """gmg_set_stream: the handle's work on the caller's HIP stream (torch.cuda.Stream, integer hipStream_t, None = its own)"""
         abi.check(self.h, self._lib.gmg_set_stream(self.h, abi.stream_arg(stream)))
@@ -865,6 +880,21 @@ class DistributedBlockSolver:
         hist = np.zeros(maxiter + 1)
         abi.check_block(self.h, self._lib.gmg_block_fgmres_solve(self.h, pb, px, ms, m, 0, 1, maxiter, atol, rtol, 1, C.byref(res),
                                                                  C.c_void_p(hist.ctypes.data), hist.size))
+        log._fill(res, hist)
+        return log
+
+    def gmres_solve(self, b, x, m=20, maxiter=100, atol=1e-10, rtol=1e-12, restart=False, m_add=1, side="right"):
+        """GMRESSolver(m; Pr=this block preconditioner) (side="right") or with it as Pl ("left") on the partitioned block system
+        (GMRESSolvers.jl:132-210)"""
+        log = ConvergenceLog("GMRES", maxiter, atol, rtol)
+        pb, ms, _k1 = _vec(b, self.n)
+        px, ms2, _k2 = _vec(x, self.n, writable=True)
+        assert side in ("right", "left")
+        res = abi.Result()
+        hist = np.zeros(maxiter + 1)
+        abi.check_block(self.h, self._lib.gmg_block_gmres_solve(self.h, pb, px, ms, m, int(restart), m_add, maxiter, atol, rtol,
+                                                                int(side == "right"), int(side == "left"), C.byref(res),
+                                                                C.c_void_p(hist.ctypes.data), hist.size))
         log._fill(res, hist)
         return log
 

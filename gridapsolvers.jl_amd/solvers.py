@@ -15,6 +15,7 @@ julia/GridapSolversAMD.jl.
     CGSolver(Pl;...)                Krylov/CGSolvers.jl:19          CGSolver
     FGMRESSolver(m,Pr;...)          Krylov/FGMRESSolvers.jl:26      FGMRESSolver
     MINRESSolver(;Pl,...)           Krylov/MINRESSolvers.jl:16      MINRESSolver
+    GMRESSolver(m;Pr,Pl,...)        Krylov/GMRESSolvers.jl:25       GMRESSolver
     BlockDiagonalSolver(blocks,solvers)   BlockSolvers/BlockDiagonalSolvers.jl:20-45     BlockDiagonalSolver
     BlockTriangularSolver(blocks,solvers,coeffs,half)  BlockTriangularSolvers.jl:55-85    BlockTriangularSolver
     LinearSystemBlock / MatrixBlock BlockSolvers/BlockSolverInterfaces.jl            same names
@@ -35,7 +36,7 @@ from . import abi
 
 __all__ = [
     "JacobiLinearSolver", "RichardsonSmoother", "PatchSolver", "BlockJacobiSolver", "LUSolver",
-    "GMGLinearSolver", "CGSolver", "FGMRESSolver", "MINRESSolver", "ConvergenceLog", "PatchProlongationOperator",
+    "GMGLinearSolver", "CGSolver", "FGMRESSolver", "MINRESSolver", "GMRESSolver", "ConvergenceLog", "PatchProlongationOperator",
     "RichardsonLinearSolver", "BlockDiagonalSolver", "BlockTriangularSolver", "LinearSystemBlock", "MatrixBlock", "LinearSolverFromSmoother",
     "symbolic_setup", "numerical_setup", "numerical_setup_", "solve_", "mul_",
     "SOLVER_CONVERGED_ATOL", "SOLVER_CONVERGED_RTOL", "SOLVER_DIVERGED_MAXITER", "SOLVER_DIVERGED_BREAKDOWN",
@@ -235,6 +236,20 @@ class MINRESSolver:
 
     def __init__(self, Pl=None, maxiter=1000, atol=1e-12, rtol=1.0e-6, verbose=0, name="MINRES"):
         self.Pl = Pl
+        self.log = ConvergenceLog(name, maxiter, atol, rtol)
+
+
+class GMRESSolver:
+    """GMRESSolver(m; Pr=nothing, Pl=nothing, restart=false, m_add=1, maxiter=100, atol=1e-12, rtol=1e-6) --
+    GMRESSolvers.jl:25.  Each side is None, a GMGLinearSolver, a BlockDiagonalSolver / BlockTriangularSolver, or the tuple
+    (None | JacobiLinearSolver() | LinearSolverFromSmoother(finest pre-smoother), gmg) that CGSolver and MINRESSolver accept for
+    "the matrix of this handle, but not its GMG"; (None, block_solver) names a block system without preconditioning it.  Both
+    sides live on one handle, and its GMG (or block preconditioner) serves on one side only.  At least one side must name the
+    handle: GMRESSolver(10, Pr=(None, gmg)) is the unpreconditioned solver on gmg's finest matrix."""
+
+    def __init__(self, m, Pr=None, Pl=None, restart=False, m_add=1, maxiter=100, atol=1e-12, rtol=1.0e-6,
+                 verbose=False, name="GMRES"):
+        self.m, self.Pr, self.Pl, self.restart, self.m_add = int(m), Pr, Pl, bool(restart), int(m_add)
         self.log = ConvergenceLog(name, maxiter, atol, rtol)
 
 
@@ -807,11 +822,14 @@ class _KrylovSymbolicSetup:
 
 
 class _KrylovNumericalSetup:
-    """CGNumericalSetup / FGMRESNumericalSetup / MINRESNumericalSetup: holds the preconditioner's numerical
+    """CGNumericalSetup / FGMRESNumericalSetup / MINRESNumericalSetup / GMRESNumericalSetup: holds the preconditioner's numerical
     setup (CGSolvers.jl:50-55, FGMRESSolvers.jl:96-102)."""
 
     def __init__(self, solver, A, device_id=None):
         self.solver = solver
+        if isinstance(solver, GMRESSolver):
+            self._init_gmres(solver, A, device_id)
+            return
         P = solver.Pr if isinstance(solver, FGMRESSolver) else solver.Pl
         if isinstance(P, (BlockDiagonalSolver, BlockTriangularSolver)):
             self.pc_kind = 1
@@ -836,12 +854,52 @@ class _KrylovNumericalSetup:
         self.P_ns = GMGNumericalSetup(gmg, A, device_id)   # numerical_setup(symbolic_setup(Pl,A),A)
         self.n = self.P_ns.n
 
+    @staticmethod
+    def _side(P):
+        """one side of GMRESSolver -> (selector, the solver object that owns the handle | None)"""
+        if P is None:
+            return 0, None
+        if isinstance(P, (GMGLinearSolver, BlockDiagonalSolver, BlockTriangularSolver)):
+            return 1, P
+        if isinstance(P, tuple) and len(P) == 2:
+            if isinstance(P[1], (BlockDiagonalSolver, BlockTriangularSolver)) and P[0] is None:
+                return 0, P[1]
+            if isinstance(P[1], GMGLinearSolver):
+                if P[0] is None:
+                    return 0, P[1]
+                if isinstance(P[0], JacobiLinearSolver):
+                    return 2, P[1]
+                if isinstance(P[0], LinearSolverFromSmoother):
+                    if P[0].smoother is not P[1].pre_smoothers[0]:
+                        raise ValueError("LinearSolverFromSmoother must wrap the GMG's finest pre-smoother")
+                    return 3, P[1]
+        raise NotImplementedError("a GMRES side is None, a GMGLinearSolver, a block solver, or (None | JacobiLinearSolver() | "
+                                  "LinearSolverFromSmoother(...), gmg)")
+
+    def _init_gmres(self, solver, A, device_id):
+        (self.pr_kind, hr), (self.pl_kind, hl) = self._side(solver.Pr), self._side(solver.Pl)
+        if hr is not None and hl is not None and hr is not hl:
+            raise ValueError("Pr and Pl of GMRESSolver must name the same GMGLinearSolver / block solver (one device handle)")
+        host = hr if hr is not None else hl
+        if host is None:
+            raise ValueError("GMRESSolver needs a device handle: pass Pr=(None, gmg) for the unpreconditioned solver")
+        if self.pr_kind == 1 and self.pl_kind == 1:
+            raise ValueError("the handle's preconditioner serves as Pr or as Pl of GMRESSolver, not both")
+        self.pc_kind = self.pr_kind
+        # numerical_setup(symbolic_setup(Pr,A),A) and the same for Pl (GMRESSolvers.jl:96-97): one handle holds both sides
+        self.P_ns = (GMGNumericalSetup if isinstance(host, GMGLinearSolver) else BlockNumericalSetup)(host, A, device_id)
+        self.n = self.P_ns.n
+
+    def close(self):
+        """releases the preconditioner's numerical setup (GMRES: the one handle that holds Pr and Pl)"""
+        self.P_ns.close()
+
 
 def symbolic_setup(solver, A=None):
     """Gridap.Algebra.symbolic_setup(solver, A)."""
     if isinstance(solver, GMGLinearSolver):
         return GMGSymbolicSetup(solver)
-    if isinstance(solver, (CGSolver, FGMRESSolver, MINRESSolver, RichardsonLinearSolver)):
+    if isinstance(solver, (CGSolver, FGMRESSolver, MINRESSolver, GMRESSolver, RichardsonLinearSolver)):
         return _KrylovSymbolicSetup(solver)
     if isinstance(solver, (BlockDiagonalSolver, BlockTriangularSolver)):
         return BlockSymbolicSetup(solver)
@@ -907,6 +965,10 @@ def solve_(x, ns, b):
         elif isinstance(s, MINRESSolver):
             abi.check_block(g.h, g._lib.gmg_block_minres_solve(g.h, pb, px, ms, log.maxiter, log.atol, log.rtol, ns.pc_kind,
                                                                C.byref(res), C.c_void_p(hist.ctypes.data), hist.size))
+        elif isinstance(s, GMRESSolver):
+            abi.check_block(g.h, g._lib.gmg_block_gmres_solve(g.h, pb, px, ms, s.m, int(s.restart), s.m_add, log.maxiter,
+                                                              log.atol, log.rtol, ns.pr_kind, ns.pl_kind, C.byref(res),
+                                                              C.c_void_p(hist.ctypes.data), hist.size))
         else:
             abi.check_block(g.h, g._lib.gmg_block_fgmres_solve(g.h, pb, px, ms, s.m, int(s.restart), s.m_add, log.maxiter,
                                                                log.atol, log.rtol, ns.pc_kind, C.byref(res),
@@ -931,6 +993,10 @@ def solve_(x, ns, b):
         elif isinstance(s, MINRESSolver):
             abi.check(g.h, g._lib.gmg_minres_solve(g.h, pb, px, ms, log.maxiter, log.atol, log.rtol, ns.pc_kind,
                                                    C.byref(res), C.c_void_p(hist.ctypes.data), hist.size))
+        elif isinstance(s, GMRESSolver):
+            abi.check(g.h, g._lib.gmg_gmres_solve(g.h, pb, px, ms, s.m, int(s.restart), s.m_add, log.maxiter, log.atol,
+                                                  log.rtol, ns.pr_kind, ns.pl_kind, C.byref(res),
+                                                  C.c_void_p(hist.ctypes.data), hist.size))
         elif isinstance(s, RichardsonLinearSolver):
             abi.check(g.h, g._lib.gmg_richardson_solve(g.h, pb, px, ms, s.omega, log.maxiter, log.atol, log.rtol, ns.pc_kind,
                                                        C.byref(res), C.c_void_p(hist.ctypes.data), hist.size))
@@ -941,7 +1007,7 @@ def solve_(x, ns, b):
                                                       log.atol, log.rtol, ns.pc_kind, pl_kind, C.byref(res),
                                                       C.c_void_p(hist.ctypes.data), hist.size))
         log._fill(res, hist)
-        if ns.pc_kind == 1:
+        if ns.pc_kind == 1 or getattr(ns, "pl_kind", 0) == 1:
             g.fill_log()
         return x
     raise TypeError(f"no solve! for {type(ns).__name__}")

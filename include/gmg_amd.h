@@ -237,6 +237,10 @@ GMG_API int gmg_set_options(gmg_handle_t h, int mode, int cycle, int maxiter, do
  *                    sells_boxsweep_kernel; 2: every level that qualifies; 0: off) pat_box_t (0: planes per chain from the level's size)
  *   reductions       red_fused (1: inside CG the second stage of every dot is done by the kernel that consumes the scalar and the
  *                    norm is reduced + posted to the host by one launch; 0: one reduce launch per dot.  Same bits either way)
+ *                    gmres_fused* (1: where red_fused applies, a GMRES Arnoldi column runs as gmres_mgs_kernel launches -- each sums the
+ *                    previous dot's partials, subtracts the projection and accumulates the next dot's partials in one pass -- and
+ *                    gmres_normalize_kernel, the solution update as one gmres_combine_kernel; 0: a dot, a reduce and an axmy launch
+ *                    per coefficient and an axpy per basis vector.  Same bits either way)
  *   one-launch pass  persist (1) persist_fenced (0) persist_max_slices (0 = one workgroup per CU) persist_shared (0)
  *                    persist_wpb (1: smallest workgroup, in waves)
  *   coarsest level   coarse_host_max (1500) coarse_host_fallback_max (6000) coarse_auto_cg_min (20000: a dense-inverse request on a
@@ -324,6 +328,17 @@ GMG_API int gmg_fgmres_solve_pl(gmg_handle_t h, const double *b, double *x, int 
  * residual.  Nine work vectors are allocated on the handle by the first call. */
 GMG_API int gmg_minres_solve(gmg_handle_t h, const double *b, double *x, int memspace, int maxiter, double atol, double rtol,
                              int use_precond, gmg_result *res, double *hist, int hist_cap);
+/* solve!(x,ns::GMRESNumericalSetup,b): Krylov/GMRESSolvers.jl:132-210; krylov_mul!/krylov_residual!, KrylovUtils.jl:17-54
+ * (GMRESSolver(m;Pr,Pl,restart,m_add,maxiter,atol,rtol), :25).  use_precond_right (Pr) and use_precond_left (Pl) each take the
+ * values of use_precond in gmg_cg_solve: 0 nothing, 1 this GMG, 2 Jacobi on the finest matrix, 3 the finest pre-smoother.  The
+ * handle's GMG serves on one side only: both equal to 1 returns GMG_ERR_INVALID.  restart != 0: the basis holds m vectors and is
+ * restarted every m iterations (:31-37); otherwise it grows by m_add vectors when full (:154-157).  x = initial guess on entry;
+ * the history holds the 2-norm of the left-preconditioned residual estimate, one entry per iteration.  The first call allocates
+ * m + 1 basis vectors and zl on the handle, and zr once a Pr is selected (m + 3 vectors where FGMRES(m) keeps 2 m + 1); later
+ * calls reuse them, gmg_device_bytes counts them.  Option gmres_fused chooses the kernels of the Arnoldi column, same bits. */
+GMG_API int gmg_gmres_solve(gmg_handle_t h, const double *b, double *x, int memspace, int m, int restart, int m_add,
+                            int maxiter, double atol, double rtol, int use_precond_right, int use_precond_left,
+                            gmg_result *res, double *hist, int hist_cap);
 /* solve!(x,ns::RichardsonLinearNumericalSetup,b): RichardsonLinearSolvers.jl:79-106, scalar omega;
  * use_precond as in gmg_cg_solve (Pl = nothing / this GMG / Jacobi / the finest pre-smoother). */
 GMG_API int gmg_richardson_solve(gmg_handle_t h, const double *b, double *x, int memspace, double omega,
@@ -576,6 +591,11 @@ GMG_API int gmg_block_cg_solve(gmg_block_handle_t h, const double *b, double *x,
  * block-triangular P is not rejected -- the reference does not reject it -- but lies outside those assumptions. */
 GMG_API int gmg_block_minres_solve(gmg_block_handle_t h, const double *b, double *x, int memspace, int maxiter, double atol,
                                    double rtol, int use_precond, gmg_result *res, double *hist, int hist_cap);
+/* GMRESSolver(m;Pr,Pl) on the block system (GMRESSolvers.jl:132-210): use_precond_right / use_precond_left are 0 (nothing) or 1
+ * (this block preconditioner); at most one side may be 1 (GMG_ERR_INVALID otherwise).  Other arguments as gmg_gmres_solve. */
+GMG_API int gmg_block_gmres_solve(gmg_block_handle_t h, const double *b, double *x, int memspace, int m, int restart, int m_add,
+                                  int maxiter, double atol, double rtol, int use_precond_right, int use_precond_left,
+                                  gmg_result *res, double *hist, int hist_cap);
 /* ConvergenceLog of the last solve of diagonal block i (GMG / CG blocks) */
 GMG_API int gmg_block_diag_log(gmg_block_handle_t h, int i, gmg_result *res);
 
