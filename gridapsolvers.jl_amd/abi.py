@@ -18,7 +18,7 @@ PATCH_LU, PATCH_NOPIVOT = 0, 1
 OP_A, OP_P, OP_R = 0, 1, 2
 LEVEL_KRYLOV = -1          # GMG_LEVEL_KRYLOV: the separate Krylov operator of a finest level in the overlapping layout
 COARSE_DENSE_INVERSE, COARSE_CG_JACOBI, COARSE_HOST_CALLBACK = 0, 1, 2
-BLOCK_DIAGONAL, BLOCK_LOWER, BLOCK_UPPER = 0, 1, 2
+BLOCK_DIAGONAL, BLOCK_LOWER, BLOCK_UPPER, BLOCK_SCHUR = 0, 1, 2, 3
 BLOCK_GMG, BLOCK_CG_JACOBI, BLOCK_LU, BLOCK_JACOBI = 1, 2, 3, 4
 
 

@@ -1,10 +1,11 @@
-// block.inc.hpp -- block-diagonal / block-triangular preconditioners and the outer Krylov solve on a
+// block.inc.hpp -- block-diagonal / block-triangular / Schur complement preconditioners and the outer Krylov solve on a
 // block system (included at the end of gmg_amd.hip; everything runs on ONE stream of ONE device).
 //
 // This is SURVEY 8(f)(2): the glue that calls the GMG hot path once per outer FGMRES iteration in
 // the reference's Stokes / Navier-Stokes / Darcy applications (test/Applications/StokesGMG.jl:142-153):
 //   BlockDiagonalSolver   solve!: src/BlockSolvers/BlockDiagonalSolvers.jl:165-177
 //   BlockTriangularSolver solve!: src/BlockSolvers/BlockTriangularSolvers.jl:186-242
+//   SchurComplementSolver solve!: src/LinearSolvers/SchurComplementSolvers.jl:55-74 (2 blocks: A = block 0, S = block 1)
 // Block vectors are contiguous on the device, block i at off[i]..off[i+1].  Diagonal-block solvers:
 // a set-up gmg handle, CGSolver(JacobiLinearSolver()), LUSolver() (small blocks) or JacobiLinearSolver().
 
@@ -30,7 +31,7 @@ struct gmg_block_solver {
   std::map<std::pair<int, int>, HostCSR> hsys, hpre;
   std::map<std::pair<int, int>, DevCSR> sys, pre;
   std::vector<double> coeff;    // nb*nb row-major, BlockTriangularSolvers.jl:66 (default 1.0)
-  double *w = nullptr, *y = nullptr, *tmp = nullptr;               // BlockTriangularSolvers.jl:145-150
+  double *w = nullptr, *y = nullptr, *tmp = nullptr;               // BlockTriangularSolvers.jl:145-150; Schur: bu, bp in w, du in y
   double *kw = nullptr, *kp = nullptr, *kz = nullptr, *kr = nullptr, *st_b = nullptr, *st_x = nullptr;
   std::vector<double *> fg_V, fg_Z;
   bool setup_done = false;
@@ -66,6 +67,12 @@ struct gmg_block_solver {
   void setup()
   {
     HIP_CHECK(hipSetDevice(eng.device));
+    if (kind == GMG_BLOCK_SCHUR) {
+      REQUIRE(!distributed(), GMG_ERR_UNSUPPORTED, "the Schur complement solver is single-GPU (no partitioned application)");
+      // SchurComplementSolvers.jl:16-19: B and C are arguments of the solver; here the precond block or, without one, the system's
+      REQUIRE(hpre.count({0, 1}) || hsys.count({0, 1}), GMG_ERR_STATE, "Schur complement solver: block (0,1) (B) is missing: no precond block and no system block");
+      REQUIRE(hpre.count({1, 0}) || hsys.count({1, 0}), GMG_ERR_STATE, "Schur complement solver: block (1,0) (C) is missing: no precond block and no system block");
+    }
     detach();
     eng.free_all();
     sys.clear(); pre.clear();
@@ -223,9 +230,27 @@ struct gmg_block_solver {
     }
   }
 
+  // solve!(x,ns,y): SchurComplementSolvers.jl:55-74.  The solves of :65 and :67 write into the caller's x, whose content on entry is
+  // the initial guess of an iterative block solver; du (the y range of block 0) persists between applications (ns.caches, :58)
+  void schur_apply(double *x, const double *b)
+  {
+    const DevCSR *Bm = pre_block(0, 1), *Cm = pre_block(1, 0);
+    const int64_t nu = bsize(0);
+    double *xu = x + off[0], *xp = x + off[1];
+    double *du = y + off[0], *bu = w + off[0], *bp = w + off[1];             // :58 du,bu,bp = ns.caches
+    diag_solve(0, xu, b + off[0]);                                           // :65 solve!(x_u,A,y_u)
+    eng.spmv_resid(*Cm, xu, b + off[1], bp);                                 // :66 copy!(bp,y_p); mul!(bp,C,x_u,-1.0,1.0)
+    diag_solve(1, xp, bp);                                                   // :67 solve!(x_p,S,bp)
+    eng.spmv_set(*Bm, xp, bu);                                               // :69 mul!(bu,B,x_p)
+    diag_solve(0, du, bu);                                                   // :70 solve!(du,A,bu)
+    hipLaunchKernelGGL(axpy_kernel, dim3(gmg_solver::grid_for(nu)), dim3(256), 0, eng.stream, nu, -1.0, du, xu);   // :71 x_u .-= du
+    HIP_CHECK(hipGetLastError());
+  }
+
   // solve!(x,ns,b): BlockDiagonalSolvers.jl:165-177 / BlockTriangularSolvers.jl:186-242
   void precond_apply(double *x, const double *b)
   {
+    if (kind == GMG_BLOCK_SCHUR) { schur_apply(x, b); return; }
     for (int step = 0; step < nb; ++step) {
       const int iB = (kind == GMG_BLOCK_UPPER) ? nb - 1 - step : step;       // :218 NB:-1:1 / :190 1:NB
       const int64_t n = bsize(iB);
@@ -320,8 +345,9 @@ int gmg_block_create(gmg_block_handle_t *out, int nblocks, const int64_t *block_
     REQUIRE(out, GMG_ERR_INVALID, "null handle pointer");
     *out = nullptr;
     REQUIRE(nblocks >= 1 && block_sizes, GMG_ERR_INVALID, "at least one block required");
-    REQUIRE(kind == GMG_BLOCK_DIAGONAL || kind == GMG_BLOCK_LOWER || kind == GMG_BLOCK_UPPER, GMG_ERR_INVALID,
-            "kind must be diagonal, :lower or :upper (BlockTriangularSolvers.jl:63)");
+    REQUIRE(kind == GMG_BLOCK_DIAGONAL || kind == GMG_BLOCK_LOWER || kind == GMG_BLOCK_UPPER || kind == GMG_BLOCK_SCHUR, GMG_ERR_INVALID,
+            "kind must be diagonal, :lower or :upper (BlockTriangularSolvers.jl:63) or Schur complement");
+    REQUIRE(kind != GMG_BLOCK_SCHUR || nblocks == 2, GMG_ERR_INVALID, "the Schur complement solver takes 2 blocks (SchurComplementSolvers.jl:60)");
     int ndev = 0;
     HIP_CHECK(hipGetDeviceCount(&ndev));
     REQUIRE(ndev > 0, GMG_ERR_HIP, "no HIP device visible: libgmgamd has no CPU path");
@@ -506,6 +532,7 @@ int gmg_block_precond_apply(gmg_block_handle_t h, const double *b, double *x, in
     const int64_t n = h->N();
     const double *db = h->eng.in_vec(b, n, memspace, h->st_b);
     double *dx = (memspace == GMG_MEM_DEVICE) ? x : h->st_x;
+    if (h->kind == GMG_BLOCK_SCHUR && memspace == GMG_MEM_HOST) h->eng.h2d(dx, x, n);   // x on entry is the block solvers' initial guess
     h->precond_apply(dx, db);
     h->eng.out_vec(x, dx, n, memspace);
   });

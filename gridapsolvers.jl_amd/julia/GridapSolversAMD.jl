@@ -38,6 +38,7 @@ export HipGMGLinearSolver, HipCGSolver, HipFGMRESSolver, HipMINRESSolver, PatchT
 export HipRichardsonLinearSolver, HipBlockTriangularSolver, HipBlockDiagonalSolver, HipBlockFGMRESSolver, block_mul!, block_cg_solve!
 export block_minres_solve!
 export HipGMRESSolver, HipBlockGMRESSolver
+export HipSchurComplementSolver
 
 const libgmgamd = get(ENV, "LIBGMGAMD", joinpath(@__DIR__, "..", "libgmgamd.so"))
 
@@ -600,6 +601,7 @@ end
 # `mats[(i,j)]` replaces the system block in the preconditioner (MatrixBlock / an assembled BiformBlock).
 # ------------------------------------------------------------------------------------------------
 const GMG_BLOCK_DIAGONAL, GMG_BLOCK_LOWER, GMG_BLOCK_UPPER = Cint(0), Cint(1), Cint(2)
+const GMG_BLOCK_SCHUR = Cint(3)
 const GMG_BLOCK_GMG, GMG_BLOCK_CG_JACOBI, GMG_BLOCK_LU, GMG_BLOCK_JACOBI = Cint(1), Cint(2), Cint(3), Cint(4)
 
 function check_block(h::Ptr{Cvoid}, status::Cint)
@@ -614,7 +616,7 @@ struct HipBlockTriangularSolver <: Gridap.Algebra.LinearSolver
   solvers :: Vector{Any}
   mats    :: Dict{Tuple{Int,Int},Any}
   coeffs  :: Matrix{Float64}
-  half    :: Symbol                      # :upper | :lower | :diagonal (BlockDiagonalSolver)
+  half    :: Symbol                      # :upper | :lower | :diagonal (BlockDiagonalSolver) | :schur (HipSchurComplementSolver)
 end
 function HipBlockTriangularSolver(solvers::AbstractVector; mats=Dict{Tuple{Int,Int},Any}(),
                                   coeffs=fill(1.0,length(solvers),length(solvers)), half=:upper)
@@ -624,6 +626,32 @@ function HipBlockTriangularSolver(solvers::AbstractVector; mats=Dict{Tuple{Int,I
 end
 HipBlockDiagonalSolver(solvers::AbstractVector; mats=Dict{Tuple{Int,Int},Any}()) =
   HipBlockTriangularSolver(solvers; mats=mats, half=:diagonal)
+
+# SchurComplementSolver(A,B,C,S) (LinearSolvers/SchurComplementSolvers.jl:11-26; solve!: :55-74) on the block handle, kind
+# GMG_BLOCK_SCHUR.  A and S are, as in the reference, numerical setups where the device has them: a HipGMGNumericalSetup is
+# borrowed as a handle (it must outlive the block setup).  The other block solvers have no device numerical setup of their own,
+# so they are given as `solver => matrix` with solver = CGSolver(JacobiLinearSolver()) | LUSolver() | JacobiLinearSolver()
+# (or a HipGMGLinearSolver, set up on `matrix` by the block setup).  B and C are SparseMatrixCSC.  The result serves wherever a
+# HipBlockTriangularSolver does: solve!, HipBlockFGMRESSolver(m, P), HipBlockGMRESSolver(m, P; side), e.g. the reference's
+# GMRESSolver(20; Pr = SchurComplementSolver(A_ns, B, C, PS_ns)) (test/LinearSolvers/SchurComplementSolversTests.jl:98-114).
+# The system matrix given to numerical_setup serves mul! and the outer residual only.  Single-GPU.
+function HipSchurComplementSolver(A, B::SparseMatrixCSC, C::SparseMatrixCSC, S)
+  mats = Dict{Tuple{Int,Int},Any}((1,2) => B, (2,1) => C)
+  solvers = Any[]
+  for (i,X) in enumerate((A,S))
+    if X isa HipGMGNumericalSetup
+      push!(solvers, X)
+    else
+      X isa Pair || error("HipSchurComplementSolver: A and S are a HipGMGNumericalSetup or `solver => matrix`")
+      push!(solvers, first(X)); mats[(i,i)] = last(X)
+    end
+  end
+  nA = solvers[1] isa HipGMGNumericalSetup ? solvers[1].n : size(mats[(1,1)],1)
+  nS = solvers[2] isa HipGMGNumericalSetup ? solvers[2].n : size(mats[(2,2)],1)
+  size(B) == (nA,nS) || error("HipSchurComplementSolver: B has size $(size(B)), expected $((nA,nS))")
+  size(C) == (nS,nA) || error("HipSchurComplementSolver: C has size $(size(C)), expected $((nS,nA))")
+  return HipBlockTriangularSolver(solvers, mats, fill(1.0,2,2), :schur)
+end
 
 struct HipBlockFGMRESSolver <: Gridap.Algebra.LinearSolver
   m :: Int; restart :: Bool; m_add :: Int
@@ -684,7 +712,7 @@ end
 function _block_numerical_setup(P::HipBlockTriangularSolver, mat, owner)
   B  = blocks(mat); NB = length(P.solvers)
   sizes = Int64[size(B[i,i],1) for i in 1:NB]
-  kind = P.half === :upper ? GMG_BLOCK_UPPER : (P.half === :lower ? GMG_BLOCK_LOWER : GMG_BLOCK_DIAGONAL)
+  kind = P.half === :upper ? GMG_BLOCK_UPPER : (P.half === :lower ? GMG_BLOCK_LOWER : (P.half === :schur ? GMG_BLOCK_SCHUR : GMG_BLOCK_DIAGONAL))
   href = Ref{Ptr{Cvoid}}(C_NULL)
   check_block(C_NULL, ccall((:gmg_block_create, libgmgamd), Cint, (Ref{Ptr{Cvoid}},Cint,Ptr{Int64},Cint,Cint), href, NB, sizes, kind, 0))
   ns = HipBlockNumericalSetup(owner, href[], Any[], sum(sizes))
@@ -700,6 +728,11 @@ function _block_numerical_setup(P::HipBlockTriangularSolver, mat, owner)
     end
   end
   for (i,s) in enumerate(P.solvers)
+    if s isa HipGMGNumericalSetup                  # borrowed as it is (HipSchurComplementSolver); kept alive with the block setup
+      push!(ns.block_ns, s)
+      check_block(h, ccall((:gmg_block_set_diag_gmg, libgmgamd), Cint, (Ptr{Cvoid},Cint,Ptr{Cvoid}), h, i-1, s.handle))
+      continue
+    end
     Mi = get(P.mats, (i,i), B[i,i])
     if s isa HipGMGLinearSolver
       g = numerical_setup(symbolic_setup(s,Mi),Mi); push!(ns.block_ns, g)
@@ -730,10 +763,10 @@ _flat(v::AbstractVector) = v isa Vector{Float64} ? v : parent(v)
 
 function _fill_block_logs!(ns::HipBlockNumericalSetup, P::HipBlockTriangularSolver)
   for (i,s) in enumerate(P.solvers)
-    (s isa HipGMGLinearSolver || s isa GridapSolvers.LinearSolvers.CGSolver) || continue
+    (s isa HipGMGLinearSolver || s isa HipGMGNumericalSetup || s isa GridapSolvers.LinearSolvers.CGSolver) || continue
     res = Ref(GmgResult(0,0,0.0,0.0))
     check_block(ns.handle, ccall((:gmg_block_diag_log, libgmgamd), Cint, (Ptr{Cvoid},Cint,Ref{GmgResult}), ns.handle, i-1, res))
-    s.log.num_iters = res[].niters
+    (s isa HipGMGNumericalSetup ? s.solver.log : s.log).num_iters = res[].niters
   end
 end
 

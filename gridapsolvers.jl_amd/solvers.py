@@ -18,6 +18,7 @@ julia/GridapSolversAMD.jl.
     GMRESSolver(m;Pr,Pl,...)        Krylov/GMRESSolvers.jl:25       GMRESSolver
     BlockDiagonalSolver(blocks,solvers)   BlockSolvers/BlockDiagonalSolvers.jl:20-45     BlockDiagonalSolver
     BlockTriangularSolver(blocks,solvers,coeffs,half)  BlockTriangularSolvers.jl:55-85    BlockTriangularSolver
+    SchurComplementSolver(A,B,C,S)  SchurComplementSolvers.jl:11-26 SchurComplementSolver (A, S = (solver, matrix) pairs)
     LinearSystemBlock / MatrixBlock BlockSolvers/BlockSolverInterfaces.jl            same names
     symbolic_setup / numerical_setup / numerical_setup! / solve!    same names (solve_ = solve!)
     ConvergenceLog                  SolverInterfaces/ConvergenceLogs.jl:42   ConvergenceLog
@@ -37,7 +38,7 @@ from . import abi
 __all__ = [
     "JacobiLinearSolver", "RichardsonSmoother", "PatchSolver", "BlockJacobiSolver", "LUSolver",
     "GMGLinearSolver", "CGSolver", "FGMRESSolver", "MINRESSolver", "GMRESSolver", "ConvergenceLog", "PatchProlongationOperator",
-    "RichardsonLinearSolver", "BlockDiagonalSolver", "BlockTriangularSolver", "LinearSystemBlock", "MatrixBlock", "LinearSolverFromSmoother",
+    "RichardsonLinearSolver", "BlockDiagonalSolver", "BlockTriangularSolver", "SchurComplementSolver", "LinearSystemBlock", "MatrixBlock", "LinearSolverFromSmoother",
     "symbolic_setup", "numerical_setup", "numerical_setup_", "solve_", "mul_",
     "SOLVER_CONVERGED_ATOL", "SOLVER_CONVERGED_RTOL", "SOLVER_DIVERGED_MAXITER", "SOLVER_DIVERGED_BREAKDOWN",
 ]
@@ -241,7 +242,7 @@ class MINRESSolver:
 
 class GMRESSolver:
     """GMRESSolver(m; Pr=nothing, Pl=nothing, restart=false, m_add=1, maxiter=100, atol=1e-12, rtol=1e-6) --
-    GMRESSolvers.jl:25.  Each side is None, a GMGLinearSolver, a BlockDiagonalSolver / BlockTriangularSolver, or the tuple
+    GMRESSolvers.jl:25.  Each side is None, a GMGLinearSolver, a BlockDiagonalSolver / BlockTriangularSolver / SchurComplementSolver, or the tuple
     (None | JacobiLinearSolver() | LinearSolverFromSmoother(finest pre-smoother), gmg) that CGSolver and MINRESSolver accept for
     "the matrix of this handle, but not its GMG"; (None, block_solver) names a block system without preconditioning it.  Both
     sides live on one handle, and its GMG (or block preconditioner) serves on one side only.  At least one side must name the
@@ -302,6 +303,54 @@ class BlockTriangularSolver:
         if self.coeffs.shape != (nb, nb):
             raise ValueError("coeffs must match blocks")
         self.half = half
+
+
+def _is_block_diag_solver(sv):
+    """what BlockNumericalSetup can put on a diagonal block"""
+    return isinstance(sv, (GMGLinearSolver, LUSolver, JacobiLinearSolver)) or \
+        (isinstance(sv, CGSolver) and isinstance(sv.Pl, JacobiLinearSolver) and not sv.flexible)
+
+
+class SchurComplementSolver:
+    """SchurComplementSolver(A, B, C, S) -- SchurComplementSolvers.jl:11-26: the block factorisation of [A B; C D] with
+    S ~ D - C A^-1 B (solve!: :55-74).  The reference receives A and S as numerical setups; here each is the pair
+    (solver, matrix) that stands for numerical_setup(symbolic_setup(solver, matrix), matrix), with solver one of
+    GMGLinearSolver | CGSolver(JacobiLinearSolver()) | LUSolver() | JacobiLinearSolver(); matrix may be None for a
+    GMGLinearSolver (its own smatrices[0]).  B and C are CSR-like matrices of shape (n_A, n_S) and (n_S, n_A).
+    The matrix given to numerical_setup (2 x 2 nested) serves mul! and the outer Krylov residual only, as in the reference."""
+
+    half = "schur"
+
+    def __init__(self, A, B, C, S):
+        sizes = []
+        for name, pair in (("A", A), ("S", S)):
+            if not (isinstance(pair, (tuple, list)) and len(pair) == 2):
+                raise TypeError(f"SchurComplementSolver: {name} must be a (solver, matrix) pair")
+            sv, M = pair
+            if not _is_block_diag_solver(sv):
+                raise TypeError(f"SchurComplementSolver: the solver of {name} must be a GMGLinearSolver, CGSolver(JacobiLinearSolver()), "
+                                "LUSolver() or JacobiLinearSolver()")
+            if M is None:
+                if not isinstance(sv, GMGLinearSolver):
+                    raise ValueError(f"SchurComplementSolver: {name} needs a matrix (only a GMGLinearSolver brings its own)")
+                M = sv.smatrices[0]
+            if M.shape[0] != M.shape[1]:
+                raise ValueError(f"SchurComplementSolver: the matrix of {name} must be square")
+            sizes.append((sv, M))
+        (sA, MA), (sS, MS) = sizes
+        nA, nS = int(MA.shape[0]), int(MS.shape[0])
+        if tuple(B.shape) != (nA, nS):
+            raise ValueError(f"SchurComplementSolver: B has shape {tuple(B.shape)}, expected {(nA, nS)}")
+        if tuple(C.shape) != (nS, nA):
+            raise ValueError(f"SchurComplementSolver: C has shape {tuple(C.shape)}, expected {(nS, nA)}")
+        self.A, self.B, self.C, self.S = (sA, MA), B, C, (sS, MS)
+        # the fields BlockNumericalSetup reads: every block is the solver's own (MatrixBlock), none is taken from the system
+        self.solvers = [sA, sS]
+        self.blocks = [[MatrixBlock(MA), MatrixBlock(B)], [MatrixBlock(C), MatrixBlock(MS)]]
+        self.coeffs = np.ones((2, 2))          # not consulted by the Schur application
+
+
+_BLOCK_SOLVERS = (BlockDiagonalSolver, BlockTriangularSolver, SchurComplementSolver)
 
 
 # ----------------------------------------------------------------------------
@@ -713,10 +762,10 @@ class BlockSymbolicSetup:
 
 
 class BlockNumericalSetup:
-    """BlockDiagonalSolverNS / BlockTriangularSolverNS (BlockTriangularSolvers.jl:132-152) on a native handle.
-    `mat` is the block system matrix as a nested list (None = zero block)."""
+    """BlockDiagonalSolverNS / BlockTriangularSolverNS (BlockTriangularSolvers.jl:132-152) / SchurComplementNumericalSetup
+    (SchurComplementSolvers.jl:36-53) on a native handle.  `mat` is the block system matrix as a nested list (None = zero block)."""
 
-    _HALF = {"diagonal": abi.BLOCK_DIAGONAL, "lower": abi.BLOCK_LOWER, "upper": abi.BLOCK_UPPER}
+    _HALF = {"diagonal": abi.BLOCK_DIAGONAL, "lower": abi.BLOCK_LOWER, "upper": abi.BLOCK_UPPER, "schur": abi.BLOCK_SCHUR}
 
     def __init__(self, solver, mat, device_id=None):
         lib = abi.load()
@@ -831,7 +880,7 @@ class _KrylovNumericalSetup:
             self._init_gmres(solver, A, device_id)
             return
         P = solver.Pr if isinstance(solver, FGMRESSolver) else solver.Pl
-        if isinstance(P, (BlockDiagonalSolver, BlockTriangularSolver)):
+        if isinstance(P, _BLOCK_SOLVERS):
             self.pc_kind = 1
             self.P_ns = BlockNumericalSetup(P, A, device_id)
             self.n = self.P_ns.n
@@ -859,10 +908,10 @@ class _KrylovNumericalSetup:
         """one side of GMRESSolver -> (selector, the solver object that owns the handle | None)"""
         if P is None:
             return 0, None
-        if isinstance(P, (GMGLinearSolver, BlockDiagonalSolver, BlockTriangularSolver)):
+        if isinstance(P, (GMGLinearSolver,) + _BLOCK_SOLVERS):
             return 1, P
         if isinstance(P, tuple) and len(P) == 2:
-            if isinstance(P[1], (BlockDiagonalSolver, BlockTriangularSolver)) and P[0] is None:
+            if isinstance(P[1], _BLOCK_SOLVERS) and P[0] is None:
                 return 0, P[1]
             if isinstance(P[1], GMGLinearSolver):
                 if P[0] is None:
@@ -901,7 +950,7 @@ def symbolic_setup(solver, A=None):
         return GMGSymbolicSetup(solver)
     if isinstance(solver, (CGSolver, FGMRESSolver, MINRESSolver, GMRESSolver, RichardsonLinearSolver)):
         return _KrylovSymbolicSetup(solver)
-    if isinstance(solver, (BlockDiagonalSolver, BlockTriangularSolver)):
+    if isinstance(solver, _BLOCK_SOLVERS):
         return BlockSymbolicSetup(solver)
     raise TypeError(f"no symbolic_setup for {type(solver).__name__}")
 

@@ -529,14 +529,25 @@ GMG_API int gmg_device_bytes(gmg_handle_t h, int64_t *bytes);
  * first, must outlive the block handle's use of it and issues its work on the block handle's stream
  * from gmg_block_setup until gmg_block_destroy. */
 typedef struct gmg_block_solver *gmg_block_handle_t;
-enum gmg_block_kind { GMG_BLOCK_DIAGONAL = 0, GMG_BLOCK_LOWER = 1, GMG_BLOCK_UPPER = 2 };
+enum gmg_block_kind {
+  GMG_BLOCK_DIAGONAL = 0, GMG_BLOCK_LOWER = 1, GMG_BLOCK_UPPER = 2,
+  GMG_BLOCK_SCHUR = 3       /* SchurComplementSolver(A,B,C,S), LinearSolvers/SchurComplementSolvers.jl:11-74 */
+};
 enum gmg_block_diag_kind {
   GMG_BLOCK_GMG = 1,        /* a GMGLinearSolver numerical setup (gmg handle) */
   GMG_BLOCK_CG_JACOBI = 2,  /* CGSolver(JacobiLinearSolver();maxiter,atol,rtol), CGSolvers.jl:73-120 */
   GMG_BLOCK_LU = 3,         /* LUSolver() on a small block: dense inverse on the device */
   GMG_BLOCK_JACOBI = 4      /* JacobiLinearSolver(), JacobiLinearSolvers.jl:43-47 */
 };
-/* BlockDiagonalSolver(solvers) / BlockTriangularSolver(blocks,solvers,coeffs,half): BlockTriangularSolvers.jl:55-85 */
+/* BlockDiagonalSolver(solvers) / BlockTriangularSolver(blocks,solvers,coeffs,half): BlockTriangularSolvers.jl:55-85.
+ * kind = GMG_BLOCK_SCHUR (exactly 2 blocks, GMG_ERR_INVALID otherwise): the block factorisation of [A B; C D] with S ~ D - C A^-1 B,
+ *   solve!(x_u,A,y_u); bp = y_p - C x_u; solve!(x_p,S,bp); bu = B x_p; solve!(du,A,bu); x_u .-= du     (SchurComplementSolvers.jl:65-71)
+ * The solver of block 0 is A's and that of block 1 is S's (gmg_block_set_diag_*; S brings its own matrix when the system has no
+ * (1,1) block); B = block (0,1) and C = block (1,0), from gmg_block_set_precond_block or else the system; gmg_block_setup gives
+ * GMG_ERR_STATE when one is absent.  The two first solves write into the caller's x: its content on entry is the initial guess of
+ * an iterative block solver (CG-Jacobi, a GMG in solver mode), and du is kept between applications -- the triangular kinds solve
+ * into an internal vector instead.  Coefficients are not consulted.  Single-GPU: GMG_ERR_UNSUPPORTED at gmg_block_setup on a
+ * handle with a communicator of more than one rank. */
 GMG_API int gmg_block_create(gmg_block_handle_t *h, int nblocks, const int64_t *block_sizes, int kind, int device_id);
 GMG_API int gmg_block_destroy(gmg_block_handle_t h);
 GMG_API const char *gmg_block_last_error(gmg_block_handle_t h);
