@@ -7,7 +7,7 @@ are checked on the levels the benchmark runs, at the rows where launch geometry 
   edge_rows        the rows of a (nx, ny, nz)-node level where slices, planes, walk chains and the level itself begin and end
   row_reference    per sampled row: the float64 sum in CSR order, the exact value and the bound gamma_k * sum|a_ij x_j|
   check_rows       asserts a device result on sampled rows against row_reference (bit for bit unless the level sums with FMA taps)
-  dot_reference    the exact dot and the bound of the order dot_partial_kernel + reduce_final_kernel sum in
+  dot_reference    the exact dot and the bound of the order dot_partial_kernel + reduce_final_kernel sum in (either path)
 
 "exact" = math.fsum of the error-free products (TwoProduct by Veltkamp splitting: a*b = p + e exactly), i.e. the exact sum
 correctly rounded once."""
@@ -156,21 +156,65 @@ def dot_exact(a, b, chunk=1 << 20):
     return math.fsum(terms())
 
 
-def dot_depth(n):
+def dot_depth(n, vec=True):
     """Longest chain of roundings a product passes through in dot_partial_kernel + reduce_final_kernel: the product itself,
     the lane's grid-stride accumulation (two terms per step of the 16-byte path, plus the odd tail on lane 0), the 64-lane
     butterfly (6), the four-wave combine (2), the strided accumulation of the <= 1024 partials over 256 lanes, again 6 + 2.
-    It is NOT log2(n) + c: above nb * 256 * 2 elements the lanes accumulate sequentially (93 terms per lane at 288^3)."""
+    It is NOT log2(n) + c: above nb * 256 * 2 elements the lanes accumulate sequentially (93 terms per lane at 288^3).
+    vec = False: the path the kernel takes when an operand is not 16-byte aligned -- the same grid of nb workgroups, but one
+    element per lane and step, ceil(n / (nb * 256)) terms per lane, and no odd tail."""
     n = int(n)
     nb = max(1, min(RED_BLOCKS, (n // 2 + K_BLOCK - 1) // K_BLOCK))
-    lane = 2 * (-(-(n // 2) // (nb * K_BLOCK))) + (n & 1)
+    if vec:
+        lane = 2 * (-(-(n // 2) // (nb * K_BLOCK))) + (n & 1)
+    else:
+        lane = -(-n // (nb * K_BLOCK))
     return 1 + lane + 6 + 2 + (-(-nb // K_BLOCK)) + 6 + 2
 
 
-def dot_reference(a, b):
-    """(exact, bound) with bound = gamma_{dot_depth(n)} * sum |a_i b_i|."""
+def dot_reference(a, b, vec=True):
+    """(exact, bound) with bound = gamma_{dot_depth(n, vec)} * sum |a_i b_i|."""
     a = np.asarray(a, dtype=np.float64); b = np.asarray(b, dtype=np.float64)
-    return dot_exact(a, b), float(gamma(dot_depth(a.size)) * np.sum(np.abs(a * b)))
+    return dot_exact(a, b), float(gamma(dot_depth(a.size, vec)) * np.sum(np.abs(a * b)))
+
+
+def _tree(s, d):
+    """block_sum of kernels.hpp on (..., 256) lanes: the xor butterfly over 64 lanes, then (sh0 + sh1) + (sh2 + sh3); s = values,
+    d = chain lengths (-1: the lane holds the literal 0.0, adding it is exact) -> (value, chain) of thread 0"""
+    def add(s1, d1, s2, d2):
+        return s1 + s2, np.where((d1 >= 0) & (d2 >= 0), np.maximum(d1, d2) + 1, np.maximum(d1, d2))
+    s = s.reshape(s.shape[:-1] + (4, 64)); d = d.reshape(s.shape)
+    lane = np.arange(64)
+    off = 32
+    while off:
+        s, d = add(s, d, s[..., lane ^ off], d[..., lane ^ off])
+        off >>= 1
+    s, d = s[..., 0], d[..., 0]
+    s01, d01 = add(s[..., 0], d[..., 0], s[..., 1], d[..., 1])
+    s23, d23 = add(s[..., 2], d[..., 2], s[..., 3], d[..., 3])
+    return add(s01, d01, s23, d23)
+
+
+def dot_emulate_scalar_path(a, b):
+    """dot_partial_kernel with vec == 0 followed by reduce_final_kernel, operation by operation in float64 on the host:
+    -> (value, length of the longest chain of roundings a product passed through)."""
+    a = np.asarray(a, dtype=np.float64); b = np.asarray(b, dtype=np.float64)
+    n = a.size
+    nb = max(1, min(RED_BLOCKS, (n // 2 + K_BLOCK - 1) // K_BLOCK))
+    lanes = nb * K_BLOCK
+    s, d = np.zeros(lanes), np.full(lanes, -1)
+    for start in range(0, n, lanes):                       # one trip of the grid-stride loop: s += a[i] * b[i]
+        m = min(lanes, n - start)
+        s[:m] = s[:m] + a[start:start + m] * b[start:start + m]
+        d[:m] = np.where(d[:m] >= 0, d[:m] + 1, 1)         # (0.0 + p is exact: the product's own rounding only)
+    parts, dparts = _tree(s.reshape(nb, K_BLOCK), d.reshape(nb, K_BLOCK))
+    s2, d2 = np.zeros(K_BLOCK), np.full(K_BLOCK, -1)
+    for start in range(0, nb, K_BLOCK):                    # reduce_final_kernel: s += partials[i], i = lane, lane + 256, ...
+        m = min(K_BLOCK, nb - start)
+        s2[:m] = s2[:m] + parts[start:start + m]
+        d2[:m] = np.where(d2[:m] >= 0, np.maximum(d2[:m], dparts[start:start + m]) + 1, dparts[start:start + m])
+    v, c = _tree(s2, d2)
+    return float(v), int(c)
 
 
 # ---------------------------------------------------------------- per-kernel checks of every level of a Q1 hierarchy
@@ -252,19 +296,35 @@ def check_q1_levels(ns, H, go, orc, families, seed=0, post_levels=(0,), coarse_t
     return report
 
 
-def check_dot(ns, n, seed, what=""):
+def check_dot(ns, n, seed, what="", offset=0):
     """ns.dot of two device vectors of length n against the exact dot: a random pair, and b = -a + tiny (heavy cancellation: the
-    result is ~1e-12 of sum|a b|, so the bound, not a relative error, is the gate).  Returns the worst |d - exact| / bound."""
+    result is ~1e-12 of sum|a b|, so the bound, not a relative error, is the gate).  Returns the worst |d - exact| / bound.
+    offset = k or (ka, kb): a and / or b are the views buf[k : k + n] of (n + k + 1)-element device tensors -- an odd k puts the
+    vector 8 bytes off a 16-byte boundary, which takes dot_partial_kernel's one-element path; the bound is that path's."""
     import torch
     rng = np.random.default_rng(seed)
     a = rng.uniform(-1, 1, n)
     out = 0.0
+    ka, kb = (offset, offset) if np.isscalar(offset) else offset
+
+    def place(v, k):
+        if k == 0:
+            return torch.from_numpy(v).cuda()
+        buf = torch.zeros(n + k + 1, dtype=torch.float64, device="cuda")
+        buf[k:k + n].copy_(torch.from_numpy(v))
+        return buf[k:k + n]
+
     for b in (rng.uniform(-1, 1, n), -a + 1e-12 * rng.uniform(-1, 1, n)):
-        ad, bd = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
+        ad, bd = place(a, ka), place(b, kb)
+        vec = ad.data_ptr() % 16 == 0 and bd.data_ptr() % 16 == 0
+        assert vec == (ka % 2 == 0 and kb % 2 == 0), (ad.data_ptr() % 16, bd.data_ptr() % 16)
         torch.cuda.synchronize()
         d = ns.dot(ad, bd)
-        ex, bound = dot_reference(a, b)
-        assert abs(d - ex) <= bound, f"dot n={n} {what}: {d!r} vs exact {ex!r}, bound {bound:.3g}"
+        ex, bound = dot_reference(a, b, vec)
+        assert abs(d - ex) <= bound, f"dot n={n} offsets ({ka}, {kb}) {what}: {d!r} vs exact {ex!r}, bound {bound:.3g}"
+        if not vec:                                        # the order is fixed and no product is contracted: the emulation's bits
+            em = dot_emulate_scalar_path(a, b)[0]
+            assert d == em, f"dot n={n} offsets ({ka}, {kb}) {what}: {d!r} is not the one-element path's sum {em!r}"
         out = max(out, abs(d - ex) / bound if bound > 0 else 0.0)
     return out
 

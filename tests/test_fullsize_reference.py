@@ -87,6 +87,27 @@ def test_dot_reference_is_exact_under_cancellation():
     assert fr.dot_depth(1) == 1 + 1 + 17 and fr.dot_depth(288 ** 3) > np.log2(288 ** 3) + 60
 
 
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 255, 256, 257, 4095, 4097, (1 << 20) + 3, 131074, 524289])
+def test_dot_depth_of_the_unaligned_path_bounds_its_emulated_chain(n):
+    """dot_partial_kernel's one-element path (an operand not 16-byte aligned) + reduce_final_kernel, emulated operation by
+    operation (fr.dot_emulate_scalar_path) at the edge lengths of tests/test_gpu_fullsize.py, 131074 and 524289: no product
+    passes through more roundings than dot_depth(n, vec=False), the emulated value is within that bound of the exact dot on
+    random data and under heavy cancellation, and the 16-byte path's depth is a different number where the orders differ."""
+    rng = np.random.default_rng(3000 + n)
+    a = rng.uniform(-1, 1, n)
+    for b in (rng.uniform(-1, 1, n), -a + 1e-12 * rng.uniform(-1, 1, n)):
+        v, chain = fr.dot_emulate_scalar_path(a, b)
+        assert 1 <= chain <= fr.dot_depth(n, vec=False)
+        ex, bound = fr.dot_reference(a, b, vec=False)
+        assert abs(v - ex) <= bound
+        assert abs(v - ex) <= float(fr.gamma(chain) * np.sum(np.abs(a * b)))
+    nb = max(1, min(fr.RED_BLOCKS, (n // 2 + fr.K_BLOCK - 1) // fr.K_BLOCK))
+    assert fr.dot_depth(n, vec=False) == 1 + -(-n // (nb * fr.K_BLOCK)) + 8 + -(-nb // fr.K_BLOCK) + 8
+    assert fr.dot_depth(n) == fr.dot_depth(n, vec=True)
+    if n <= 2 * fr.K_BLOCK:                               # one workgroup: the whole vector is one term per lane (two at n > 256)
+        assert fr.dot_depth(n, vec=False) == 1 + (1 if n <= fr.K_BLOCK else 2) + 17
+
+
 def test_patch_precond_reference_is_the_oracles_patch_operator(po, orc):
     """patch_precond_reference (blocks from plane_rows, numpy LU) against the oracle's additive vertex-star patch operator on a
     small streamed Q2 level: the reference the sampled config-3 check stands on."""

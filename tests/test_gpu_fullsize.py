@@ -98,6 +98,19 @@ def test_dot_edge_lengths_against_the_exact_dot(S, po):
     ns.close()
 
 
+def test_dot_edge_lengths_unaligned_against_the_exact_dot(S, po):
+    """The same on vectors 8 bytes off a 16-byte boundary (views buf[1 : n + 1] of device tensors; both operands, and a alone):
+    dot_partial_kernel then takes its one-element path, whose order of summation differs -- the bound is
+    fullsize_reference.dot_depth(n, vec=False), which tests/test_fullsize_reference.py checks against an emulation of that order.
+    Also at 131074 (the first length with 257 partials) and 524289 (the odd length after which the grid stops growing)."""
+    H = po.build_hierarchy((8, 8, 8), 2, 1)
+    ns = setup(S, make_gmg(S, H), H["mats"][0])
+    for offset in ((1, 1), (1, 0)):
+        worst = {n: fr.check_dot(ns, n, 2000 + n, offset=offset) for n in DOT_EDGE_N + [131074, 524289]}
+        print("dot, offsets %s: |d - exact| / bound:" % (offset,), {n: f"{v:.3g}" for n, v in worst.items()})
+    ns.close()
+
+
 def test_prand_64cubed_cg_gmg_against_the_oracle(S, po, orc):
     """Problem P-rand (b ~ U(-1,1), po.random_rhs) on Q1 64^3, 4 levels, CG + GMG to rtol 1e-8: the oracle's iteration count and
     flag, its residual history within TOL_HIST, its solution within 1e-10."""
