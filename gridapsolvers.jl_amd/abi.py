@@ -105,6 +105,18 @@ SYMBOLS = {
     "gmg_precond_apply": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int],
     "gmg_coarse_solve": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
     "gmg_dot": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double)],
+    "gmg_nullspace_set": [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int],
+    "gmg_nullspace_get": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int],
+    "gmg_nullspace_size": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64)],
+    "gmg_nullspace_orthonormalize": [C.c_void_p, C.c_int],
+    "gmg_nullspace_project": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int],
+    "gmg_nullspace_make_orthogonal": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
+    "gmg_nullspace_reconstruct": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
+    "gmg_nullspace_gram": [C.c_void_p, C.c_void_p],
+    "gmg_nullspace_dots": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
+    "gmg_nullspace_image_norms": [C.c_void_p, C.c_void_p],
+    "gmg_nullspace_project_guess": [C.c_void_p, C.c_int],
+    "gmg_set_coarse_nullspace": [C.c_void_p, C.c_int, C.c_void_p, C.c_int64],
     "gmg_comm_unique_id": [C.c_char_p, C.c_char_p],
     "gmg_comm_init_rccl": [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int],
     "gmg_comm_selftest": [C.c_void_p, C.POINTER(C.c_double)],
@@ -159,6 +171,17 @@ SYMBOLS = {
     "gmg_block_gmres_solve": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                               C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Result), C.c_void_p, C.c_int],
     "gmg_block_diag_log": [C.c_void_p, C.c_int, C.POINTER(Result)],
+    "gmg_block_nullspace_set": [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int],
+    "gmg_block_nullspace_get": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int],
+    "gmg_block_nullspace_size": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64)],
+    "gmg_block_nullspace_orthonormalize": [C.c_void_p, C.c_int],
+    "gmg_block_nullspace_project": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int],
+    "gmg_block_nullspace_make_orthogonal": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
+    "gmg_block_nullspace_reconstruct": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
+    "gmg_block_nullspace_gram": [C.c_void_p, C.c_void_p],
+    "gmg_block_nullspace_dots": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
+    "gmg_block_nullspace_image_norms": [C.c_void_p, C.c_void_p],
+    "gmg_block_nullspace_project_guess": [C.c_void_p, C.c_int],
 }
 
 HOST_EXCHANGE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double),

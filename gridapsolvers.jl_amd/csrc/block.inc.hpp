@@ -381,6 +381,7 @@ int gmg_block_destroy(gmg_block_handle_t h)
   (void)hipSetDevice(h->eng.device);
   (void)hipStreamSynchronize(h->eng.stream);
   h->detach();                                            // GMG handles get their own stream back
+  h->eng.ns_clear();
   h->eng.free_all();
   for (auto &P : h->plan) {
     if (P.h_send) (void)hipHostFree(P.h_send);
@@ -562,6 +563,7 @@ int gmg_block_fgmres_solve(gmg_block_handle_t h, const double *b, double *x, int
     const double *db = h->eng.in_vec(b, n, memspace, h->st_b);
     double *dx = (memspace == GMG_MEM_DEVICE) ? x : h->st_x;
     if (memspace == GMG_MEM_HOST) h->eng.h2d(dx, x, n);
+    if (h->eng.ns.project_guess) h->eng.ns_project_guess(dx, n, false);   // NullspaceSolvers.jl:115-116
     ConvLog log;
     log.configure(maxiter, atol, rtol);
     KrylovOps ops = h->ops(use_precond != 0);
@@ -582,6 +584,7 @@ int gmg_block_cg_solve(gmg_block_handle_t h, const double *b, double *x, int mem
     const double *db = h->eng.in_vec(b, n, memspace, h->st_b);
     double *dx = (memspace == GMG_MEM_DEVICE) ? x : h->st_x;
     if (memspace == GMG_MEM_HOST) h->eng.h2d(dx, x, n);
+    if (h->eng.ns.project_guess) h->eng.ns_project_guess(dx, n, false);   // NullspaceSolvers.jl:115-116
     ConvLog log;
     log.configure(maxiter, atol, rtol);
     KrylovOps ops = h->ops(use_precond != 0);
@@ -602,6 +605,7 @@ int gmg_block_minres_solve(gmg_block_handle_t h, const double *b, double *x, int
     const double *db = h->eng.in_vec(b, n, memspace, h->st_b);
     double *dx = (memspace == GMG_MEM_DEVICE) ? x : h->st_x;
     if (memspace == GMG_MEM_HOST) h->eng.h2d(dx, x, n);
+    if (h->eng.ns.project_guess) h->eng.ns_project_guess(dx, n, false);   // NullspaceSolvers.jl:115-116
     ConvLog log;
     log.configure(maxiter, atol, rtol);
     KrylovOps ops = h->ops(use_precond != 0);
@@ -627,6 +631,7 @@ int gmg_block_gmres_solve(gmg_block_handle_t h, const double *b, double *x, int 
     const double *db = h->eng.in_vec(b, n, memspace, h->st_b);
     double *dx = (memspace == GMG_MEM_DEVICE) ? x : h->st_x;
     if (memspace == GMG_MEM_HOST) h->eng.h2d(dx, x, n);
+    if (h->eng.ns.project_guess) h->eng.ns_project_guess(dx, n, false);   // NullspaceSolvers.jl:115-116
     ConvLog log;
     log.configure(maxiter, atol, rtol);
     KrylovOps ops = h->ops(use_precond_right != 0);
@@ -648,6 +653,55 @@ int gmg_block_diag_log(gmg_block_handle_t h, int i, gmg_result *res)
     REQUIRE(!L->residuals.empty(), GMG_ERR_STATE, "this block solver keeps no convergence log");
     const size_t k = std::min<size_t>((size_t)L->num_iters, L->residuals.size() - 1);
     L->export_to(res, nullptr, 0, L->residuals[k]);
+  });
+}
+
+// ---- null space of the block system: the twins of gmg_nullspace_* on the block handle's engine (vectors of length N()) ----------
+#define GMG_BLOCK_NS(body) return guarded_b(h, [&] { REQUIRE(h, GMG_ERR_INVALID, "null handle"); ns_single_rank(h->eng); check_block_ready(h); body; })
+int gmg_block_nullspace_set(gmg_block_handle_t h, int64_t n, int k, const double *V, int64_t ld, int memspace)
+{
+  GMG_BLOCK_NS(nsapi_set(h->eng, h->N(), n, k, V, ld, memspace));
+}
+int gmg_block_nullspace_size(gmg_block_handle_t h, int *k, int64_t *n)
+{
+  return guarded_b(h, [&] {
+    REQUIRE(h && k && n, GMG_ERR_INVALID, "null argument");
+    *k = h->eng.ns.k; *n = h->eng.ns.n;
+  });
+}
+int gmg_block_nullspace_get(gmg_block_handle_t h, double *V_out, int64_t ld, int memspace)
+{
+  return guarded_b(h, [&] { REQUIRE(h, GMG_ERR_INVALID, "null handle"); nsapi_get(h->eng, V_out, ld, memspace); });
+}
+int gmg_block_nullspace_orthonormalize(gmg_block_handle_t h, int method) { GMG_BLOCK_NS(nsapi_orthonormalize(h->eng, method)); }
+int gmg_block_nullspace_project(gmg_block_handle_t h, double *v, double *p, double *alpha_out, int memspace, int subtract)
+{
+  GMG_BLOCK_NS(nsapi_project(h->eng, v, p, alpha_out, memspace, subtract));
+}
+int gmg_block_nullspace_make_orthogonal(gmg_block_handle_t h, double *v, double *alpha_out, int memspace)
+{
+  GMG_BLOCK_NS(nsapi_make_orthogonal(h->eng, v, alpha_out, memspace));
+}
+int gmg_block_nullspace_reconstruct(gmg_block_handle_t h, double *v, const double *alpha, int memspace)
+{
+  GMG_BLOCK_NS(nsapi_reconstruct(h->eng, v, alpha, memspace));
+}
+int gmg_block_nullspace_gram(gmg_block_handle_t h, double *G_out) { GMG_BLOCK_NS(nsapi_gram(h->eng, G_out)); }
+int gmg_block_nullspace_dots(gmg_block_handle_t h, const double *v, double *out_k, int memspace)
+{
+  GMG_BLOCK_NS(nsapi_dots(h->eng, v, out_k, memspace));
+}
+int gmg_block_nullspace_image_norms(gmg_block_handle_t h, double *out_k)
+{
+  GMG_BLOCK_NS(nsapi_image_norms(h->eng, out_k, [h](double *x, double *y) { h->sys_apply(x, y); }));
+}
+#undef GMG_BLOCK_NS
+int gmg_block_nullspace_project_guess(gmg_block_handle_t h, int on)
+{
+  return guarded_b(h, [&] {
+    REQUIRE(h, GMG_ERR_INVALID, "null handle");
+    if (on) ns_need(h->eng);
+    h->eng.ns.project_guess = on != 0;
   });
 }
 

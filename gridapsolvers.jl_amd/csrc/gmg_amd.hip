@@ -625,6 +625,10 @@ struct gmg_solver {
   ConvLog coarse_log;
   double coarse_last = 0.0;
   double *cc_w = nullptr, *cc_p = nullptr, *cc_z = nullptr, *cc_r = nullptr;   // CGSolvers.jl:42-48 on the coarsest level
+  // gmg_set_coarse_nullspace: the kernel K (n_L x coarse_k, column-major, packed) of a singular coarsest matrix; the dense-inverse
+  // solver then keeps the leading block of inv([A_L K; K' 0]) -- NullspaceSolver(LUSolver(), N; constrain_matrix = true)
+  std::vector<double> coarse_K;
+  int coarse_k = 0;
   double *h_cr = nullptr, *h_cx = nullptr;   // pinned staging of the host callback
   bool reduce_local = false;                 // reductions over a REPLICATED vector: no all-reduce across ranks
   int krylov_depth = 0;                      // nesting of cg_core calls (each level owns its scalar slots)
@@ -875,7 +879,7 @@ struct gmg_solver {
     for (void *p : allocs) (void)hipFree(p);
     allocs.clear();
     d_perr_dev = nullptr;
-    dev_bytes = 0;
+    dev_bytes = ns.bytes;                                    // the null space is not part of a setup: it stays
     for (auto &L : lev) {
       L.A = DevCSR(); L.P = DevCSR(); L.R = DevCSR(); L.G = DevCSR();
       L.dinv = L.x = L.dx = L.rcur = nullptr;
@@ -3756,6 +3760,257 @@ struct gmg_solver {
     return st_extra[i];
   }
 
+  // ---- null space of the handle's operator (SolverInterfaces/NullSpaces.jl; NullspaceSolvers.jl:109-120, the :projected mode) ------
+  // k vectors of length n in allocations of their own: they outlive gmg_setup / gmg_block_setup (free_all leaves them alone) and are
+  // counted by gmg_device_bytes.  Single rank only.  With option nullspace_fused (default 1, where fuse_reductions() holds) the dots
+  // of a projection are one pass (nullspace_dots_kernel), the combination and the subtraction another (nullspace_project_kernel),
+  // and the sequential forms chain nullspace_mgs_kernel; otherwise dot, axpy_kernel, axmy_dev_kernel and div_kernel.  Same bits.
+  struct NullSpaceDev {
+    int k = 0;
+    int64_t n = 0;
+    std::vector<double *> V;
+    const double **tab = nullptr;              // device table of V (nullspace_dots_kernel, nullspace_project_kernel, gmres_combine_kernel)
+    double *alpha = nullptr;                   // k coefficient slots
+    double *parts = nullptr;                   // kNullChunk rows of kRedBlocks partials + two rows for the nullspace_mgs_kernel chain
+    double *sv = nullptr, *sp = nullptr;       // staging of host callers / the projection when the caller wants none
+    std::vector<void *> allocs;
+    int64_t bytes = 0;
+    bool project_guess = false;                // gmg_nullspace_project_guess
+    std::vector<double> h_alpha;
+  } ns;
+  template <typename T>
+  T *ns_alloc(size_t count)
+  {
+    void *p = nullptr;
+    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T) + 64;
+    HIP_CHECK(hipMalloc(&p, bytes));
+    ns.allocs.push_back(p);
+    ns.bytes += (int64_t)bytes; dev_bytes += (int64_t)bytes;
+    return reinterpret_cast<T *>(p);
+  }
+  void ns_clear()
+  {
+    if (!ns.allocs.empty()) (void)hipStreamSynchronize(stream);
+    for (void *p : ns.allocs) (void)hipFree(p);
+    dev_bytes -= ns.bytes;
+    const bool pg = ns.project_guess;
+    ns = NullSpaceDev();
+    ns.project_guess = pg;
+  }
+  static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+  bool ns_fused() const { return opt_int("GMG_NULLSPACE_FUSED", 1) != 0 && fuse_reductions(); }
+  double *ns_ping() const { return ns.parts + (size_t)kNullChunk * kRedBlocks; }
+  double *ns_pong() const { return ns.parts + (size_t)(kNullChunk + 1) * kRedBlocks; }
+  void ns_set(int64_t n, int k, const double *Vin, int64_t ld, int memspace)
+  {
+    ns_clear();
+    if (k == 0) return;
+    try {
+      ns.k = k; ns.n = n;
+      for (int q = 0; q < k; ++q) {
+        double *w = ns_alloc<double>((size_t)n);
+        ns.V.push_back(w);
+        HIP_CHECK(hipMemcpy(w, Vin + (size_t)q * (size_t)ld, sizeof(double) * (size_t)n,
+                            memspace == GMG_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice));
+      }
+      ns.tab = ns_alloc<const double *>((size_t)k);
+      HIP_CHECK(hipMemcpy(ns.tab, ns.V.data(), sizeof(double *) * (size_t)k, hipMemcpyHostToDevice));
+      ns.alpha = ns_alloc<double>((size_t)k);
+      ns.parts = ns_alloc<double>((size_t)(kNullChunk + 2) * kRedBlocks);
+      ns.sv = ns_alloc<double>((size_t)n);
+      ns.sp = ns_alloc<double>((size_t)n);
+      ns.h_alpha.assign((size_t)k, 0.0);
+    } catch (...) {
+      ns_clear();
+      throw;
+    }
+  }
+  void ns_get(double *Vout, int64_t ld, int memspace)
+  {
+    HIP_CHECK(hipStreamSynchronize(stream));
+    for (int q = 0; q < ns.k; ++q)
+      HIP_CHECK(hipMemcpy(Vout + (size_t)q * (size_t)ld, ns.V[q], sizeof(double) * (size_t)ns.n,
+                          memspace == GMG_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+  }
+  void ns_fetch_alpha()
+  {
+    HIP_CHECK(hipMemcpyAsync(ns.h_alpha.data(), ns.alpha, sizeof(double) * (size_t)ns.k, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+  }
+  // rows 0 .. c-1 of ns.parts = first stages of dot(v, V[k0 + q]) -> the row length
+  int ns_dot_rows(const double *v, int k0, int c)
+  {
+    const int nb = dot_grid(ns.n);
+    hipLaunchKernelGGL(nullspace_dots_kernel, dim3(nb), dim3(kBlock), 0, stream, ns.n, v, ns.tab + k0, c, ns.parts, aligned16(v) ? 1 : 0);
+    HIP_CHECK(hipGetLastError());
+    return nb;
+  }
+  void ns_mgs_step(double *v, const double *wk, const double *wnext, int next, const double *hparts, int nh, double *aslot, double *pout)
+  {
+    const int vec = aligned16(v) && aligned16(wk) && (next != 1 || aligned16(wnext));
+    hipLaunchKernelGGL(nullspace_mgs_kernel, dim3(dot_grid(ns.n)), dim3(kBlock), 0, stream, ns.n, v, wk, wnext, next, hparts, nh, aslot, pout, vec);
+    HIP_CHECK(hipGetLastError());
+  }
+  // project!(p,N,v), NullSpaces.jl:107-116 (alpha_k = dot(v, w_k) ; p = sum_k alpha_k w_k from 0.0 in the order k = 1..K), and with
+  // `subtract` the x .-= w1 of NullspaceSolvers.jl:116 on the same vector.  Device pointers; p may be null.  alpha -> ns.h_alpha.
+  void ns_project(double *v, double *p, bool subtract, bool want_alpha)
+  {
+    const int64_t n = ns.n;
+    const int K = ns.k, grid = grid_for(n);
+    if (ns_fused()) {
+      const int nchunks = (K + kNullChunk - 1) / kNullChunk;
+      double *pp = (p || nchunks == 1) ? p : ns.sp;
+      const int vec = (!subtract || aligned16(v)) && (!pp || aligned16(pp));
+      for (int j = 0; j < nchunks; ++j) {
+        const int k0 = j * kNullChunk, c = std::min(kNullChunk, K - k0);
+        const int nb = ns_dot_rows(v, k0, c);
+        hipLaunchKernelGGL(nullspace_project_kernel, dim3(grid), dim3(kBlock), 0, stream, n, v, pp, ns.tab + k0, c, ns.parts, nb,
+                           ns.alpha + k0, j == 0 ? 1 : 0, (subtract && j == nchunks - 1) ? 1 : 0, vec);
+        HIP_CHECK(hipGetLastError());
+      }
+      if (want_alpha) ns_fetch_alpha();
+      return;
+    }
+    double *pp = p ? p : ns.sp;
+    zero(pp, n);                                             // :110
+    for (int q = 0; q < K; ++q) {
+      ns.h_alpha[(size_t)q] = dot(n, v, ns.V[q]);            // :112
+      hipLaunchKernelGGL(axpy_kernel, dim3(grid), dim3(256), 0, stream, n, ns.h_alpha[(size_t)q], ns.V[q], pp);   // :113
+      HIP_CHECK(hipGetLastError());
+    }
+    if (subtract) {
+      hipLaunchKernelGGL(axpy_kernel, dim3(grid), dim3(256), 0, stream, n, -1.0, pp, v);
+      HIP_CHECK(hipGetLastError());
+    }
+  }
+  // make_orthogonal!(N,v), NullSpaces.jl:118-126: alpha_k from the already updated v.  Fused: one dot_partial_kernel launch and K
+  // nullspace_mgs_kernel launches, each leaving the partials of the next dot.
+  void ns_make_orthogonal(double *v, bool want_alpha)
+  {
+    const int64_t n = ns.n;
+    const int K = ns.k;
+    if (ns_fused()) {
+      double *pin = ns_ping(), *pout = ns_pong();
+      int np = dot_partials(n, v, ns.V[0], pin);
+      for (int q = 0; q < K; ++q) {
+        const bool more = q + 1 < K;
+        ns_mgs_step(v, ns.V[q], more ? ns.V[q + 1] : nullptr, more ? 1 : 0, pin, np, ns.alpha + q, pout);
+        std::swap(pin, pout);
+        np = dot_grid(n);
+      }
+      if (want_alpha) ns_fetch_alpha();
+      return;
+    }
+    for (int q = 0; q < K; ++q) {
+      ns.h_alpha[(size_t)q] = dot(n, v, ns.V[q]);            // :122 (the scalar is also in d_scalars[0])
+      hipLaunchKernelGGL(axmy_dev_kernel, dim3(grid_for(n)), dim3(256), 0, stream, n, d_scalars, ns.V[q], v);   // :123
+      HIP_CHECK(hipGetLastError());
+    }
+  }
+  // reconstruct!(N,v,alpha), NullSpaces.jl:134-139: v .+= alpha[k] .* w in the order k = 1..K
+  void ns_reconstruct(double *v, const double *alpha)
+  {
+    const int64_t n = ns.n;
+    const int K = ns.k, grid = grid_for(n);
+    if (ns_fused()) {
+      HIP_CHECK(hipMemcpyAsync(ns.alpha, alpha, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, stream));
+      HIP_CHECK(hipStreamSynchronize(stream));               // (alpha is the caller's pageable array)
+      hipLaunchKernelGGL(gmres_combine_kernel, dim3(grid), dim3(kBlock), 0, stream, n, v, (const double *)v, ns.tab, ns.alpha, K, aligned16(v) ? 1 : 0);
+      HIP_CHECK(hipGetLastError());
+      return;
+    }
+    for (int q = 0; q < K; ++q) {
+      hipLaunchKernelGGL(axpy_kernel, dim3(grid), dim3(256), 0, stream, n, alpha[q], ns.V[q], v);
+      HIP_CHECK(hipGetLastError());
+    }
+  }
+  // dot(v, w_k) for every k (is_orthogonal(N,v), NullSpaces.jl:49-55) -> out[0 .. K)
+  void ns_dots(const double *v, double *out)
+  {
+    const int K = ns.k;
+    if (ns_fused()) {
+      for (int k0 = 0; k0 < K; k0 += kNullChunk) {
+        const int c = std::min(kNullChunk, K - k0);
+        const int nb = ns_dot_rows(v, k0, c);
+        hipLaunchKernelGGL(nullspace_sums_kernel, dim3(c), dim3(kBlock), 0, stream, nb, ns.parts, ns.alpha + k0, 0);
+        HIP_CHECK(hipGetLastError());
+      }
+      ns_fetch_alpha();
+      std::copy(ns.h_alpha.begin(), ns.h_alpha.end(), out);
+      return;
+    }
+    for (int q = 0; q < K; ++q) out[q] = dot(ns.n, v, ns.V[q]);
+  }
+  // gram_schmidt!(V) (method 0, NullSpaces.jl:78-88) / modified_gram_schmidt!(V) (method 1, :90-100), loop for loop
+  void ns_orthonormalize(int method)
+  {
+    const int64_t n = ns.n;
+    const int K = ns.k, grid = grid_for(n), nb = dot_grid(n);
+    const bool fuse = ns_fused();
+    auto normalize = [&](int j, double nrm) {
+      REQUIRE(nrm != 0.0, GMG_ERR_SINGULAR, "null-space vector " + std::to_string(j) + " of V has norm 0 in the orthonormalisation (linearly dependent or zero vector)");
+      hipLaunchKernelGGL(div_kernel, dim3(grid), dim3(256), 0, stream, n, nrm, ns.V[j]);
+      HIP_CHECK(hipGetLastError());
+    };
+    for (int j = 0; j < K; ++j) {
+      double *v = ns.V[j];
+      if (method == 0) {
+        double nrm;
+        if (fuse && j > 0) {
+          double *pin = ns_ping(), *pout = ns_pong();
+          int np = dot_partials(n, v, ns.V[0], pin);         // :82
+          for (int i = 0; i < j; ++i) {                      // :81-84 ; the last launch leaves the partials of norm(V[j])^2 (:85)
+            const bool more = i + 1 < j;
+            ns_mgs_step(v, ns.V[i], more ? ns.V[i + 1] : nullptr, more ? 1 : 2, pin, np, ns.alpha + i, pout);
+            std::swap(pin, pout);
+            np = nb;
+          }
+          finish_reduction(np, 0, true, pin, true);
+          nrm = fetch_scalar(0);
+        } else {
+          for (int i = 0; i < j; ++i) {
+            (void)dot(n, v, ns.V[i]);                        // :82
+            hipLaunchKernelGGL(axmy_dev_kernel, dim3(grid), dim3(256), 0, stream, n, d_scalars, ns.V[i], v);   // :83
+            HIP_CHECK(hipGetLastError());
+          }
+          nrm = norm(n, v);
+        }
+        normalize(j, nrm);                                   // :85
+      } else {
+        normalize(j, norm(n, v));                            // :93
+        if (fuse) {
+          for (int i0 = j + 1; i0 < K; i0 += kNullChunk) {   // :94-97: the dots of a chunk in one pass over V[j]
+            const int c = std::min(kNullChunk, K - i0);
+            (void)ns_dot_rows(v, i0, c);
+            for (int q = 0; q < c; ++q)
+              ns_mgs_step(ns.V[i0 + q], v, nullptr, 0, ns.parts + (size_t)q * nb, nb, ns.alpha + i0 + q, ns_pong());
+          }
+        } else {
+          for (int i = j + 1; i < K; ++i) {
+            (void)dot(n, v, ns.V[i]);                        // :95
+            hipLaunchKernelGGL(axmy_dev_kernel, dim3(grid), dim3(256), 0, stream, n, d_scalars, v, ns.V[i]);   // :96
+            HIP_CHECK(hipGetLastError());
+          }
+        }
+      }
+    }
+    HIP_CHECK(hipStreamSynchronize(stream));
+  }
+  // G[i * K + j] = dot(w_i, w_j): what is_orthonormal / is_orthogonal(N) compare (NullSpaces.jl:33-47)
+  void ns_gram(double *G)
+  {
+    const int K = ns.k;
+    for (int i = 0; i < K; ++i) ns_dots(ns.V[i], G + (size_t)i * K);
+  }
+  // NullspaceSolvers.jl:115-116 on the device copy of the initial guess of a Krylov entry
+  void ns_project_guess(double *dx, int64_t n, bool x0_zero)
+  {
+    if (ns.k == 0 || x0_zero) return;
+    REQUIRE(comm.nranks == 1, GMG_ERR_UNSUPPORTED, "the null-space projection is single-rank");
+    REQUIRE(n == ns.n, GMG_ERR_STATE, "the null space was set for vectors of another length than this solve's x");
+    ns_project(dx, nullptr, true, false);
+  }
+
   void read_tuning()
   {
     xcd_remap = opt_int("GMG_XCD_REMAP", 1);   // XCD-contiguous row ranges: each L2 sees 1/8 of the gathered vector (pattern kernels: -6 % per solve)
@@ -3919,6 +4174,7 @@ struct gmg_solver {
   void build_coarse();
   double *build_dense_inverse(const HostCSR &A, const std::string &what);
   double *build_coarse_device(const HostCSR &A, const std::string &what);
+  double *build_constrained_inverse(const HostCSR &A, const std::string &what);
 };
 
 // ----------------------------------------------------------------------------
@@ -5173,6 +5429,12 @@ struct BandLU {
     piv.assign(n, 0);
     for (int i = 0; i < n; ++i)
       for (int64_t k = A.ptr[i]; k < A.ptr[i + 1]; ++k) at(i, A.col[k]) += A.val[k];
+    // A pivot that is rounding noise against its column of A marks a singular matrix as surely as an exact zero: the last pivot
+    // of a pure-Neumann stiffness matrix comes out as ~1e-16 times its diagonal, not as 0.0, and its "inverse" would be garbage.
+    std::vector<double> cmax((size_t)n, 0.0);
+    for (int j = 0; j < n; ++j)
+      for (int i = std::max(0, j - ku); i <= std::min(n - 1, j + kl); ++i) cmax[(size_t)j] = std::max(cmax[(size_t)j], std::fabs(get(i, j)));
+    const double rtol = (double)n * 2.220446049250313e-16;
     int ju = 0;
     for (int j = 0; j < n; ++j) {
       const int km = std::min(kl, n - 1 - j);
@@ -5180,7 +5442,7 @@ struct BandLU {
       double best = std::fabs(get(j, j));
       for (int i = j + 1; i <= j + km; ++i)
         if (std::fabs(get(i, j)) > best) { best = std::fabs(get(i, j)); p = i; }
-      if (best == 0.0) return false;
+      if (best <= rtol * cmax[(size_t)j]) return false;
       piv[j] = p;
       ju = std::max(ju, std::min(p + ku, n - 1));
       ju = std::max(ju, j);
@@ -5220,7 +5482,10 @@ void gmg_solver::build_coarse()
   const int64_t n = lev[nlev - 1].n;
   REQUIRE(!(lev[nlev - 1].sA && coarse_eff == GMG_COARSE_DENSE_INVERSE), GMG_ERR_UNSUPPORTED,
           "the dense-inverse coarse solver needs the coarsest matrix whole (gmg_set_matrix), not streamed");
-  if (coarse_eff == GMG_COARSE_DENSE_INVERSE) d_Ainv = build_dense_inverse(lev[nlev - 1].hA, "coarsest-level matrix");
+  REQUIRE(coarse_k == 0 || coarse_eff == GMG_COARSE_DENSE_INVERSE, GMG_ERR_UNSUPPORTED,
+          "gmg_set_coarse_nullspace: the constrained coarsest solve exists for the dense-inverse coarse solver (LUSolver()) only");
+  if (coarse_eff == GMG_COARSE_DENSE_INVERSE && coarse_k > 0) d_Ainv = build_constrained_inverse(lev[nlev - 1].hA, "coarsest-level matrix");
+  else if (coarse_eff == GMG_COARSE_DENSE_INVERSE) d_Ainv = build_dense_inverse(lev[nlev - 1].hA, "coarsest-level matrix");
   else if (coarse_eff == GMG_COARSE_CG_JACOBI) { cc_w = dvec(n); cc_p = dvec(n); cc_z = dvec(n); cc_r = dvec(n); }
   else {
     REQUIRE(coarse_fn, GMG_ERR_STATE, "coarse-solver callback missing");
@@ -5265,6 +5530,47 @@ double *gmg_solver::build_dense_inverse(const HostCSR &A, const std::string &wha
       e[c] = 1.0;
       lu.solve(e.data());
       for (int i = 0; i < n; ++i) inv[(size_t)i * n + c] = e[i]; // row-major inverse
+    }
+  };
+  run_threads(nthreads, work);
+  double *d = upload(inv);
+  HIP_CHECK(hipStreamSynchronize(stream));
+  return d;
+}
+
+// NullspaceSolvers.jl:59-107 (:constrained) for LUSolver() on the coarsest level: mat = [A K; K' 0] (:66) is factorised by the host's
+// LU with partial pivoting (the zero block rules out a method without pivoting), and because the right-hand side's tail is zero
+// (:103) and lambda is dropped (:105), the solve is x = inv(mat)[1:n,1:n] * b: that block is the dense matrix dense_gemv_kernel applies.
+double *gmg_solver::build_constrained_inverse(const HostCSR &A, const std::string &what)
+{
+  const int n = (int)A.nrows, k = coarse_k, m = n + k;
+  REQUIRE((int64_t)coarse_K.size() == (int64_t)n * k, GMG_ERR_INVALID,
+          "gmg_set_coarse_nullspace: Kc was given for a coarsest level of another size than the one set up (" + std::to_string(n) + " dofs)");
+  REQUIRE(m <= opt_int("GMG_COARSE_HOST_MAX", 1500), GMG_ERR_UNSUPPORTED,
+          what + " with its null space has n_L + k = " + std::to_string(m) + " rows, more than coarse_host_max: the constrained inverse is built on the host; add multigrid levels");
+  HostCSR M;
+  M.nrows = M.ncols = m;
+  M.ptr.assign(1, 0);
+  for (int i = 0; i < n; ++i) {
+    for (int64_t e = A.ptr[i]; e < A.ptr[i + 1]; ++e) { M.col.push_back(A.col[e]); M.val.push_back(A.val[e]); }
+    for (int q = 0; q < k; ++q) { M.col.push_back(n + q); M.val.push_back(coarse_K[(size_t)q * n + i]); }
+    M.ptr.push_back((int64_t)M.col.size());
+  }
+  for (int q = 0; q < k; ++q) {
+    for (int i = 0; i < n; ++i) { M.col.push_back(i); M.val.push_back(coarse_K[(size_t)q * n + i]); }
+    M.ptr.push_back((int64_t)M.col.size());
+  }
+  BandLU lu;
+  REQUIRE(lu.factor(M), GMG_ERR_SINGULAR, what + " constrained by the given null space [A K; K' 0] is singular: Kc does not span the kernel of the matrix");
+  std::vector<double> inv((size_t)n * n);
+  const int nthreads = host_threads(std::max(1, n / 16));
+  auto work = [&](int t) {
+    std::vector<double> e(m);
+    for (int c = t; c < n; c += nthreads) {
+      std::fill(e.begin(), e.end(), 0.0);
+      e[c] = 1.0;
+      lu.solve(e.data());
+      for (int i = 0; i < n; ++i) inv[(size_t)i * n + c] = e[i];
     }
   };
   run_threads(nthreads, work);
@@ -5864,6 +6170,110 @@ void check_ready(gmg_handle_t h)
 }
 } // namespace
 
+// ---- null space of a handle: one implementation behind the gmg_nullspace_* and gmg_block_nullspace_* entry points --------------
+// `S` is the GMG handle or the engine of the block handle, n_handle the length of its Krylov vectors.
+namespace {
+void ns_single_rank(const gmg_solver &S)
+{
+  REQUIRE(S.comm.nranks == 1, GMG_ERR_UNSUPPORTED, "null spaces are single-GPU: this handle's communicator has more than one rank (real or loopback)");
+}
+void ns_need(const gmg_solver &S)
+{
+  ns_single_rank(S);
+  REQUIRE(S.ns.k > 0, GMG_ERR_STATE, "no null space set on this handle (gmg_nullspace_set)");
+}
+void nsapi_set(gmg_solver &S, int64_t n_handle, int64_t n, int k, const double *V, int64_t ld, int memspace)
+{
+  REQUIRE(k >= 0, GMG_ERR_INVALID, "k < 0");
+  REQUIRE(memspace == GMG_MEM_HOST || memspace == GMG_MEM_DEVICE, GMG_ERR_INVALID, "memspace must be GMG_MEM_HOST or GMG_MEM_DEVICE");
+  if (k > 0) {
+    REQUIRE(n == n_handle, GMG_ERR_INVALID, "n = " + std::to_string(n) + " does not match the handle's vectors (" + std::to_string(n_handle) + ")");
+    REQUIRE(V, GMG_ERR_INVALID, "null V with k > 0");
+    REQUIRE(ld >= n, GMG_ERR_INVALID, "ld < n");
+  }
+  S.ns_set(n, k, V, ld, memspace);
+}
+void nsapi_get(gmg_solver &S, double *V_out, int64_t ld, int memspace)
+{
+  ns_need(S);
+  REQUIRE(V_out, GMG_ERR_INVALID, "null V_out");
+  REQUIRE(ld >= S.ns.n, GMG_ERR_INVALID, "ld < n");
+  S.ns_get(V_out, ld, memspace);
+}
+void nsapi_orthonormalize(gmg_solver &S, int method)
+{
+  ns_need(S);
+  REQUIRE(method == 0 || method == 1, GMG_ERR_INVALID, "method must be 0 (:gram_schmidt) or 1 (:modified_gram_schmidt)");
+  S.ns_orthonormalize(method);
+}
+void ns_alpha_out(gmg_solver &S, double *alpha_out)
+{
+  if (alpha_out) std::copy(S.ns.h_alpha.begin(), S.ns.h_alpha.end(), alpha_out);
+}
+void nsapi_project(gmg_solver &S, double *v, double *p, double *alpha_out, int memspace, int subtract)
+{
+  ns_need(S);
+  REQUIRE(v, GMG_ERR_INVALID, "null v");
+  REQUIRE(p || subtract || alpha_out, GMG_ERR_INVALID, "nothing asked for: p and alpha_out null and subtract = 0");
+  const int64_t n = S.ns.n;
+  const bool host = memspace == GMG_MEM_HOST;
+  double *dv = v, *dp = p;
+  if (host) {
+    S.h2d(S.ns.sv, v, n);
+    dv = S.ns.sv;
+    dp = (p || !subtract) ? S.ns.sp : nullptr;
+  }
+  S.ns_project(dv, dp, subtract != 0, alpha_out != nullptr);
+  if (host && p) S.out_vec(p, dp, n, memspace);
+  if (host && subtract) S.out_vec(v, dv, n, memspace);
+  HIP_CHECK(hipStreamSynchronize(S.stream));
+  ns_alpha_out(S, alpha_out);
+}
+void nsapi_make_orthogonal(gmg_solver &S, double *v, double *alpha_out, int memspace)
+{
+  ns_need(S);
+  REQUIRE(v, GMG_ERR_INVALID, "null v");
+  const int64_t n = S.ns.n;
+  double *dv = v;
+  if (memspace == GMG_MEM_HOST) { S.h2d(S.ns.sv, v, n); dv = S.ns.sv; }
+  S.ns_make_orthogonal(dv, alpha_out != nullptr);
+  S.out_vec(v, dv, n, memspace);
+  ns_alpha_out(S, alpha_out);
+}
+void nsapi_reconstruct(gmg_solver &S, double *v, const double *alpha, int memspace)
+{
+  ns_need(S);
+  REQUIRE(v && alpha, GMG_ERR_INVALID, "null v or alpha");
+  const int64_t n = S.ns.n;
+  double *dv = v;
+  if (memspace == GMG_MEM_HOST) { S.h2d(S.ns.sv, v, n); dv = S.ns.sv; }
+  S.ns_reconstruct(dv, alpha);
+  S.out_vec(v, dv, n, memspace);
+}
+void nsapi_gram(gmg_solver &S, double *G_out)
+{
+  ns_need(S);
+  REQUIRE(G_out, GMG_ERR_INVALID, "null G_out");
+  S.ns_gram(G_out);
+}
+void nsapi_dots(gmg_solver &S, const double *v, double *out_k, int memspace)
+{
+  ns_need(S);
+  REQUIRE(v && out_k, GMG_ERR_INVALID, "null v or out_k");
+  S.ns_dots(S.in_vec(v, S.ns.n, memspace, S.ns.sv), out_k);
+}
+void nsapi_image_norms(gmg_solver &S, double *out_k, const std::function<void(double *, double *)> &apply)
+{
+  ns_need(S);
+  REQUIRE(out_k, GMG_ERR_INVALID, "null out_k");
+  for (int q = 0; q < S.ns.k; ++q) {                         // mul!(v,A,w) ; norm(v), NullSpaces.jl:60-62
+    S.copy(S.ns.sv, S.ns.V[q], S.ns.n);
+    apply(S.ns.sv, S.ns.sp);
+    out_k[q] = S.norm(S.ns.n, S.ns.sp);
+  }
+}
+} // namespace
+
 extern "C" {
 
 int gmg_version(void) { return 100; }
@@ -5904,6 +6314,7 @@ int gmg_destroy(gmg_handle_t h)
   if (h->attached_to) block_forget(h->attached_to, h);
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
+  h->ns_clear();
   h->free_all();
   for (auto &L : h->lev) {
     if (L.halo.h_send) (void)hipHostFree(L.halo.h_send);
@@ -6394,7 +6805,7 @@ const OptionKey kOptionKeys[] = {
   {"GMG_PAT_WIDE_ROUNDS", false}, {"GMG_PERSIST", false}, {"GMG_PERSIST_FENCED", false}, {"GMG_PERSIST_MAX_SLICES", false},
   {"GMG_PERSIST_SHARED", false}, {"GMG_PROF_STRIDE", true}, {"GMG_REFRESH", true}, {"GMG_SELL", false}, {"GMG_SELL_BLOCK", false},
   {"GMG_SELL_DEFER", false}, {"GMG_SELL_MAXPAD", false}, {"GMG_SELL_UN", false}, {"GMG_SETUP_TIMING", true}, {"GMG_VDICT", false},
-  {"GMG_XCD_REMAP", false}, {"GMG_XCD_REMAP_BIG", false}, {"GMG_X0_ZERO", true}, {"GMG_HOST_POLL", true}, {"GMG_HOST_CHUNK_BYTES", true}, {"GMG_PAT_FMA", false}, {"GMG_PAT_R2", false}, {"GMG_RED_FUSED", false}, {"GMG_GMRES_FUSED", true}, {"GMG_PAT_R2MV", false}, {"GMG_PAT_R2_OCC", false}, {"GMG_PAT_PAIR_P", false}, {"GMG_PAT_R2MV_DOT", false}, {"GMG_PERSIST_WPB", false}, {"GMG_HOST_TIMELINE", true}, {"GMG_PAT_R2MV_MIN", false}, {"GMG_PAT_BCAST", false}, {"GMG_PAT_R2_WGS", false}, {"GMG_PAT_ZWALK", false}, {"GMG_PAT_ZWALK_T", false}, {"GMG_PAT_ZWALK_ROWS", false}, {"GMG_PAT_ZWALK_MV", false}, {"GMG_PAT_ZWALK_WIDE", false}, {"GMG_PAT_ZWALK_WIDE_ROWS", false}, {"GMG_PAT_FUSE2", false}, {"GMG_PAT_FUSE2_W", false}, {"GMG_PAT_FUSE2_T", false}, {"GMG_PAT_FUSE2_ROWS", false}, {"GMG_PAT_FUSE2_BOX", false}, {"GMG_PAT_BOX", false}, {"GMG_PAT_WIDE_GRID", false}, {"GMG_PAT_BOX_T", false}, {"GMG_PAT_BOX_MIN_ROWS", false}, {"GMG_PAT_BOX_MAX_ROWS", false},
+  {"GMG_XCD_REMAP", false}, {"GMG_XCD_REMAP_BIG", false}, {"GMG_X0_ZERO", true}, {"GMG_HOST_POLL", true}, {"GMG_HOST_CHUNK_BYTES", true}, {"GMG_PAT_FMA", false}, {"GMG_PAT_R2", false}, {"GMG_RED_FUSED", false}, {"GMG_GMRES_FUSED", true}, {"GMG_NULLSPACE_FUSED", true}, {"GMG_PAT_R2MV", false}, {"GMG_PAT_R2_OCC", false}, {"GMG_PAT_PAIR_P", false}, {"GMG_PAT_R2MV_DOT", false}, {"GMG_PERSIST_WPB", false}, {"GMG_HOST_TIMELINE", true}, {"GMG_PAT_R2MV_MIN", false}, {"GMG_PAT_BCAST", false}, {"GMG_PAT_R2_WGS", false}, {"GMG_PAT_ZWALK", false}, {"GMG_PAT_ZWALK_T", false}, {"GMG_PAT_ZWALK_ROWS", false}, {"GMG_PAT_ZWALK_MV", false}, {"GMG_PAT_ZWALK_WIDE", false}, {"GMG_PAT_ZWALK_WIDE_ROWS", false}, {"GMG_PAT_FUSE2", false}, {"GMG_PAT_FUSE2_W", false}, {"GMG_PAT_FUSE2_T", false}, {"GMG_PAT_FUSE2_ROWS", false}, {"GMG_PAT_FUSE2_BOX", false}, {"GMG_PAT_BOX", false}, {"GMG_PAT_WIDE_GRID", false}, {"GMG_PAT_BOX_T", false}, {"GMG_PAT_BOX_MIN_ROWS", false}, {"GMG_PAT_BOX_MAX_ROWS", false},
   {"GMG_PERSIST_FORCE_TIMEOUT", true},
 };
 // "pat_tile", "PAT_TILE" and "GMG_PAT_TILE" name the same option
@@ -6588,6 +6999,7 @@ int gmg_cg_solve(gmg_handle_t h, const double *b, double *x, int memspace, int m
       const bool dist = S.comm.nranks > 1;
       double *dx = dist ? S.cg_x : ((memspace == GMG_MEM_DEVICE) ? x : S.st_x);
       S.in_guess(dx, x, n, memspace);                        // x = initial guess on entry (CGSolvers.jl:79)
+      if (S.ns.project_guess) S.ns_project_guess(dx, n, S.opt_int("GMG_X0_ZERO", 0) != 0);   // NullspaceSolvers.jl:115-116
       ConvLog log;
       log.configure(maxiter, atol, rtol);
       KrylovOps ops = S.level0_ops(use_precond);
@@ -6625,6 +7037,7 @@ int gmg_fgmres_solve_pl(gmg_handle_t h, const double *b, double *x, int memspace
       const int64_t nv = L0.nvec;
       double *dx = dist ? S.cg_x : ((memspace == GMG_MEM_DEVICE) ? x : S.st_x);
       S.in_guess(dx, x, n, memspace);                        // x = initial guess on entry (CGSolvers.jl:79)
+      if (S.ns.project_guess) S.ns_project_guess(dx, n, S.opt_int("GMG_X0_ZERO", 0) != 0);   // NullspaceSolvers.jl:115-116
       ConvLog log;
       log.configure(maxiter, atol, rtol);
       KrylovOps ops = S.level0_ops(use_precond);
@@ -6655,6 +7068,7 @@ int gmg_minres_solve(gmg_handle_t h, const double *b, double *x, int memspace, i
       const bool dist = S.comm.nranks > 1;
       double *dx = dist ? S.cg_x : ((memspace == GMG_MEM_DEVICE) ? x : S.st_x);
       S.in_guess(dx, x, n, memspace);                        // x = initial guess on entry (MINRESSolvers.jl:90)
+      if (S.ns.project_guess) S.ns_project_guess(dx, n, S.opt_int("GMG_X0_ZERO", 0) != 0);   // NullspaceSolvers.jl:115-116
       ConvLog log;
       log.configure(maxiter, atol, rtol);
       KrylovOps ops = S.level0_ops(use_precond);
@@ -6690,6 +7104,7 @@ int gmg_gmres_solve(gmg_handle_t h, const double *b, double *x, int memspace, in
       const bool dist = S.comm.nranks > 1;
       double *dx = dist ? S.cg_x : ((memspace == GMG_MEM_DEVICE) ? x : S.st_x);
       S.in_guess(dx, x, n, memspace);                        // x = initial guess on entry (GMRESSolvers.jl:143)
+      if (S.ns.project_guess) S.ns_project_guess(dx, n, S.opt_int("GMG_X0_ZERO", 0) != 0);   // NullspaceSolvers.jl:115-116
       ConvLog log;
       log.configure(maxiter, atol, rtol);
       KrylovOps ops = S.level0_ops(use_precond_right);
@@ -6718,6 +7133,7 @@ int gmg_richardson_solve(gmg_handle_t h, const double *b, double *x, int memspac
       const bool dist = S.comm.nranks > 1;
       double *dx = dist ? S.cg_x : ((memspace == GMG_MEM_DEVICE) ? x : S.st_x);
       S.in_guess(dx, x, n, memspace);                        // x = initial guess on entry (CGSolvers.jl:79)
+      if (S.ns.project_guess) S.ns_project_guess(dx, n, S.opt_int("GMG_X0_ZERO", 0) != 0);   // NullspaceSolvers.jl:115-116
       double *z = S.cg_z, *r = S.cg_r;
       ConvLog log;
       log.configure(maxiter, atol, rtol);
@@ -6847,6 +7263,91 @@ int gmg_dot(gmg_handle_t h, int64_t n, const double *a, const double *b, int mem
     const double *da = h->in_vec(a, n, memspace, h->scratch_vec(0, h->lev[0].nvec));
     const double *db = (a == b) ? da : h->in_vec(b, n, memspace, h->scratch_vec(1, h->lev[0].nvec));
     *out = h->dot(n, da, db);
+  });
+}
+
+// ---- null space (SolverInterfaces/NullSpaces.jl, LinearSolvers/NullspaceSolvers.jl) ---------------------------------------------
+int gmg_nullspace_set(gmg_handle_t h, int64_t n, int k, const double *V, int64_t ld, int memspace)
+{
+  return guarded(h, [&] {
+    REQUIRE(h, GMG_ERR_INVALID, "null handle");
+    ns_single_rank(*h);
+    check_ready(h);
+    nsapi_set(*h, h->user_n(), n, k, V, ld, memspace);
+  });
+}
+int gmg_nullspace_size(gmg_handle_t h, int *k, int64_t *n)
+{
+  return guarded(h, [&] {
+    REQUIRE(h && k && n, GMG_ERR_INVALID, "null argument");
+    *k = h->ns.k; *n = h->ns.n;
+  });
+}
+int gmg_nullspace_get(gmg_handle_t h, double *V_out, int64_t ld, int memspace)
+{
+  return guarded(h, [&] { REQUIRE(h, GMG_ERR_INVALID, "null handle"); nsapi_get(*h, V_out, ld, memspace); });
+}
+int gmg_nullspace_orthonormalize(gmg_handle_t h, int method)
+{
+  return guarded(h, [&] { REQUIRE(h, GMG_ERR_INVALID, "null handle"); ns_single_rank(*h); check_ready(h); nsapi_orthonormalize(*h, method); });
+}
+int gmg_nullspace_project(gmg_handle_t h, double *v, double *p, double *alpha_out, int memspace, int subtract)
+{
+  return guarded(h, [&] { REQUIRE(h, GMG_ERR_INVALID, "null handle"); ns_single_rank(*h); check_ready(h); nsapi_project(*h, v, p, alpha_out, memspace, subtract); });
+}
+int gmg_nullspace_make_orthogonal(gmg_handle_t h, double *v, double *alpha_out, int memspace)
+{
+  return guarded(h, [&] { REQUIRE(h, GMG_ERR_INVALID, "null handle"); ns_single_rank(*h); check_ready(h); nsapi_make_orthogonal(*h, v, alpha_out, memspace); });
+}
+int gmg_nullspace_reconstruct(gmg_handle_t h, double *v, const double *alpha, int memspace)
+{
+  return guarded(h, [&] { REQUIRE(h, GMG_ERR_INVALID, "null handle"); ns_single_rank(*h); check_ready(h); nsapi_reconstruct(*h, v, alpha, memspace); });
+}
+int gmg_nullspace_gram(gmg_handle_t h, double *G_out)
+{
+  return guarded(h, [&] { REQUIRE(h, GMG_ERR_INVALID, "null handle"); ns_single_rank(*h); check_ready(h); nsapi_gram(*h, G_out); });
+}
+int gmg_nullspace_dots(gmg_handle_t h, const double *v, double *out_k, int memspace)
+{
+  return guarded(h, [&] { REQUIRE(h, GMG_ERR_INVALID, "null handle"); ns_single_rank(*h); check_ready(h); nsapi_dots(*h, v, out_k, memspace); });
+}
+int gmg_nullspace_image_norms(gmg_handle_t h, double *out_k)
+{
+  return guarded(h, [&] {
+    REQUIRE(h, GMG_ERR_INVALID, "null handle");
+    ns_single_rank(*h);
+    check_ready(h);
+    nsapi_image_norms(*h, out_k, [h](double *x, double *y) { h->apply_A_set(h->kl(), x, y); });
+  });
+}
+int gmg_nullspace_project_guess(gmg_handle_t h, int on)
+{
+  return guarded(h, [&] {
+    REQUIRE(h, GMG_ERR_INVALID, "null handle");
+    if (on) ns_need(*h);
+    h->ns.project_guess = on != 0;
+  });
+}
+int gmg_set_coarse_nullspace(gmg_handle_t h, int k, const double *Kc, int64_t ld)
+{
+  return guarded(h, [&] {
+    REQUIRE(h, GMG_ERR_INVALID, "null handle");
+    ns_single_rank(*h);
+    REQUIRE(k >= 0, GMG_ERR_INVALID, "k < 0");
+    if (k == 0) {
+      if (h->coarse_k) h->touch();
+      h->coarse_k = 0; h->coarse_K.clear();
+      return;
+    }
+    REQUIRE(Kc, GMG_ERR_INVALID, "null Kc with k > 0");
+    const Level &L = h->lev[h->nlev - 1];
+    REQUIRE(L.hasA, GMG_ERR_STATE, "gmg_set_coarse_nullspace: set the coarsest matrix first (gmg_set_matrix)");
+    const int64_t n = L.hA.nrows;
+    REQUIRE(ld >= n, GMG_ERR_INVALID, "ld is smaller than the coarsest level (" + std::to_string(n) + " dofs)");
+    h->coarse_K.resize((size_t)n * (size_t)k);
+    for (int q = 0; q < k; ++q) std::copy(Kc + (size_t)q * (size_t)ld, Kc + (size_t)q * (size_t)ld + n, h->coarse_K.begin() + (size_t)q * (size_t)n);
+    h->coarse_k = k;
+    h->touch();
   });
 }
 

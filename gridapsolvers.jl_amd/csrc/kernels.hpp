@@ -4027,6 +4027,202 @@ __global__ __launch_bounds__(kBlock) void gmres_combine_kernel(int64_t n, double
   }
 }
 
+// ---------------------------------------------------------------------------
+// K13: null spaces (SolverInterfaces/NullSpaces.jl:78-139, LinearSolvers/NullspaceSolvers.jl:109-120).  As in K12 each kernel performs
+// the floating-point operations of the launches it replaces, in their order, so nullspace_fused = 1 and 0 give the same bits.
+// ---------------------------------------------------------------------------
+constexpr int kNullChunk = 8;                                // basis vectors one launch of the two kernels below takes
+
+// partials[q * gridDim.x + blockIdx.x], q < c <= kNullChunk: the first stage of dot(v, tab[q]) in ONE pass over v -- row q holds the
+// numbers dot_partial_kernel(n, v, tab[q], ., vec) writes (same grid: dot_grid(n); same per-lane order; vec != 0: v and every tab[q]
+// 16-byte aligned, the double2 order with the odd tail on thread 0 of workgroup 0), c + 1 streams instead of 2 c.
+__global__ __launch_bounds__(kBlock) void nullspace_dots_kernel(int64_t n, const double *__restrict__ v,
+                                                                const double *const *__restrict__ tab, int c,
+                                                                double *__restrict__ partials, int vec)
+{
+  __shared__ double sh[kNullChunk][4];
+  const double *w[kNullChunk];
+  double s[kNullChunk];
+#pragma unroll
+  for (int q = 0; q < kNullChunk; ++q) { w[q] = q < c ? tab[q] : nullptr; s[q] = 0.0; }
+  if (vec) {
+    const int64_t n2 = n >> 1;
+    const double2 *v2 = reinterpret_cast<const double2 *>(v);
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n2; i += (int64_t)gridDim.x * kBlock) {
+      const double2 u = v2[i];
+#pragma unroll
+      for (int q = 0; q < kNullChunk; ++q)
+        if (q < c) {
+          const double2 t = reinterpret_cast<const double2 *>(w[q])[i];
+          s[q] += u.x * t.x;
+          s[q] += u.y * t.y;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1)) {
+#pragma unroll
+      for (int q = 0; q < kNullChunk; ++q)
+        if (q < c) s[q] += v[n - 1] * w[q][n - 1];
+    }
+  } else {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+      const double u = v[i];
+#pragma unroll
+      for (int q = 0; q < kNullChunk; ++q)
+        if (q < c) s[q] += u * w[q][i];
+    }
+  }
+  const int wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < kNullChunk; ++q)
+    if (q < c) {
+      const double t = wave_sum(s[q]);
+      if ((threadIdx.x & 63) == 0) sh[q][wv] = t;
+    }
+  __syncthreads();
+  if (threadIdx.x < c) {                                     // block_sum's tree, one lane per row
+    const int q = threadIdx.x;
+    partials[(size_t)q * gridDim.x + blockIdx.x] = (sh[q][0] + sh[q][1]) + (sh[q][2] + sh[q][3]);
+  }
+}
+
+// out[row] = (take_sqrt ? sqrt : id)(sum of partials[row * nparts .. + nparts)): reduce_final_kernel, one workgroup per row
+__global__ __launch_bounds__(kBlock) void nullspace_sums_kernel(int nparts, const double *__restrict__ partials,
+                                                                double *__restrict__ out, int take_sqrt)
+{
+  __shared__ double sh[4];
+  const double *row = partials + (size_t)blockIdx.x * nparts;
+  double s = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += kBlock) s += row[i];
+  const double t = block_sum(s, sh);
+  if (threadIdx.x == 0) out[blockIdx.x] = take_sqrt ? sqrt(t) : t;
+}
+
+// project!(p,N,v) (NullSpaces.jl:107-116) for the chunk tab[0 .. c), c <= kNullChunk, whose first stages nullspace_dots_kernel left in
+// `parts` (c rows of nparts): every workgroup sums each row as reduce_final_kernel does (sum_partials_all), workgroup 0 stores
+// alpha[q]; then a = (first ? 0.0 : p[i]) ; a = a + alpha[q] * tab[q][i] for q = 0 .. c-1 (product and sum rounded separately: the
+// fill!(p,0.0) ; p .+= alpha[k] .* w of :110-113, axpy_kernel's operations) ; p[i] = a when p != nullptr ; with subtract != 0 also
+// x[i] = x[i] - a (NullspaceSolvers.jl:116, x .-= w1).  More than kNullChunk vectors: one launch per chunk, first = 0 and a p to
+// carry the sum from the second on, subtract on the last only.  vec != 0: x (if written), p (if given) and every tab[q] 16-byte aligned.
+__global__ __launch_bounds__(kBlock) void nullspace_project_kernel(int64_t n, double *x, double *p,
+                                                                   const double *const *__restrict__ tab, int c,
+                                                                   const double *__restrict__ parts, int nparts,
+                                                                   double *__restrict__ alpha, int first, int subtract, int vec)
+{
+  __shared__ double sh[5];
+  const double *w[kNullChunk];
+  double al[kNullChunk];
+#pragma unroll
+  for (int q = 0; q < kNullChunk; ++q) {
+    w[q] = q < c ? tab[q] : nullptr;
+    al[q] = 0.0;
+    if (q < c) {
+      al[q] = sum_partials_all(parts + (size_t)q * nparts, nparts, sh);
+      if (blockIdx.x == 0 && threadIdx.x == 0) alpha[q] = al[q];
+    }
+  }
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  if (vec) {
+    const int64_t n2 = n >> 1;
+    double2 *x2 = reinterpret_cast<double2 *>(x);
+    double2 *p2 = reinterpret_cast<double2 *>(p);
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n2; i += stride) {
+      double2 a = first ? make_double2(0.0, 0.0) : p2[i];
+#pragma unroll
+      for (int g = 0; g < kNullChunk; g += 4) {
+        if (g + 4 <= c) {                                    // four basis loads in flight, added in order (gmres_combine_kernel)
+          const double2 v0 = reinterpret_cast<const double2 *>(w[g])[i], v1 = reinterpret_cast<const double2 *>(w[g + 1])[i];
+          const double2 v2 = reinterpret_cast<const double2 *>(w[g + 2])[i], v3 = reinterpret_cast<const double2 *>(w[g + 3])[i];
+          a.x = a.x + al[g] * v0.x; a.y = a.y + al[g] * v0.y;
+          a.x = a.x + al[g + 1] * v1.x; a.y = a.y + al[g + 1] * v1.y;
+          a.x = a.x + al[g + 2] * v2.x; a.y = a.y + al[g + 2] * v2.y;
+          a.x = a.x + al[g + 3] * v3.x; a.y = a.y + al[g + 3] * v3.y;
+        } else {
+#pragma unroll
+          for (int q = g; q < g + 4; ++q)
+            if (q < c) {
+              const double2 t = reinterpret_cast<const double2 *>(w[q])[i];
+              a.x = a.x + al[q] * t.x; a.y = a.y + al[q] * t.y;
+            }
+        }
+      }
+      if (p) p2[i] = a;
+      if (subtract) {
+        double2 u = x2[i];
+        u.x = u.x - a.x; u.y = u.y - a.y;
+        x2[i] = u;
+      }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1)) {
+      double a = first ? 0.0 : p[n - 1];
+#pragma unroll
+      for (int q = 0; q < kNullChunk; ++q)
+        if (q < c) a = a + al[q] * w[q][n - 1];
+      if (p) p[n - 1] = a;
+      if (subtract) x[n - 1] = x[n - 1] - a;
+    }
+  } else {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+      double a = first ? 0.0 : p[i];
+#pragma unroll
+      for (int q = 0; q < kNullChunk; ++q)
+        if (q < c) a = a + al[q] * w[q][i];
+      if (p) p[i] = a;
+      if (subtract) x[i] = x[i] - a;
+    }
+  }
+}
+
+// Step k of make_orthogonal!(N,v) (NullSpaces.jl:118-126; the inner loops of gram_schmidt! / modified_gram_schmidt!, :78-100): the
+// dataflow of gmres_mgs_kernel on a vector the caller owns, so with an element-wise form for a v that is not 16-byte aligned.
+//   alpha_k = sum of the partials of dot(v, w_k) the previous launch left in `hparts` (workgroup 0 stores it into *aslot)
+//   v .= v .- alpha_k .* w_k                                  (product and difference rounded separately: axmy_dev_kernel)
+//   next == 1: partials[blockIdx.x] = first stage of dot(v, wnext) ; next == 2: of dot(v, v) ; next == 0: none (the last step)
+// The partials are dot_partial_kernel's (launch with dot_grid(n)); vec != 0: v, wk and wnext 16-byte aligned.  `partials` and `hparts`
+// must be different arrays.
+__global__ __launch_bounds__(kBlock) void nullspace_mgs_kernel(int64_t n, double *__restrict__ v, const double *__restrict__ wk,
+                                                               const double *__restrict__ wnext, int next,
+                                                               const double *__restrict__ hparts, int nhparts,
+                                                               double *__restrict__ aslot, double *__restrict__ partials, int vec)
+{
+  __shared__ double sh[5];
+  const double h = sum_partials_all(hparts, nhparts, sh);
+  if (blockIdx.x == 0 && threadIdx.x == 0) aslot[0] = h;
+  __syncthreads();                                           // sh is reused below
+  double s = 0.0;
+  if (vec) {
+    const int64_t n2 = n >> 1;
+    double2 *v2 = reinterpret_cast<double2 *>(v);
+    const double2 *k2 = reinterpret_cast<const double2 *>(wk);
+    const double2 *x2 = reinterpret_cast<const double2 *>(wnext);
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n2; i += (int64_t)gridDim.x * kBlock) {
+      double2 u = v2[i];
+      const double2 t = k2[i];
+      u.x = u.x - h * t.x;
+      u.y = u.y - h * t.y;
+      v2[i] = u;
+      if (next) {
+        const double2 q = next == 2 ? u : x2[i];
+        s += u.x * q.x;
+        s += u.y * q.y;
+      }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1)) {
+      const double u = v[n - 1] - h * wk[n - 1];
+      v[n - 1] = u;
+      if (next) s += u * (next == 2 ? u : wnext[n - 1]);
+    }
+  } else {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+      const double u = v[i] - h * wk[i];
+      v[i] = u;
+      if (next) s += u * (next == 2 ? u : wnext[i]);
+    }
+  }
+  if (!next) return;
+  const double t = block_sum(s, sh);
+  if (threadIdx.x == 0) partials[blockIdx.x] = t;
+}
+
 // dx = omega*(dinv.*r) ; optionally x += dx     (unfused Jacobi apply, gmg_precond_apply)
 __global__ void jacobi_apply_kernel(int64_t n, const double *__restrict__ dinv, const double *__restrict__ r,
                                     double *__restrict__ dx)

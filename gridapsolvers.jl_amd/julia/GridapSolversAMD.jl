@@ -39,6 +39,7 @@ export HipRichardsonLinearSolver, HipBlockTriangularSolver, HipBlockDiagonalSolv
 export block_minres_solve!
 export HipGMRESSolver, HipBlockGMRESSolver
 export HipSchurComplementSolver
+export HipNullspaceSolver, device_project!, device_make_orthogonal!, device_reconstruct!, device_is_orthonormal
 
 const libgmgamd = get(ENV, "LIBGMGAMD", joinpath(@__DIR__, "..", "libgmgamd.so"))
 
@@ -563,6 +564,108 @@ function Gridap.Algebra.solve!(x::Vector{Float64}, ns::HipKrylovNumericalSetup{<
 end
 
 # RichardsonLinearSolver(omega,maxiter;Pl=gmg) on the device: RichardsonLinearSolvers.jl:79-106
+# ---------------------------------------------------------------------------------
+# NullspaceSolver(solver, N; constrain_matrix=false) on the device: LinearSolvers/NullspaceSolvers.jl:30-75,109-120.  `solver` is one
+# of the Hip Krylov solvers above; the numerical setup uploads N.V to the handle (gmg_nullspace_set), orthonormalises it there with
+# Gram-Schmidt (make_orthonormal!(N), :68 -- N.V receives the result, as the reference mutates N) and switches the projection of the
+# initial guess on: every later solve! is x .-= sum_k dot(x,w_k) w_k on the device, then the inner solve (:115-117).
+# The :constrained mode needs a direct solver for [A K; K' 0]: on the device that exists on the coarsest level of a GMG only
+# (gmg_set_coarse_nullspace before gmg_setup).
+struct HipNullspaceSolver{A,B} <: Gridap.Algebra.LinearSolver
+  solver    :: A
+  nullspace :: B          # GridapSolvers.SolverInterfaces.NullSpace, or any object with a field V :: Vector{Vector{Float64}}
+end
+struct HipNullspaceSymbolicSetup{A} <: Gridap.Algebra.SymbolicSetup
+  solver :: A
+end
+Gridap.Algebra.symbolic_setup(s::HipNullspaceSolver, ::AbstractMatrix) = HipNullspaceSymbolicSetup(s)
+mutable struct HipNullspaceNumericalSetup{A,B} <: Gridap.Algebra.NumericalSetup
+  solver :: A
+  ns     :: B
+end
+
+function _nullspace_upload!(h::Ptr{Cvoid}, V::Vector{Vector{Float64}})
+  n, k = length(first(V)), length(V)
+  @assert all(length(v) == n for v in V)                                     # NullSpaces.jl:7
+  W = reduce(hcat, V)                                                        # n x k, column-major: vector q at W + (q-1)*n
+  GC.@preserve W begin
+    check(h, ccall((:gmg_nullspace_set, libgmgamd), Cint, (Ptr{Cvoid},Int64,Cint,Ptr{Float64},Int64,Cint), h, n, k, W, n, GMG_MEM_HOST))
+  end
+  return nothing
+end
+function _nullspace_download!(h::Ptr{Cvoid}, V::Vector{Vector{Float64}})
+  n, k = length(first(V)), length(V)
+  W = zeros(n, k)
+  GC.@preserve W begin
+    check(h, ccall((:gmg_nullspace_get, libgmgamd), Cint, (Ptr{Cvoid},Ptr{Float64},Int64,Cint), h, W, n, GMG_MEM_HOST))
+  end
+  for q in 1:k
+    V[q] .= view(W, :, q)
+  end
+  return V
+end
+
+function Gridap.Algebra.numerical_setup(ss::HipNullspaceSymbolicSetup, A::AbstractMatrix)
+  s  = ss.solver
+  ns = numerical_setup(symbolic_setup(s.solver, A), A)                       # :72
+  h  = ns.P_ns.handle
+  V  = s.nullspace.V
+  @assert length(first(V)) == size(A,2)                                      # :63
+  _nullspace_upload!(h, V)
+  check(h, ccall((:gmg_nullspace_orthonormalize, libgmgamd), Cint, (Ptr{Cvoid},Cint), h, 0))   # :68, :gram_schmidt
+  _nullspace_download!(h, V)
+  check(h, ccall((:gmg_nullspace_project_guess, libgmgamd), Cint, (Ptr{Cvoid},Cint), h, 1))
+  return HipNullspaceNumericalSetup(s, ns)
+end
+function Gridap.Algebra.numerical_setup!(ns::HipNullspaceNumericalSetup, A::AbstractMatrix)   # :77-90 (the null space stays on the handle)
+  numerical_setup!(ns.ns, A)
+  return ns
+end
+Gridap.Algebra.solve!(x::Vector{Float64}, ns::HipNullspaceNumericalSetup, b::Vector{Float64}) = solve!(x, ns.ns, b)   # :109-120
+
+# NullSpaces.jl:102-139 on the handle of a numerical setup that carries a null space (host vectors)
+_ns_handle(ns::HipNullspaceNumericalSetup) = ns.ns.P_ns.handle
+function _ns_size(h::Ptr{Cvoid})
+  k, n = Ref{Cint}(0), Ref{Int64}(0)
+  check(h, ccall((:gmg_nullspace_size, libgmgamd), Cint, (Ptr{Cvoid},Ref{Cint},Ref{Int64}), h, k, n))
+  return Int(k[]), Int(n[])
+end
+function device_project!(p::Vector{Float64}, ns::HipNullspaceNumericalSetup, v::Vector{Float64})   # project!(p,N,v) -> (p, alpha)
+  h = _ns_handle(ns)
+  alpha = zeros(_ns_size(h)[1])
+  GC.@preserve p v alpha begin
+    check(h, ccall((:gmg_nullspace_project, libgmgamd), Cint, (Ptr{Cvoid},Ptr{Float64},Ptr{Float64},Ptr{Float64},Cint,Cint),
+                   h, v, p, alpha, GMG_MEM_HOST, 0))
+  end
+  return p, alpha
+end
+function device_make_orthogonal!(ns::HipNullspaceNumericalSetup, v::Vector{Float64})              # make_orthogonal!(N,v) -> (v, alpha)
+  h = _ns_handle(ns)
+  alpha = zeros(_ns_size(h)[1])
+  GC.@preserve v alpha begin
+    check(h, ccall((:gmg_nullspace_make_orthogonal, libgmgamd), Cint, (Ptr{Cvoid},Ptr{Float64},Ptr{Float64},Cint), h, v, alpha, GMG_MEM_HOST))
+  end
+  return v, alpha
+end
+function device_reconstruct!(ns::HipNullspaceNumericalSetup, v::Vector{Float64}, alpha::Vector{Float64})   # reconstruct!(N,v,alpha)
+  h = _ns_handle(ns)
+  @assert length(alpha) == _ns_size(h)[1]
+  GC.@preserve v alpha begin
+    check(h, ccall((:gmg_nullspace_reconstruct, libgmgamd), Cint, (Ptr{Cvoid},Ptr{Float64},Ptr{Float64},Cint), h, v, alpha, GMG_MEM_HOST))
+  end
+  return v
+end
+function device_is_orthonormal(ns::HipNullspaceNumericalSetup; tol = 1.e-12)                      # NullSpaces.jl:33-47
+  h = _ns_handle(ns)
+  k = _ns_size(h)[1]
+  G = zeros(k, k)
+  GC.@preserve G begin
+    check(h, ccall((:gmg_nullspace_gram, libgmgamd), Cint, (Ptr{Cvoid},Ptr{Float64}), h, G))
+  end
+  all(abs(sqrt(G[i,i]) - 1.0) < tol for i in 1:k) || return false
+  return all(abs(G[i,j]) < tol for i in 1:k for j in i+1:k)
+end
+
 struct HipRichardsonLinearSolver{A} <: Gridap.Algebra.LinearSolver
   omega :: Float64
   Pl    :: A

@@ -30,7 +30,7 @@ __all__ = [
     "CSR", "poisson_matrix", "prolongation", "dirichlet_lift_rhs", "nodal_values",
     "l2_error_sq", "vertex_star_patches", "coarse_cell_interior_patches", "build_hierarchy", "random_rhs", "level_sizes",
     "poisson_matrix_varcoef", "smooth_kappa", "StreamedCSR", "poisson_matrix_stream", "prolongation_stream",
-    "restriction_stream",
+    "restriction_stream", "neumann_matrix", "neumann_prolongation", "neumann_hierarchy", "neumann_rhs",
 ]
 
 
@@ -739,3 +739,68 @@ def build_hierarchy(ncells_fine, nlevels, order=1, lengths=None, kappa=None, str
     Ps = [prolongation(cells[l + 1], order) for l in range(nlevels - 1)]
     Rs = [P.transpose() for P in Ps]
     return dict(mats=mats, prolongations=Ps, restrictions=Rs, ncells=cells, order=order)
+
+
+# --------------------------------------------------------------------------
+# pure-Neumann problems: every node is a dof, the constants span the kernel
+# (test/LinearSolvers/NullspaceTests.jl:39-58: FESpace(model, reffe) without Dirichlet tags)
+# --------------------------------------------------------------------------
+def _axis_tables_all(n, order, dim_active, length=1.0):
+    """`_axis_tables` with every node kept"""
+    if not dim_active:
+        return 1, np.zeros((1, 1), dtype=np.int64), np.zeros((1, 1)), np.ones((1, 1))
+    K, M, S = _assemble_1d(n, order, length)
+    nn = order * n + 1
+    cols, (kv, mv) = _padded_rows(S, [K, M], np.arange(nn), np.arange(nn, dtype=np.int64))
+    return nn, cols, kv, mv
+
+
+def neumann_matrix(ncells, order=1, lengths=None) -> CSR:
+    """Q`order` stiffness matrix of -Laplace on all nodes (natural boundary conditions): symmetric positive semi-definite, A 1 = 0."""
+    nc, d = _dims(ncells)
+    Ls = _lengths(lengths, d)
+    tabs = [_axis_tables_all(nc[k], order, k < d, Ls[k]) for k in range(3)]
+    ncols, cols, K, M = ([t[i] for t in tabs] for i in range(4))
+    terms = [(K[0], M[1], M[2]), (M[0], K[1], M[2])]
+    if d == 3:
+        terms.append((M[0], M[1], K[2]))
+    return _tensor_csr(cols, terms, ncols)
+
+
+def neumann_prolongation(ncells_coarse, order=1) -> CSR:
+    """P : all coarse nodes -> all fine nodes (fine mesh = coarse refined x2).  Rows sum to 1: P 1_H = 1_h."""
+    nc, d = _dims(ncells_coarse)
+    cols, vals, ncols = [], [], []
+    for k in range(3):
+        if k >= d:
+            cols.append(np.zeros((1, 1), dtype=np.int64)); vals.append(np.ones((1, 1))); ncols.append(1)
+            continue
+        P, S = _interp_1d(nc[k], order)
+        nh, nH = P.shape
+        c, (v,) = _padded_rows(S, [P], np.arange(nh), np.arange(nH, dtype=np.int64))
+        cols.append(c); vals.append(v); ncols.append(nH)
+    return _tensor_csr(cols, [tuple(vals)], ncols)
+
+
+def neumann_hierarchy(ncells, nlevels, order=1):
+    """`build_hierarchy` for the pure-Neumann problem: matrices on all nodes, full-node prolongations, R = P^T.
+    Every level matrix is singular (kernel: the constants); `ncells` needs >= 1 coarsest cell per direction."""
+    nc = tuple(int(c) for c in ncells)
+    cells = [tuple(c // (2 ** l) for c in nc) for l in range(nlevels)]
+    for l in range(nlevels):
+        if any(cells[l][k] * 2 ** l != nc[k] or cells[l][k] < 1 for k in range(len(nc))):
+            raise ValueError("ncells must be divisible by 2^(nlevels-1)")
+    mats = [neumann_matrix(c, order) for c in cells]
+    Ps = [neumann_prolongation(cells[l + 1], order) for l in range(nlevels - 1)]
+    Rs = [P.transpose() for P in Ps]
+    return dict(mats=mats, prolongations=Ps, restrictions=Rs, ncells=cells, order=order)
+
+
+def neumann_rhs(ncells, order=1, u=None):
+    """b = A u_h for the nodal interpolant u_h of u (default u = x1 x2, the u_exact of NullspaceTests.jl:50: harmonic, so b is the
+    boundary term of :53): a right-hand side in the range of the Neumann matrix, hence orthogonal to the constants."""
+    nc, d = _dims(ncells)
+    if u is None:
+        u = lambda X, Y, Z: X * Y
+    X, Y, Z = _node_coords(nc, order, d)
+    return np.ascontiguousarray(neumann_matrix(ncells, order).matvec(u(X, Y, Z).reshape(-1).astype(np.float64)))

@@ -19,6 +19,7 @@ julia/GridapSolversAMD.jl.
     BlockDiagonalSolver(blocks,solvers)   BlockSolvers/BlockDiagonalSolvers.jl:20-45     BlockDiagonalSolver
     BlockTriangularSolver(blocks,solvers,coeffs,half)  BlockTriangularSolvers.jl:55-85    BlockTriangularSolver
     SchurComplementSolver(A,B,C,S)  SchurComplementSolvers.jl:11-26 SchurComplementSolver (A, S = (solver, matrix) pairs)
+    NullSpace(V) / NullspaceSolver(solver,N;constrain_matrix)  SolverInterfaces/NullSpaces.jl, NullspaceSolvers.jl:30-43   same names (f! = f_)
     LinearSystemBlock / MatrixBlock BlockSolvers/BlockSolverInterfaces.jl            same names
     symbolic_setup / numerical_setup / numerical_setup! / solve!    same names (solve_ = solve!)
     ConvergenceLog                  SolverInterfaces/ConvergenceLogs.jl:42   ConvergenceLog
@@ -39,6 +40,8 @@ __all__ = [
     "JacobiLinearSolver", "RichardsonSmoother", "PatchSolver", "BlockJacobiSolver", "LUSolver",
     "GMGLinearSolver", "CGSolver", "FGMRESSolver", "MINRESSolver", "GMRESSolver", "ConvergenceLog", "PatchProlongationOperator",
     "RichardsonLinearSolver", "BlockDiagonalSolver", "BlockTriangularSolver", "SchurComplementSolver", "LinearSystemBlock", "MatrixBlock", "LinearSolverFromSmoother",
+    "NullSpace", "NullspaceSolver", "is_orthonormal", "is_orthogonal", "make_orthonormal_", "gram_schmidt_", "modified_gram_schmidt_",
+    "project", "project_", "make_orthogonal_", "reconstruct", "reconstruct_",
     "symbolic_setup", "numerical_setup", "numerical_setup_", "solve_", "mul_",
     "SOLVER_CONVERGED_ATOL", "SOLVER_CONVERGED_RTOL", "SOLVER_DIVERGED_MAXITER", "SOLVER_DIVERGED_BREAKDOWN",
 ]
@@ -175,7 +178,15 @@ class GMGLinearSolver:
             raise ValueError("cycle_type must be 'v_cycle', 'w_cycle' or 'f_cycle'")
         # coarsest_solver: LUSolver() (default, GMGLinearSolvers.jl:54), CGSolver(JacobiLinearSolver();...) on the device, or any
         # host-side solver wrapped in HostCallbackSolver (the analogue of passing PETSc / UMFPACK objects in Julia)
-        if coarsest_solver is not None and not isinstance(coarsest_solver, (LUSolver, HostCallbackSolver)):
+        if isinstance(coarsest_solver, NullspaceSolver):
+            # NullspaceSolver(LUSolver(), N_coarse): the :constrained mode (NullspaceSolvers.jl:59-107) inside the dense coarsest solve
+            if not (coarsest_solver.constrain_matrix and isinstance(coarsest_solver.solver, LUSolver)):
+                raise NotImplementedError("coarsest_solver: NullspaceSolver(LUSolver(), N_coarse) with constrain_matrix=True "
+                                          "(an iterative coarsest solver needs no constraint: CGSolver(JacobiLinearSolver()))")
+            if coarsest_solver.nullspace.size()[1] != int(smatrices[-1].shape[0]):
+                raise ValueError(f"coarsest_solver: the null space has vectors of length {coarsest_solver.nullspace.size()[1]}, "
+                                 f"the coarsest matrix {int(smatrices[-1].shape[0])} rows")
+        elif coarsest_solver is not None and not isinstance(coarsest_solver, (LUSolver, HostCallbackSolver)):
             if not (isinstance(coarsest_solver, CGSolver) and isinstance(coarsest_solver.Pl, JacobiLinearSolver)
                     and not coarsest_solver.flexible):
                 raise NotImplementedError("coarsest_solver on the device: LUSolver(), CGSolver(JacobiLinearSolver()) or HostCallbackSolver(fn)")
@@ -576,6 +587,9 @@ class GMGNumericalSetup:
                     return 1
             self._coarse_cb = abi.COARSE_SOLVE_FN(_cb)
             abi.check(h, lib.gmg_set_coarse_solver(h, abi.COARSE_HOST_CALLBACK, 0, 0.0, 0.0, C.cast(self._coarse_cb, C.c_void_p), None))
+        elif isinstance(cs, NullspaceSolver):
+            Kc = np.ascontiguousarray(cs.nullspace.matrix_representation().T)      # vector q at Kc + q*n_L
+            abi.check(h, lib.gmg_set_coarse_nullspace(h, Kc.shape[0], C.c_void_p(Kc.ctypes.data), Kc.shape[1]))
         abi.check(h, lib.gmg_setup(h))
         self.n = int(mats[0].shape[0])
         self.sizes = [int(A.shape[0]) for A in mats]
@@ -944,6 +958,280 @@ class _KrylovNumericalSetup:
         self.P_ns.close()
 
 
+# ----------------------------------------------------------------------------
+# null spaces (SolverInterfaces/NullSpaces.jl, LinearSolvers/NullspaceSolvers.jl)
+# ----------------------------------------------------------------------------
+class NullSpace:
+    """struct NullSpace (NullSpaces.jl:1-31): `V` is a list of k vectors of equal length n.  NullSpace(list of vectors),
+    NullSpace(n x k array) (the columns; what matrix_representation returns), NullSpace(vector) (:21).  The vectors are host copies;
+    the algebra below runs on the device, on the copy `bind(ns)` uploads to the handle of a numerical setup."""
+
+    def __init__(self, V):
+        if isinstance(V, np.ndarray) and V.ndim == 2:
+            vecs = [V[:, q] for q in range(V.shape[1])]
+        elif isinstance(V, np.ndarray) and V.ndim == 1:
+            vecs = [V]                                                           # :21
+        else:
+            vecs = list(V)
+            if vecs and np.isscalar(vecs[0]):
+                vecs = [vecs]
+        if not vecs:
+            raise ValueError("NullSpace: at least one vector")
+        self.V = [np.array(v, dtype=np.float64).reshape(-1) for v in vecs]
+        n = self.V[0].size
+        if not all(v.size == n for v in self.V):                                 # @assert :7
+            raise ValueError("NullSpace: all vectors must have the same length")
+        self._ns = None
+
+    @classmethod
+    def from_matrix(cls, A):
+        """NullSpace(A::Matrix) (:23-26): the columns of LinearAlgebra.nullspace(A) -- the right singular vectors whose singular value
+        is <= min(size(A)) * eps * sigma_max.  On the host (setup only)."""
+        A = np.asarray(A, dtype=np.float64)
+        if A.ndim != 2:
+            raise ValueError("NullSpace.from_matrix: a dense matrix is expected")
+        _u, sv, vt = np.linalg.svd(A, full_matrices=True)
+        tol = min(A.shape) * np.finfo(np.float64).eps * (sv[0] if sv.size else 0.0)
+        r = int(np.sum(sv > tol))
+        if r == A.shape[1]:
+            raise ValueError("NullSpace.from_matrix: the matrix has a trivial null space")
+        return cls([vt[i].copy() for i in range(r, A.shape[1])])
+
+    def size(self, i=None):
+        """Base.size(N) = (k, n) (:13-14)"""
+        sz = (len(self.V), self.V[0].size)
+        return sz if i is None else sz[i]
+
+    def merge(self, other):
+        """Base.merge(a, b) (:15)"""
+        return NullSpace([v.copy() for v in self.V] + [v.copy() for v in other.V])
+
+    def matrix_representation(self):
+        """stack(N.V) (:17-19): n x k"""
+        return np.stack(self.V, axis=1)
+
+    # -- the device copy
+    def bind(self, ns):
+        """Upload the vectors to the handle behind `ns` (a GMG, block, Krylov or NullspaceSolver numerical setup); the algebra functions
+        then run there.  Bind again after changing N.V on the host."""
+        tgt = _ns_target(ns)
+        k, n = self.size()
+        if n != tgt.n:
+            raise ValueError(f"NullSpace.bind: vectors of length {n}, the numerical setup has {tgt.n}")
+        Vp = np.ascontiguousarray(np.stack(self.V, axis=0))
+        _ns_call(tgt, "set", n, k, C.c_void_p(Vp.ctypes.data), n, abi.MEM_HOST)
+        self._ns = tgt
+        return self
+
+    def unbind(self):
+        """Remove the device copy (gmg_nullspace_set with k = 0: its storage is freed)."""
+        if self._ns is not None and getattr(self._ns, "h", None):
+            _ns_call(self._ns, "set", 0, 0, None, 0, abi.MEM_HOST)
+        self._ns = None
+        return self
+
+    def gram(self):
+        """G[i, j] = dot(w_i, w_j) on the device: what is_orthonormal / is_orthogonal(N) compare"""
+        k = self.size(0)
+        G = np.zeros((k, k))
+        _ns_call(self._bound(), "gram", C.c_void_p(G.ctypes.data))
+        return G
+
+    def dots(self, v):
+        """[dot(v, w_k) for w_k in N.V] on the device: what is_orthogonal(N, v) compares"""
+        k, n = self.size()
+        out = np.zeros(k)
+        pv, ms, _k = _vec(v, n)                                                  # @assert NullSpaces.jl:50
+        _ns_call(self._bound(), "dots", pv, C.c_void_p(out.ctypes.data), ms)
+        return out
+
+    def _bound(self):
+        if self._ns is None or not getattr(self._ns, "h", None):
+            raise RuntimeError("this NullSpace is not bound to a numerical setup: call N.bind(ns) first (the algebra runs on the device)")
+        return self._ns
+
+    def _download(self):
+        k, n = self.size()
+        Vp = np.zeros((k, n))
+        _ns_call(self._bound(), "get", C.c_void_p(Vp.ctypes.data), n, abi.MEM_HOST)
+        for q in range(k):
+            self.V[q][:] = Vp[q]
+
+
+def _ns_target(ns):
+    """the numerical setup that owns the native handle"""
+    while not isinstance(ns, (GMGNumericalSetup, BlockNumericalSetup)):
+        if isinstance(ns, NullspaceNumericalSetup):
+            ns = ns.ns
+        elif isinstance(ns, _KrylovNumericalSetup):
+            ns = ns.P_ns
+        else:
+            raise TypeError(f"a null space lives on a GMG, block or Krylov numerical setup, not {type(ns).__name__}")
+    return ns
+
+
+def _ns_call(tgt, name, *args):
+    if isinstance(tgt, BlockNumericalSetup):
+        return abi.check_block(tgt.h, getattr(tgt._lib, "gmg_block_nullspace_" + name)(tgt.h, *args))
+    return abi.check(tgt.h, getattr(tgt._lib, "gmg_nullspace_" + name)(tgt.h, *args))
+
+
+def is_orthogonal(N, other=None, tol=1.0e-12):
+    """is_orthogonal(N) (NullSpaces.jl:40-47), is_orthogonal(N, v) (:49-55), is_orthogonal(N, A) (:57-65) with A given as
+    (ns, A): the operator of the numerical setup N is bound to."""
+    tgt = N._bound()
+    k, n = N.size()
+    if other is None:
+        G = N.gram()
+        return all(abs(G[i, j]) < tol for i in range(k) for j in range(i + 1, k))
+    if isinstance(other, tuple):
+        ns, A = other
+        if _ns_target(ns) is not tgt:
+            raise ValueError("is_orthogonal(N, (ns, A)): N is bound to another numerical setup")
+        if A is not None and hasattr(A, "shape") and int(A.shape[1]) != n:       # @assert :58
+            raise ValueError("is_orthogonal: size(A,2) != size(N,2)")
+        out = np.zeros(k)
+        _ns_call(tgt, "image_norms", C.c_void_p(out.ctypes.data))
+    else:
+        out = N.dots(other)
+    return all(abs(a) < tol for a in out)
+
+
+def is_orthonormal(N, tol=1.0e-12):
+    """is_orthonormal(N) (NullSpaces.jl:33-38)"""
+    k = N.size(0)
+    G = N.gram()
+    if not all(abs(np.sqrt(G[i, i]) - 1.0) < tol for i in range(k)):
+        return False
+    return all(abs(G[i, j]) < tol for i in range(k) for j in range(i + 1, k))
+
+
+_ORTHO_METHODS = {"gram_schmidt": 0, "modified_gram_schmidt": 1}
+
+
+def make_orthonormal_(N, method="gram_schmidt"):
+    """make_orthonormal!(N; method) (NullSpaces.jl:67-76) on the device; N.V receives the orthonormal vectors."""
+    if method not in _ORTHO_METHODS:
+        raise ValueError(f"Unknown method: {method}")                            # :73
+    _ns_call(N._bound(), "orthonormalize", _ORTHO_METHODS[method])
+    N._download()
+    return N
+
+
+def gram_schmidt_(N):
+    """gram_schmidt!(N.V) (NullSpaces.jl:78-88) -> N.V"""
+    return make_orthonormal_(N, "gram_schmidt").V
+
+
+def modified_gram_schmidt_(N):
+    """modified_gram_schmidt!(N.V) (NullSpaces.jl:90-100) -> N.V"""
+    return make_orthonormal_(N, "modified_gram_schmidt").V
+
+
+def _like(v):
+    if _is_device(v):
+        import torch
+        return torch.empty_like(v)
+    return np.zeros(np.asarray(v).size)
+
+
+def project_(p, N, v, subtract=False):
+    """project!(p, N, v) (NullSpaces.jl:107-116) -> (p, alpha).  subtract=True also performs v .-= p in the same pass
+    (NullspaceSolvers.jl:116); p may then be None."""
+    tgt = N._bound()
+    k, n = N.size()
+    pv, ms, _kv = _vec(v, n, writable=bool(subtract))
+    pp = None
+    if p is not None:
+        pp, ms2, _kp = _vec(p, n, writable=True)
+        if ms != ms2:
+            raise TypeError("p and v must live in the same memory space")
+    alpha = np.zeros(k)
+    _ns_call(tgt, "project", pv, pp, C.c_void_p(alpha.ctypes.data), ms, 1 if subtract else 0)
+    return p, alpha
+
+
+def project(N, v):
+    """project(N, v) (NullSpaces.jl:102-105) -> (p, alpha)"""
+    return project_(_like(v), N, v)
+
+
+def make_orthogonal_(N, v):
+    """make_orthogonal!(N, v) (NullSpaces.jl:118-126) -> (v, alpha)"""
+    tgt = N._bound()
+    k, n = N.size()
+    pv, ms, _kv = _vec(v, n, writable=True)
+    alpha = np.zeros(k)
+    _ns_call(tgt, "make_orthogonal", pv, C.c_void_p(alpha.ctypes.data), ms)
+    return v, alpha
+
+
+def reconstruct_(N, v, alpha):
+    """reconstruct!(N, v, alpha) (NullSpaces.jl:134-139) -> v"""
+    tgt = N._bound()
+    k, n = N.size()
+    pv, ms, _kv = _vec(v, n, writable=True)
+    a = np.ascontiguousarray(alpha, dtype=np.float64)
+    if a.size != k:
+        raise ValueError(f"reconstruct!: {a.size} coefficients for {k} vectors")
+    _ns_call(tgt, "reconstruct", pv, C.c_void_p(a.ctypes.data), ms)
+    return v
+
+
+def reconstruct(N, v, alpha):
+    """reconstruct(N, v, alpha) (NullSpaces.jl:128-132) -> a new vector"""
+    w = v.clone() if _is_device(v) else np.array(v, dtype=np.float64)
+    return reconstruct_(N, w, alpha)
+
+
+_KRYLOV_SOLVERS = (CGSolver, FGMRESSolver, MINRESSolver, GMRESSolver, RichardsonLinearSolver)
+
+
+class NullspaceSolver:
+    """NullspaceSolver(solver, nullspace; constrain_matrix=true) -- NullspaceSolvers.jl:30-43.
+    constrain_matrix=False (:projected, :109-120): `solver` is any of the device Krylov solvers, on a GMG or a block handle; the
+    numerical setup orthonormalises `nullspace` (Gram-Schmidt, :68 -- nullspace.V receives the result) and every solve starts from the
+    initial guess with its kernel component removed.
+    constrain_matrix=True (:constrained, :59-107): the augmented matrix needs a direct solver, and the device has one only on the
+    coarsest level of a GMG: accepted as GMGLinearSolver(..., coarsest_solver=NullspaceSolver(LUSolver(), N_coarse))."""
+
+    def __init__(self, solver, nullspace, constrain_matrix=True):
+        if not isinstance(nullspace, NullSpace):
+            raise TypeError("NullspaceSolver: nullspace must be a NullSpace")
+        if not isinstance(solver, _KRYLOV_SOLVERS + (LUSolver,)):
+            raise TypeError("NullspaceSolver: solver must be a Krylov solver of this package or LUSolver()")
+        self.solver, self.nullspace, self.constrain_matrix = solver, nullspace, bool(constrain_matrix)
+
+
+class NullspaceSymbolicSetup:
+    """NullspaceSolverSS (NullspaceSolvers.jl:45-51)"""
+
+    def __init__(self, solver):
+        self.solver = solver
+
+
+class NullspaceNumericalSetup:
+    """NullspaceSolverNS{:projected} (NullspaceSolvers.jl:53-75): the inner solver's numerical setup, the null space on its handle."""
+
+    def __init__(self, solver, A, device_id=None):
+        self.solver = solver
+        N = solver.nullspace
+        self.ns = numerical_setup(symbolic_setup(solver.solver, A), A, device_id)
+        self.n = self.ns.n
+        try:
+            if N.size(1) != self.n:                                              # @assert :63
+                raise ValueError(f"NullspaceSolver: null-space vectors of length {N.size(1)}, the matrix has {self.n} rows")
+            N.bind(self.ns)
+            make_orthonormal_(N)                                                 # :68
+            _ns_call(N._bound(), "project_guess", 1)
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        self.ns.close()
+
+
 def symbolic_setup(solver, A=None):
     """Gridap.Algebra.symbolic_setup(solver, A)."""
     if isinstance(solver, GMGLinearSolver):
@@ -952,6 +1240,14 @@ def symbolic_setup(solver, A=None):
         return _KrylovSymbolicSetup(solver)
     if isinstance(solver, _BLOCK_SOLVERS):
         return BlockSymbolicSetup(solver)
+    if isinstance(solver, NullspaceSolver):
+        if solver.constrain_matrix:
+            raise NotImplementedError("NullspaceSolver(constrain_matrix=True) needs a direct solver for [A K; K' 0] and the device has no "
+                                      "top-level direct solver: pass it as GMGLinearSolver(..., coarsest_solver=NullspaceSolver(LUSolver(), "
+                                      "N_coarse)), or use the projected mode, NullspaceSolver(krylov_solver, N, constrain_matrix=False)")
+        if not isinstance(solver.solver, _KRYLOV_SOLVERS):
+            raise NotImplementedError("NullspaceSolver(constrain_matrix=False) wraps a Krylov solver (CG, FGMRES, MINRES, GMRES, Richardson)")
+        return NullspaceSymbolicSetup(solver)
     raise TypeError(f"no symbolic_setup for {type(solver).__name__}")
 
 
@@ -963,6 +1259,8 @@ def numerical_setup(ss, A=None, device_id=None):
         return _KrylovNumericalSetup(ss.solver, A, device_id)
     if isinstance(ss, BlockSymbolicSetup):
         return BlockNumericalSetup(ss.solver, A, device_id)
+    if isinstance(ss, NullspaceSymbolicSetup):
+        return NullspaceNumericalSetup(ss.solver, A, device_id)
     raise TypeError(f"no numerical_setup for {type(ss).__name__}")
 
 
@@ -973,11 +1271,16 @@ def numerical_setup_(ns, A, smatrices=None):
     if isinstance(ns, _KrylovNumericalSetup):
         ns.P_ns.update(A, smatrices)
         return ns
+    if isinstance(ns, NullspaceNumericalSetup):                # NullspaceSolvers.jl:77-90: forwarded; the null space stays on the handle
+        numerical_setup_(ns.ns, A, smatrices)
+        return ns
     raise TypeError(f"no numerical_setup! for {type(ns).__name__}")
 
 
 def solve_(x, ns, b):
     """Gridap.Algebra.solve!(x, ns, b): in place on x, returns x."""
+    if isinstance(ns, NullspaceNumericalSetup):                # NullspaceSolvers.jl:109-120: the handle projects the initial guess
+        return solve_(x, ns.ns, b)
     if isinstance(ns, GMGNumericalSetup):
         log = ns.solver.log
         pb, ms, _kb = _vec(b, ns.n)

@@ -241,6 +241,10 @@ GMG_API int gmg_set_options(gmg_handle_t h, int mode, int cycle, int maxiter, do
  *                    previous dot's partials, subtracts the projection and accumulates the next dot's partials in one pass -- and
  *                    gmres_normalize_kernel, the solution update as one gmres_combine_kernel; 0: a dot, a reduce and an axmy launch
  *                    per coefficient and an axpy per basis vector.  Same bits either way)
+ *                    nullspace_fused* (1: where red_fused applies, the dots of a null-space projection are one pass over v for up to
+ *                    8 basis vectors, nullspace_dots_kernel, the combination and the subtraction from x another,
+ *                    nullspace_project_kernel, and make_orthogonal! / Gram-Schmidt chain nullspace_mgs_kernel; 0: a dot per
+ *                    vector, axpy_kernel / axmy_dev_kernel per term.  Same bits either way)
  *   one-launch pass  persist (1) persist_fenced (0) persist_max_slices (0 = one workgroup per CU) persist_shared (0)
  *                    persist_wpb (1: smallest workgroup, in waves)
  *   coarsest level   coarse_host_max (1500) coarse_host_fallback_max (6000) coarse_auto_cg_min (20000: a dense-inverse request on a
@@ -359,6 +363,50 @@ GMG_API int gmg_precond_apply(gmg_handle_t h, int lev, int which, const double *
 GMG_API int gmg_coarse_solve(gmg_handle_t h, const double *r, double *x, int memspace);
 /* dot / norm as used by the Krylov solvers (CGSolvers.jl:85,95,105). */
 GMG_API int gmg_dot(gmg_handle_t h, int64_t n, const double *a, const double *b, int memspace, double *out);
+
+/* ---- null space of the handle's operator: SolverInterfaces/NullSpaces.jl, LinearSolvers/NullspaceSolvers.jl ------------------
+ * For singular systems (pure-Neumann Poisson, enclosed-flow pressure, floating sub-problems).  A null space lives on a set-up
+ * handle: k vectors of the length of its Krylov vectors, copied into storage of the library's own that stays across later
+ * gmg_setup calls (numerical_setup!) and is counted by gmg_device_bytes.  Single rank only: a communicator of more than one rank
+ * (real or loopback) returns GMG_ERR_UNSUPPORTED.  Every operation except _set and _size returns GMG_ERR_STATE while no null
+ * space is set.  v / p / V follow `memspace`; alpha, G and the k-vectors of results are always host arrays.
+ * Option nullspace_fused chooses the kernels, same bits (see gmg_set_option).
+ *   _set             V: k vectors, vector q at V + q*ld (ld >= n).  n must be the handle's vector length (GMG_ERR_INVALID
+ *                    otherwise, as for k < 0 or a null V with k > 0).  Replaces -- and frees -- a null space set before; k = 0 clears it.
+ *   _get / _size     the vectors as they are now (after _orthonormalize: orthonormal) / k and n (0, 0: none set)
+ *   _orthonormalize  make_orthonormal!(N; method), NullSpaces.jl:67-100, on the device: method 0 = :gram_schmidt, 1 =
+ *                    :modified_gram_schmidt, the reference's loops in their order.  A vector whose norm is exactly 0 when it is to
+ *                    be normalised: GMG_ERR_SINGULAR.
+ *   _project         project!(p,N,v), :107-116: alpha_k = dot(v, w_k), p = sum_k alpha_k w_k (from 0.0, in the order k = 1..K).  p and
+ *                    alpha_out may be NULL.  subtract != 0: also v = v - p in the same pass (NullspaceSolvers.jl:116).
+ *   _make_orthogonal make_orthogonal!(N,v), :118-126: sequential, alpha_k from the already updated v
+ *   _reconstruct     reconstruct!(N,v,alpha), :134-139
+ *   _gram            G_out[i*k + j] = dot(w_i, w_j): the host evaluates is_orthonormal / is_orthogonal(N) (:33-47) from it
+ *   _dots            out_k[q] = dot(v, w_q): is_orthogonal(N, v), :49-55
+ *   _image_norms     out_k[q] = norm(A w_q) through the handle's finest (Krylov) operator: is_orthogonal(N, A), :57-65
+ *   _project_guess   on != 0: every Krylov entry of this handle (gmg_cg_solve, gmg_fgmres_solve[_pl], gmg_minres_solve,
+ *                    gmg_gmres_solve, gmg_richardson_solve) projects the initial guess, x -= sum_k dot(x, w_k) w_k, once, on the
+ *                    device copy of x before the iteration starts: solve!(::NullspaceSolverNS{:projected}), NullspaceSolvers.jl:109-120
+ *                    (with an orthonormal basis this removes the kernel component; the returned solution is not projected, as
+ *                    in the reference).  Skipped under option x0_zero.  Off by default; off costs no launch. */
+GMG_API int gmg_nullspace_set(gmg_handle_t h, int64_t n, int k, const double *V, int64_t ld, int memspace);
+GMG_API int gmg_nullspace_get(gmg_handle_t h, double *V_out, int64_t ld, int memspace);
+GMG_API int gmg_nullspace_size(gmg_handle_t h, int *k, int64_t *n);
+GMG_API int gmg_nullspace_orthonormalize(gmg_handle_t h, int method);
+GMG_API int gmg_nullspace_project(gmg_handle_t h, double *v, double *p, double *alpha_out, int memspace, int subtract);
+GMG_API int gmg_nullspace_make_orthogonal(gmg_handle_t h, double *v, double *alpha_out, int memspace);
+GMG_API int gmg_nullspace_reconstruct(gmg_handle_t h, double *v, const double *alpha, int memspace);
+GMG_API int gmg_nullspace_gram(gmg_handle_t h, double *G_out);
+GMG_API int gmg_nullspace_dots(gmg_handle_t h, const double *v, double *out_k, int memspace);
+GMG_API int gmg_nullspace_image_norms(gmg_handle_t h, double *out_k);
+GMG_API int gmg_nullspace_project_guess(gmg_handle_t h, int on);
+/* NullspaceSolver(LUSolver(), N; constrain_matrix = true) as the coarsest solver (NullspaceSolvers.jl:59-107): Kc holds k kernel
+ * vectors of the coarsest matrix (vector q at Kc + q*ld, host memory; the coarsest matrix must have been set).  With the
+ * dense-inverse coarse solver gmg_setup then inverts [A_L Kc; Kc' 0] on the host (LU with partial pivoting) and keeps its leading
+ * n_L x n_L block: the per-cycle solve is the same GEMV, its result is orthogonal to Kc.  n_L + k > coarse_host_max, or another
+ * coarse solver kind: GMG_ERR_UNSUPPORTED at gmg_setup.  gmg_update_values + gmg_setup rebuild it (numerical_setup!, :77-90).
+ * k = 0 removes the constraint. */
+GMG_API int gmg_set_coarse_nullspace(gmg_handle_t h, int k, const double *Kc, int64_t ld);
 
 /* ---- multi-GPU: one handle per rank/GPU ---------------------------------
  * The reference row-partitions every level with PartitionedArrays (own-then-ghost local
@@ -609,6 +657,20 @@ GMG_API int gmg_block_gmres_solve(gmg_block_handle_t h, const double *b, double 
                                   gmg_result *res, double *hist, int hist_cap);
 /* ConvergenceLog of the last solve of diagonal block i (GMG / CG blocks) */
 GMG_API int gmg_block_diag_log(gmg_block_handle_t h, int i, gmg_result *res);
+/* The null space of the block system (vectors of the total length, blocks concatenated): the twins of gmg_nullspace_* above, same
+ * arguments and status codes; _project_guess covers gmg_block_cg_solve, _fgmres_solve, _minres_solve and _gmres_solve; _image_norms
+ * applies the system blocks.  The handle must be set up; the null space stays across later gmg_block_setup calls. */
+GMG_API int gmg_block_nullspace_set(gmg_block_handle_t h, int64_t n, int k, const double *V, int64_t ld, int memspace);
+GMG_API int gmg_block_nullspace_get(gmg_block_handle_t h, double *V_out, int64_t ld, int memspace);
+GMG_API int gmg_block_nullspace_size(gmg_block_handle_t h, int *k, int64_t *n);
+GMG_API int gmg_block_nullspace_orthonormalize(gmg_block_handle_t h, int method);
+GMG_API int gmg_block_nullspace_project(gmg_block_handle_t h, double *v, double *p, double *alpha_out, int memspace, int subtract);
+GMG_API int gmg_block_nullspace_make_orthogonal(gmg_block_handle_t h, double *v, double *alpha_out, int memspace);
+GMG_API int gmg_block_nullspace_reconstruct(gmg_block_handle_t h, double *v, const double *alpha, int memspace);
+GMG_API int gmg_block_nullspace_gram(gmg_block_handle_t h, double *G_out);
+GMG_API int gmg_block_nullspace_dots(gmg_block_handle_t h, const double *v, double *out_k, int memspace);
+GMG_API int gmg_block_nullspace_image_norms(gmg_block_handle_t h, double *out_k);
+GMG_API int gmg_block_nullspace_project_guess(gmg_block_handle_t h, int on);
 
 #ifdef __cplusplus
 }
