@@ -4799,13 +4799,13 @@ void gmg_solver::build_patch(Level &L, Smoother &S, bool blocks_only)
         HIP_CHECK(hipGetLastError());
         if (from_dense) HIP_CHECK(hipStreamSynchronize(stream));   // d_dense is refilled by the next batch
       } else {
-        // patches with more than 64 dofs: one thread per patch on global scratch (rows = cols, CSR source)
+        // patches with more than 64 dofs: one thread per patch on global scratch (CSR source)
         const int grid = (int)((cnt + 63) / 64);
         if (L.A.ptr64)
-          hipLaunchKernelGGL((patch_factor_kernel<int64_t>), dim3(grid), dim3(64), 0, stream, cnt, S.d_pptr + p0, S.d_pdofs,
+          hipLaunchKernelGGL((patch_factor_kernel<int64_t>), dim3(grid), dim3(64), 0, stream, cnt, S.d_pptr + p0, S.d_pdofs, d_pcol,
                              S.d_boff + p0, (const int64_t *)L.A.rowptr, L.A.col, L.A.val, out - e0, d_scratch, max_np, pivoting, d_nsing);
         else
-          hipLaunchKernelGGL((patch_factor_kernel<int32_t>), dim3(grid), dim3(64), 0, stream, cnt, S.d_pptr + p0, S.d_pdofs,
+          hipLaunchKernelGGL((patch_factor_kernel<int32_t>), dim3(grid), dim3(64), 0, stream, cnt, S.d_pptr + p0, S.d_pdofs, d_pcol,
                              S.d_boff + p0, (const int32_t *)L.A.rowptr, L.A.col, L.A.val, out - e0, d_scratch, max_np, pivoting, d_nsing);
         HIP_CHECK(hipGetLastError());
       }

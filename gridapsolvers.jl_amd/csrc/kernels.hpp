@@ -4616,9 +4616,11 @@ __global__ void densify_ld_kernel(int64_t n, int64_t lda, const PtrT *__restrict
 //           PatchSolvers.jl:288-297 => deterministic, no atomics).
 // ---------------------------------------------------------------------------
 // One thread per patch builds the inverse by Gauss-Jordan on an identity-augmented
-// copy held in global scratch (setup only, not on the timed path).
+// copy held in global scratch (setup only, not on the timed path).  Block = A[rows_p, cols_p]: pdofs holds the rows, pcol the
+// columns (the same table when the caller gave no separate patch_cols).
 template <typename PtrT>
 __global__ void patch_factor_kernel(int64_t npatch, const int64_t *__restrict__ pptr, const int32_t *__restrict__ pdofs,
+                                    const int32_t *__restrict__ pcol,
                                     const int64_t *__restrict__ boff, const PtrT *__restrict__ rowptr,
                                     const int32_t *__restrict__ col, const double *__restrict__ val,
                                     double *__restrict__ binv, double *__restrict__ scratch, int max_np,
@@ -4629,7 +4631,8 @@ __global__ void patch_factor_kernel(int64_t npatch, const int64_t *__restrict__ 
   const int np = (int)(pptr[p + 1] - pptr[p]);
   if (np == 0) return;
   const int32_t *dofs = pdofs + pptr[p];
-  double *M = scratch + (size_t)p * max_np * max_np; // row-major np x np copy of A[p,p]
+  const int32_t *cdofs = pcol + pptr[p];
+  double *M = scratch + (size_t)p * max_np * max_np; // row-major np x np copy of A[rows_p, cols_p]
   double *X = binv + boff[p];                        // row-major np x np, becomes the inverse
   for (int r = 0; r < np; ++r) {
     for (int c = 0; c < np; ++c) { M[r * np + c] = 0.0; X[r * np + c] = (r == c) ? 1.0 : 0.0; }
@@ -4637,7 +4640,7 @@ __global__ void patch_factor_kernel(int64_t npatch, const int64_t *__restrict__ 
     for (PtrT k = rowptr[gr]; k < rowptr[gr + 1]; ++k) {
       const int32_t gc = col[k];
       for (int c = 0; c < np; ++c)
-        if (dofs[c] == gc) M[r * np + c] += val[k];
+        if (cdofs[c] == gc) M[r * np + c] += val[k];
     }
   }
   // LU-ordered elimination (forward), then back-substitution on all columns of X
