@@ -232,6 +232,7 @@ struct DevCSR {
   mutable Z2Geo z2;                 // fused pair of sweeps (sells_z2sweep_kernel): geometry, valid when z2_ok > 0
   mutable Z2Geo zbx;                // single sweep of a constant-coefficient box (sells_boxsweep_kernel): the same grid, its own chains
   mutable int z2_ok = -1;           // -1 not examined yet, 0 no, 1 yes
+  mutable bool xnext_used = false;  // the last per-sweep pass of this operator ran the x-from-the-next-residual schedule (byte counts)
   int64_t nrows = 0, ncols = 0, nnz = 0;
   bool ptr64 = false;
   void *rowptr = nullptr;
@@ -800,6 +801,9 @@ struct gmg_solver {
   int pat_fma = 0;      // GMG_PAT_FMA: fused multiply-add taps in the row-pattern sweeps (one rounding per tap: not the reference's mul! arithmetic)
   int pat_rsweep = 1;   // GMG_PAT_RSWEEP: sweeps of uniform-diagonal row-pattern levels gather r itself (no s vector: sells_rsweep_kernel)
   int pat_defer = 1;    // GMG_PAT_DEFER: x updated every second sweep (shared-offset pattern kernel)
+  int pat_xnext = 1;    // GMG_PAT_XNEXT: per-sweep passes of an even number of r-gather sweeps update x in sweeps 0, 2, ... with s_k and s_{k+1} (the latter from the r_{k+1} the sweep holds in registers: no r_{k-1} re-read); 0: x = (x + s_{k-1}) + s_k in sweeps 1, 3, ...
+  int pat_close = 1;    // GMG_PAT_CLOSE: a post-smoothing pass whose residual nobody reads (final post pass of levels >= 1; of level 0 in a one-cycle preconditioner application) does not run its last sweep
+  bool r0_dead = false; // set by gmg_solve_dev around a cycle whose post-cycle residual of level 0 is not read
   int pat_dinv = 1;     // GMG_PAT_DINV: Jacobi inverse diagonal from the pattern table instead of its vector
   int pat_shared = 1;   // GMG_PAT_SHARED: shared-offset (stencil) form when the offsets are row-relative
   int one_gather_sweep = 1;   // GMG_ONE_GATHER: sweep gathers s = w*Dinv*r (1) or r and Dinv (0)
@@ -2495,6 +2499,17 @@ struct gmg_solver {
     ensure_z2(M);
     return M.z2_ok > 0 && M.z2.box != 0;
   }
+  // Does launch_rsweep() end in a kernel that has x mode 3 (x = (x + s_k) + s_{k+1}, the latter from the row's own r_{k+1} in
+  // registers) for this operator?  Same order of decisions as launch_rsweep(): tile, box, z-walk, pair sweep, single-row sweep --
+  // only the z-walk and the pair sweep have it.
+  bool xnext_kernel(const DevCSR &M)
+  {
+    if (pat_tile >= 2 || (pat_tile == 1 && M.nrows >= pat_tile_rows)) return false;   // (whether or not the tile sweep then applies)
+    if (box_level(M)) return false;
+    ZWalkGeo zg;
+    if (pat_r2 && pat_zwalk && (pat_zwalk >= 2 || M.nrows >= pat_zwalk_rows) && zwalk_geo(M, zg)) return true;
+    return pat_r2 && (M.pat_nruns == 9 || M.pat_nruns == 3);
+  }
   void launch_rsweep(const DevCSR &M, const double *r_cur, double *r_next, const double *r_prev, double *x, bool x_zero, double omega, int xmode)
   {
     SellSArgs a;
@@ -2505,7 +2520,7 @@ struct gmg_solver {
     const int nsl = (int)((M.nrows + rows - 1) / rows);
     a.nrows = M.nrows; a.ncols = M.ncols; a.nslices = nsl; a.xcd_remap = xcd_remap;
     a.x_zero = x_zero ? 1 : 0; a.x = r_cur; a.omega = omega; a.y = r_next; a.b = r_cur; a.x2 = x; a.s_out = const_cast<double *>(r_prev);
-    if ((pat_tile >= 2 || (pat_tile == 1 && M.nrows >= pat_tile_rows)) && launch_tsweep(M, a, nsl)) return;
+    if ((pat_tile >= 2 || (pat_tile == 1 && M.nrows >= pat_tile_rows)) && xmode != 3 && launch_tsweep(M, a, nsl)) return;
     const int wpb = sell_block > 0 ? sell_block / 64 : (nsl >= 256 * 32 ? 4 : pat_small_wpb);
     const int nu = M.pat_k * M.pat_nruns;
     const int nb = pat_nb > 0 ? pat_nb : (nsl >= 200000 ? 2 : 1);
@@ -2514,7 +2529,7 @@ struct gmg_solver {
     const size_t lds2 = (size_t)M.pat_np * nu * 16 + 16;
     const bool mk = pat_strict || !M.ptab8;
     // constant-coefficient box: one coefficient set per wave from the kernel arguments, no pattern ids, no LDS
-    if (box_level(M)) {
+    if (xmode != 3 && box_level(M)) {                        // (xmode 3 is only asked for where xnext_kernel() has ruled these forms out)
       const Z2Geo &gb = M.zbx;
       const int nch = gb.nzb * gb.ny * gb.nxs;
       const dim3 gx((unsigned)((nch + 3) / 4)), bx(256);
@@ -2545,7 +2560,7 @@ struct gmg_solver {
         else { if (pat_fma) hipLaunchKernelGGL((sells_zsweep_kernel<XMV, false, true>), gz, bz, ldsz, stream, a, zg);       \
                else hipLaunchKernelGGL((sells_zsweep_kernel<XMV, false, false>), gz, bz, ldsz, stream, a, zg); }            \
       } while (0)
-      if (xmode == 0) GMG_ZW_LAUNCH(0); else if (xmode == 1) GMG_ZW_LAUNCH(1); else GMG_ZW_LAUNCH(2);
+      if (xmode == 0) GMG_ZW_LAUNCH(0); else if (xmode == 1) GMG_ZW_LAUNCH(1); else if (xmode == 3) GMG_ZW_LAUNCH(3); else GMG_ZW_LAUNCH(2);
 #undef GMG_ZW_LAUNCH
       HIP_CHECK(hipGetLastError());
       return;
@@ -2572,7 +2587,7 @@ struct gmg_solver {
           else { if (pat_fma) hipLaunchKernelGGL((sells_r2sweep_kernel<XMV, false, true, 9, 2>), g8, b8, lds2, stream, a);     \
                  else hipLaunchKernelGGL((sells_r2sweep_kernel<XMV, false, false, 9, 2>), g8, b8, lds2, stream, a); }          \
         } while (0)
-        if (xmode == 0) GMG_R2_LAUNCH8(0); else if (xmode == 1) GMG_R2_LAUNCH8(1); else GMG_R2_LAUNCH8(2);
+        if (xmode == 0) GMG_R2_LAUNCH8(0); else if (xmode == 1) GMG_R2_LAUNCH8(1); else if (xmode == 3) GMG_R2_LAUNCH8(3); else GMG_R2_LAUNCH8(2);
 #undef GMG_R2_LAUNCH8
         HIP_CHECK(hipGetLastError());
         return;
@@ -2592,12 +2607,13 @@ struct gmg_solver {
         if (mk) { if (pat_fma) GMG_R2_LAUNCH2(XMV, true, true); else GMG_R2_LAUNCH2(XMV, true, false); }         \
         else { if (pat_fma) GMG_R2_LAUNCH2(XMV, false, true); else GMG_R2_LAUNCH2(XMV, false, false); }          \
       } while (0)
-      if (xmode == 0) GMG_R2_LAUNCH(0); else if (xmode == 1) GMG_R2_LAUNCH(1); else GMG_R2_LAUNCH(2);
+      if (xmode == 0) GMG_R2_LAUNCH(0); else if (xmode == 1) GMG_R2_LAUNCH(1); else if (xmode == 3) GMG_R2_LAUNCH(3); else GMG_R2_LAUNCH(2);
 #undef GMG_R2_LAUNCH2
 #undef GMG_R2_LAUNCH
       HIP_CHECK(hipGetLastError());
       return;
     }
+    REQUIRE(xmode != 3, GMG_ERR_STATE, "sells_rsweep_kernel has no x mode 3 (xnext_kernel() and launch_rsweep() disagree)");
     M.note_sweep("sells_rsweep_kernel<XM=*,NB=%d,MK=%d,FM=%d> wgs=%d wpb=%d", nb >= 2 ? 2 : 1, mk ? 1 : 0, pat_fma ? 1 : 0, wg2, wpb);
 #define GMG_RSWEEP_LAUNCH(XMV, NBV)                                                                            \
     do {                                                                                                         \
@@ -3097,7 +3113,8 @@ struct gmg_solver {
   // One launch for the whole pass on small single-GPU levels in the shared-offset pattern form (see sells_smooth_kernel).
   // s_0 is in L.sbuf[0].  Returns false when the level does not qualify (the caller then runs sweep by sweep).
   // dry = true: only answer whether the pass WOULD run as one launch (nothing is allocated or launched)
-  bool smooth_persistent(int l, const Smoother &S, double *x, const double *r_in, double *r_out, bool x_zero, int niter, bool dry = false)
+  // close: the pass's residual has no reader -- the kernel stops one sweep early and adds the pending increment to x (r_out is not written)
+  bool smooth_persistent(int l, const Smoother &S, double *x, const double *r_in, double *r_out, bool x_zero, int niter, bool dry = false, bool close = false)
   {
     Level &L = lev[l];
     const DevCSR &M = L.A;
@@ -3156,7 +3173,7 @@ struct gmg_solver {
     a.rowpid = M.rowpid; a.tab = M.ptab; a.tab8 = M.ptab8; a.run_off = M.prun; a.np = M.pat_np; a.nruns = M.pat_nruns;
     a.nrows = M.nrows; a.ncols = M.ncols; a.nslices = nsl;
     a.pdinv = pat_dinv ? M.pdinv : nullptr; a.dinv = L.dinv; a.omega = S.omega;
-    a.niter = niter; a.x_zero = x_zero ? 1 : 0;
+    a.niter = niter; a.x_zero = x_zero ? 1 : 0; a.close = close && niter >= 2 ? 1 : 0;
     a.r_in = r_in; a.r_out = r_out; a.x = x; a.s_a = L.sbuf[0]; a.s_b = L.sbuf[1];
     a.flags = L.pflags; a.epoch = L.pf_epoch; a.err = d_perr; a.err_dev = d_perr_dev; a.halo_wg = halo; a.fenced = persist_fenced;
     L.pf_epoch += (uint32_t)niter;
@@ -3176,7 +3193,7 @@ struct gmg_solver {
     HIP_CHECK(hipGetLastError());
     if (prof) {
       HIP_CHECK(hipEventRecord(prof_ev[prof_used + 1], stream));
-      prof_w[prof_used / 2] = niter;
+      prof_w[prof_used / 2] = niter - a.close;
       prof_xm[prof_used / 2] = 0;
       prof_used += 2;
     }
@@ -3276,9 +3293,12 @@ struct gmg_solver {
   // solve!(x,ns::RichardsonSmootherNumericalSetup,r), RichardsonSmoothers.jl:84-98.
   // r_in may be a caller-owned read-only vector; returns the buffer holding the
   // updated residual (one of L.rbuf[]).
-  double *smooth(int l, Smoother &S, double *x, const double *r_in, bool x_zero)
+  // r_dead: nobody reads the residual this pass leaves behind (cycle(): which passes) -- the returned buffer then holds no defined
+  // values.  Only acted on by the Jacobi passes of a single rank (option pat_close); every other pass runs all its sweeps.
+  double *smooth(int l, Smoother &S, double *x, const double *r_in, bool x_zero, bool r_dead = false)
   {
     Level &L = lev[l];
+    r_dead = r_dead && pat_close && comm.nranks == 1;
     const int64_t n = L.n;
     const bool r_internal = (r_in == L.rbuf[0] || r_in == L.rbuf[1]);
     if (S.niter <= 0) {
@@ -3322,7 +3342,15 @@ struct gmg_solver {
           }
           if (pat_fuse2) ensure_z2(L.A);
           const bool fuse2 = fuse2_level(L);
-          for (int it = 0; it < nb; ++it) {
+          // x from the NEXT residual: sweep k holds its rows' r_{k+1} in registers, so the pair's two increments can both be added
+          // there -- x = (x + s_k) + s_{k+1} in sweeps 0, 2, ..., the same sums in the same order as x = (x + s_{k-1}) + s_k one sweep
+          // later, without reading r_{k-1} back.  Needs an even number of sweeps and a level without halo (ghost_fix_* corrects the
+          // boundary rows of r_next AFTER the sweep: what the sweep had in registers was not r_{k+1} there).
+          const bool xnext = pat_xnext && !fuse2 && (nb & 1) == 0 && comm.nranks == 1 && xnext_kernel(L.A);
+          L.A.xnext_used = xnext;
+          // ... and then x is complete after sweep nb - 2: where r is dead, sweep nb - 1 (x untouched) has nothing left to do
+          const int nsw = (xnext && r_dead) ? nb - 1 : nb;
+          for (int it = 0; it < nsw; ++it) {
             double *next = (cur == L.rbuf[0]) ? L.rbuf[1] : L.rbuf[0];
             if (fuse2 && (it & 1) == 0 && it + 1 < nb) {
               // sweeps it (x untouched) and it + 1 (x += both increments) in ONE launch: r_k -> r_{k+2}, r_{k+1} never leaves the CUs
@@ -3342,7 +3370,8 @@ struct gmg_solver {
             }
             int xmode = 0;
             bool xz = xz0 && it == 0;
-            if ((it & 1) == 0 && it + 1 < nb) xmode = 1;
+            if (xnext) xmode = (it & 1) ? 1 : 3;
+            else if ((it & 1) == 0 && it + 1 < nb) xmode = 1;
             else if (it & 1) { xmode = 2; xz = xz0 && it == 1; }
             const bool fp = can_fuse_pack(l);
             rsweep(l, S, x, cur, next, prev, xz, xmode, fp && it > 0, fp && it + 1 < nb);
@@ -3357,7 +3386,7 @@ struct gmg_solver {
           HIP_CHECK(hipGetLastError());
         }
         L.s0_ready = false;
-        if (one_launch && smooth_persistent(l, S, x, cur, out, xz0, nb)) { cur = out; continue; }
+        if (one_launch && smooth_persistent(l, S, x, cur, out, xz0, nb, false, r_dead)) { cur = out; continue; }
         for (int it = 0; it < nb; ++it) {
           int xmode = 0;
           bool xz = xz0 && it == 0;
@@ -3565,8 +3594,11 @@ struct gmg_solver {
       else
       { StepTimer tm(*this, "r -= A dx", l); apply_A_sub(l, L.dx, r, &L.post); }                    // :495-496 rh -= Ah dxh (+ the post-smoother's first s)
     }
-    { StepTimer tm(*this, "post-smooth", l); r = smooth(l, L.post, x, r, false); }                    // :499
-    L.rcur = r;
+    // the residual of this last pass: on levels >= 1 nothing reads it (the parent takes x only); on level 0 gmg_solve_dev says
+    // whether it will (r0_dead).  The W / F re-smooth above is followed by a restriction: its r is live.
+    const bool r_dead = l > 0 || r0_dead;
+    { StepTimer tm(*this, "post-smooth", l); r = smooth(l, L.post, x, r, false, r_dead); }            // :499
+    L.rcur = r_dead ? nullptr : r;
   }
 
   // solve!(x,ns::GMGNumericalSetup,b), GMGLinearSolvers.jl:612-645 (device pointers).
@@ -3591,11 +3623,16 @@ struct gmg_solver {
     bool done = log.init(res);                             // :628
     if (done && x_zero) zero(x, n);
     const bool single = (log.maxiter == 1);
+    // the fast path below neither takes the post-cycle norm nor runs another cycle: the residual level 0's post-smoother leaves is dead
+    const bool fast = single && known_res0 >= 0.0 && (verbose <= 0 || has_outer());
     while (!done) {
-      cycle(0, x, r_in, x_zero, cycle_type);               // :630-637
-      r_in = L0.rcur;
+      r0_dead = fast && mode == GMG_MODE_PRECONDITIONER;
+      try { cycle(0, x, r_in, x_zero, cycle_type); }       // :630-637
+      catch (...) { r0_dead = false; throw; }
+      r0_dead = false;
+      r_in = L0.rcur;                                      // (null on the fast path)
       x_zero = false;
-      if (single && known_res0 >= 0.0 && (verbose <= 0 || has_outer())) {
+      if (fast) {
         // maxiter == 1: update! returns true whatever the norm is (:640); the post-cycle norm is a
         // logging-only quantity here and is not evaluated unless the solver is verbose (gmg_set_verbose):
         // residuals[1] of the GMG's own log then reads NaN (documented in INTEGRATION.md).
@@ -4034,6 +4071,8 @@ struct gmg_solver {
     halo_fuse_pack = opt_int("GMG_HALO_FUSE_PACK", 1);
     prof_stride = std::max(1, opt_int("GMG_PROF_STRIDE", 7));
     pat_defer = opt_int("GMG_PAT_DEFER", 1);
+    pat_xnext = opt_int("GMG_PAT_XNEXT", 1);
+    pat_close = opt_int("GMG_PAT_CLOSE", 1);
     pat_rsweep = opt_int("GMG_PAT_RSWEEP", 1);
     if (n_cus <= 0) {
       int v = 0;
@@ -4141,7 +4180,7 @@ struct gmg_solver {
       mat = 2.0 * N;                                       // 16-bit pattern id per row; the table lives in LDS
       if (pat_dinv && A.pdinv) vec -= 8.0 * N;             // 1/diag from the pattern table
       if (pat_defer) vec -= 4.0 * N;                       // x touched every second sweep: (8+8+8)/2 instead of 8+8
-      if (pat_defer && rsweep_level(L)) vec = 28.0 * N;    // sells_rsweep_kernel: r in + r out, (x in + x out + r_prev) every second sweep; no s, no 1/diag
+      if (pat_defer && rsweep_level(L)) vec = A.xnext_used ? 24.0 * N : 28.0 * N;   // r-gather sweeps: r in + r out, (x in + x out [+ r_prev: not with pat_xnext]) every second sweep; no s, no 1/diag
       if (fuse2_level(L)) vec = 16.0 * N;                  // sells_z2sweep_kernel, per sweep of the pair: (r_k in + r_{k+2} out + x in + x out) / 2
       if (box_active(A)) mat = 0.0;                        // sells_boxsweep_kernel: no pattern ids either -- the coefficients are kernel arguments
     } else if (A.pat) mat = (A.rowbase ? 6.0 : 2.0) * N;
@@ -4165,6 +4204,7 @@ struct gmg_solver {
                      : (A.sell && (A.comp_idx || A.vdict)) ? false
                      : (A.sell) ? (sell_defer && sell_un >= 6 && sell_un < 9) : false;
     if (!defer || fuse2_level(L)) return mean;              // (a fused pair is one form: half of the pair's bytes per sweep)
+    if (A.xnext_used && rsweep_level(L)) return mean - 8.0 * N + (xmode == 1 ? 0.0 : 16.0 * N);   // x in + x out on every second sweep, no r_prev
     return mean - 12.0 * N + (xmode == 1 ? 0.0 : xmode == 2 ? 24.0 * N : 16.0 * N);
   }
   KrylovOps level0_ops(int use_precond);
@@ -4220,6 +4260,7 @@ static double cg_core(gmg_solver &S, int64_t n, const double *db, double *dx, do
   // fused second stages (sum_partials_all): gamma = dot(z,r) is summed by xpby_dev_kernel, dot(p,w) by cg_update_kernel, and
   // ||r|| is reduced and posted to the host by one launch -- 4 launches per iteration instead of 8 for the scalars
   const bool fuse = S.fuse_reductions();
+  const bool split = fuse && S.opt_int("GMG_CG_SPLIT", 0) != 0;
   const unsigned xgrid = fuse ? (unsigned)nb : (unsigned)gmg_solver::grid_for(n);
   while (!done) {
     int ngp = 0;                                         // gamma still in partials?
@@ -4245,15 +4286,29 @@ static double cg_core(gmg_solver &S, int64_t n, const double *db, double *dx, do
       if (fuse) npw = S.dot_partials(n, p, w, S.d_partials); else { S.dot_async(n, p, w, kPW, false); npw = 0; }   // :105
     }
     double *nparts = fuse ? S.d_partials2 : S.d_partials;
+    if (split) {
+      // (option cg_split, default 0: measured equal to the single kernel, profiles/xnext_ab_128.md)
+      // r -= alpha w and ||r|| first, x += alpha p behind the launch that posts the norm: it runs while the host decides
+      hipLaunchKernelGGL(cg_update_r_kernel, dim3(nb), dim3(kBlock), 0, S.stream, n, S.d_scalars + g_new, S.d_scalars + kPW, w, r,
+                         nparts, npw ? S.d_partials : nullptr, npw); // :109
+      HIP_CHECK(hipGetLastError());
+      S.finish_reduction(nb, 0, true, nparts, true);
+      hipLaunchKernelGGL(cg_update_x_kernel, dim3(nb), dim3(kBlock), 0, S.stream, n, S.d_scalars + g_new, S.d_scalars + kPW, p, dx);   // :108
+      HIP_CHECK(hipGetLastError());
+    } else {
     hipLaunchKernelGGL(cg_update_kernel, dim3(nb), dim3(kBlock), 0, S.stream, n, S.d_scalars + g_new, S.d_scalars + kPW, p, w, dx, r,
                        nparts, npw ? S.d_partials : nullptr, npw); // :108-109
     HIP_CHECK(hipGetLastError());
     S.finish_reduction(nb, 0, true, nparts, true);
+    }
     resn = S.fetch_scalar(0);                            // :111
     done = log.update(resn);                             // :112
     std::swap(g_old, g_new);
     first = false;
   }
+  // the posted norm no longer implies that x is complete: the last x += alpha p was issued behind it.  The outermost solve hands x
+  // to its caller (who may read it from another stream); a nested one is consumed in stream order.
+  if (split && S.krylov_depth == 1) HIP_CHECK(hipStreamSynchronize(S.stream));
   return resn;
 }
 
@@ -6806,7 +6861,7 @@ const OptionKey kOptionKeys[] = {
   {"GMG_PERSIST_SHARED", false}, {"GMG_PROF_STRIDE", true}, {"GMG_REFRESH", true}, {"GMG_SELL", false}, {"GMG_SELL_BLOCK", false},
   {"GMG_SELL_DEFER", false}, {"GMG_SELL_MAXPAD", false}, {"GMG_SELL_UN", false}, {"GMG_SETUP_TIMING", true}, {"GMG_VDICT", false},
   {"GMG_XCD_REMAP", false}, {"GMG_XCD_REMAP_BIG", false}, {"GMG_X0_ZERO", true}, {"GMG_HOST_POLL", true}, {"GMG_HOST_CHUNK_BYTES", true}, {"GMG_PAT_FMA", false}, {"GMG_PAT_R2", false}, {"GMG_RED_FUSED", false}, {"GMG_GMRES_FUSED", true}, {"GMG_NULLSPACE_FUSED", true}, {"GMG_PAT_R2MV", false}, {"GMG_PAT_R2_OCC", false}, {"GMG_PAT_PAIR_P", false}, {"GMG_PAT_R2MV_DOT", false}, {"GMG_PERSIST_WPB", false}, {"GMG_HOST_TIMELINE", true}, {"GMG_PAT_R2MV_MIN", false}, {"GMG_PAT_BCAST", false}, {"GMG_PAT_R2_WGS", false}, {"GMG_PAT_ZWALK", false}, {"GMG_PAT_ZWALK_T", false}, {"GMG_PAT_ZWALK_ROWS", false}, {"GMG_PAT_ZWALK_MV", false}, {"GMG_PAT_ZWALK_WIDE", false}, {"GMG_PAT_ZWALK_WIDE_ROWS", false}, {"GMG_PAT_FUSE2", false}, {"GMG_PAT_FUSE2_W", false}, {"GMG_PAT_FUSE2_T", false}, {"GMG_PAT_FUSE2_ROWS", false}, {"GMG_PAT_FUSE2_BOX", false}, {"GMG_PAT_BOX", false}, {"GMG_PAT_WIDE_GRID", false}, {"GMG_PAT_BOX_T", false}, {"GMG_PAT_BOX_MIN_ROWS", false}, {"GMG_PAT_BOX_MAX_ROWS", false},
-  {"GMG_PERSIST_FORCE_TIMEOUT", true},
+  {"GMG_PERSIST_FORCE_TIMEOUT", true}, {"GMG_PAT_XNEXT", false}, {"GMG_PAT_CLOSE", false}, {"GMG_CG_SPLIT", true},
 };
 // "pat_tile", "PAT_TILE" and "GMG_PAT_TILE" name the same option
 const OptionKey *find_option(const char *key)

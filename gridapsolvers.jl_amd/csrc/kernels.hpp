@@ -1839,6 +1839,8 @@ __device__ __forceinline__ void st2_unaligned(double *p, gmg_d2 v)
   *reinterpret_cast<d2u *>(p) = v;
 }
 
+// XM = 3 (option pat_xnext): x = (x + s_k) + s_{k+1} with s_{k+1} = omega*(d*r_{k+1}) formed from the r_{k+1} the lane is about to store
+// (after the masked redo) -- the sums of XM = 2 one sweep earlier, same order, same roundings, no a.s_out load.  Also in sells_zsweep_kernel.
 // NR = number of runs (9: 27-point operators; 3: 9-point) -- compile time, so that the run offsets live in scalar registers (read in the
 // loop from the argument array they are vector loads the gathers then wait for) and the run loop is fully unrolled.
 // OCC = 1: the run loop stays rolled (groups of three runs; unrolled, the compiler hoists the 54 coefficient reads of a slice and the
@@ -2010,6 +2012,7 @@ __global__ __launch_bounds__(OCC == 2 ? 2 * kBlock : kBlock, OCC == 2 ? 4 : (OCC
     gmg_d2 xn = gmg_d2{0.0, 0.0};
     if (XM == 0) xn = gmg_d2{e2.x + sk.x, e2.y + sk.y};
     else if (XM == 2) xn = gmg_d2{(e2.x + omega * (du * rp.x)) + sk.x, (e2.y + omega * (du * rp.y)) + sk.y};
+    else if (XM == 3) xn = gmg_d2{(e2.x + sk.x) + omega * (du * rn.x), (e2.y + sk.y) + omega * (du * rn.y)};   // s_k, then s_{k+1} from the r_{k+1} just formed
     if (lane < 63) {
       if (inner) {
         if (XM != 1) st2_unaligned(a.x2 + row, xn);
@@ -2241,6 +2244,7 @@ __global__ __launch_bounds__(kBlock, 4) void sells_zsweep_kernel(SellSArgs a, ZW
       gmg_d2 xn = gmg_d2{0.0, 0.0};
       if (XM == 0) xn = gmg_d2{cur.e2.x + sk.x, cur.e2.y + sk.y};
       else if (XM == 2) xn = gmg_d2{(cur.e2.x + omega * (du * cur.rp.x)) + sk.x, (cur.e2.y + omega * (du * cur.rp.y)) + sk.y};
+      else if (XM == 3) xn = gmg_d2{(cur.e2.x + sk.x) + omega * (du * rn.x), (cur.e2.y + sk.y) + omega * (du * rn.y)};   // s_k, then s_{k+1} from the r_{k+1} just formed
       prow = r0 + 2 * lane;
       pnm = min(len - 2 * lane, lastrow + 1 - prow);                       // rows of this lane inside the interval and the level: <= 0, 1, >= 2
       prn = rn; pxn = xn;
@@ -3256,6 +3260,7 @@ struct SellSmoothArgs {
   int halo_wg;              // workgroup w waits for w-halo_wg .. w+halo_wg
   int fenced;               // progress words: release store / acquire after the poll (agent scope) on top of the explicit store drain
   uint32_t *err_dev;        // device-memory twin of *err (read at the end of the pass: a host-mapped word would cost a PCIe round trip)
+  int close;                // the pass's r has no reader (niter >= 2): the last sweep's A s is not formed, x += s_{niter-1} from registers, r_out not written
 };
 
 __device__ __forceinline__ double ld_agent(const double *p)
@@ -3314,7 +3319,13 @@ __global__ __launch_bounds__(1024) void sells_smooth_kernel(SellSmoothArgs a)
   const double *sin = a.s_a;
   double *sout = a.s_b;
   const int nb_lo = max(0, w - a.halo_wg), nb_hi = min((int)gridDim.x - 1, w + a.halo_wg);
-  for (int k = 0; k < a.niter; ++k) {
+  // close: sweep niter - 1 would only turn r_{niter-1} into r_niter, which nobody reads; its increment s_{niter-1} is already in `so`
+  // after sweep niter - 2, so the loop stops one sweep early and x takes it below -- one neighbour wait and one publish fewer, none
+  // added.  The epoch still advances by niter per launch although the workgroups now publish epoch + niter - 2 at most: the words
+  // only grow and are compared by signed difference, so the next launch (which waits for epoch + niter + k, k >= 1) just sees words
+  // that are further behind -- exactly what it sees of a neighbour that has not started yet.
+  const int nk = a.close ? a.niter - 1 : a.niter;
+  for (int k = 0; k < nk; ++k) {
     if (k > 0 && !(DBG & 1)) {
       // neighbours' sweep k-1 published?  one lane per neighbour, relaxed agent-scope polls
       if (wave == 0 && nb_lo + lane <= nb_hi && nb_lo + lane != w) {
@@ -3378,7 +3389,7 @@ __global__ __launch_bounds__(1024) void sells_smooth_kernel(SellSmoothArgs a)
       }
       acc[i] = s;
     }
-    const bool publish = k + 1 < a.niter;                    // the s of the last sweep has no reader
+    const bool publish = k + 1 < nk;                         // the s of the last sweep has no reader
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
       xr[i] = xr[i] + so[i];                                 // x += s_k
@@ -3400,6 +3411,13 @@ __global__ __launch_bounds__(1024) void sells_smooth_kernel(SellSmoothArgs a)
   // a wait timed out somewhere (as far as this workgroup can see): the pass is void -- leave x and r as they were, the host
   // re-runs the solve sweep by sweep (with_persist_retry)
   if (a.err_dev && __hip_atomic_load(a.err_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return;
+  if (a.close) {
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      if (own[i]) a.x[row[i]] = xr[i] + so[i];               // x += s_{niter-1}
+    }
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < NS; ++i) {
     if (own[i]) { a.x[row[i]] = xr[i]; a.r_out[row[i]] = r[i]; }
@@ -3756,6 +3774,38 @@ __global__ __launch_bounds__(kBlock) void cg_update_kernel(int64_t n, const doub
   }
   const double t = block_sum(s, sh);
   if (threadIdx.x == 0) partials[blockIdx.x] = t;
+}
+// cg_update_kernel in two launches (option cg_split): the half the residual norm waits for -- r -= alpha*w and the partial ||r||^2,
+// same loop, same block_sum, so the partials are the same bits -- and the half nothing in the iteration waits for, x += alpha*p,
+// which then runs while the host looks at the norm.  Both form alpha = gamma / dot(p,w) from the same two stored scalars.
+__global__ __launch_bounds__(kBlock) void cg_update_r_kernel(int64_t n, const double *__restrict__ gamma,
+                                                             double *__restrict__ pw, const double *__restrict__ w,
+                                                             double *__restrict__ r, double *__restrict__ partials,
+                                                             const double *__restrict__ pwparts, int npwparts)
+{
+  __shared__ double sh[5];
+  double pwv;
+  if (pwparts) {
+    pwv = sum_partials_all(pwparts, npwparts, sh);
+    if (blockIdx.x == 0 && threadIdx.x == 0) pw[0] = pwv;
+    __syncthreads();                                         // sh is reused below
+  } else pwv = pw[0];
+  const double alpha = gamma[0] / pwv;
+  double s = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+    const double rn = r[i] - alpha * w[i];
+    r[i] = rn;
+    s += rn * rn;
+  }
+  const double t = block_sum(s, sh);
+  if (threadIdx.x == 0) partials[blockIdx.x] = t;
+}
+// pw[0] was stored by cg_update_r_kernel (or by the reduce launch in front of it)
+__global__ __launch_bounds__(kBlock) void cg_update_x_kernel(int64_t n, const double *__restrict__ gamma, const double *__restrict__ pw,
+                                                             const double *__restrict__ p, double *__restrict__ x)
+{
+  const double alpha = gamma[0] / pw[0];
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) x[i] += alpha * p[i];
 }
 // y += alpha*x                        (FGMRESSolvers.jl:162,192)
 __global__ void axpy_kernel(int64_t n, double alpha, const double *__restrict__ x, double *__restrict__ y)

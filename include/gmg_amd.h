@@ -217,6 +217,11 @@ GMG_API int gmg_set_options(gmg_handle_t h, int mode, int cycle, int maxiter, do
  *   sweep kernels    pat_rsweep (1) pat_r2 (1: two rows per lane in the r-gather sweep) pat_r2_occ (2: its 64-register form, eight waves per SIMD, in workgroups of eight waves on big levels; 1: four waves; 0: off) pat_r2_wgs (0 = one round of workgroups) pat_tile (0: never -- levels >= pat_tile_rows (3500000) take the pair sweep with one slice per wave; 1: tile sweep on those levels; 2: wherever it applies) pat_tile_min (512)
  *                    pat_tile_t (48) pat_tile_lds (79872) pat_strict (1) pat_fma (0: products and sums rounded separately, as the
  *                    reference's mul!; 1: fused multiply-add taps in the row-pattern sweeps -- not bit-identical)
+ *                    pat_xnext (1: per-sweep passes of an even number of r-gather sweeps on one rank add s_k and s_{k+1} to x in sweeps
+ *                    0, 2, ... -- s_{k+1} from the r_{k+1} the sweep holds in registers, no r_{k-1} re-read; 0: x = (x + s_{k-1}) + s_k in
+ *                    sweeps 1, 3, ....  Same bits) pat_close (1: the last sweep of a post-smoothing pass whose residual nobody reads --
+ *                    the final post pass of levels >= 1, and of level 0 in a one-cycle, non-verbose preconditioner application -- is
+ *                    not run; per-sweep passes need pat_xnext, one-launch passes stop one sweep early.  Same bits in x; 0: every sweep)
  *                    pat_defer (1) pat_dinv (1) pat_emit (1) pat_nb (0 = auto) pat_rb (3) pat_un (9) pat_wgs (2048) pat_batched (1)
  *                    pat_small_wpb (4) pat_small_wpb2 (2) pat_wide (1) pat_wide_lds (73728) pat_wide_rounds (1) one_gather (1)
  *                    sell_un (6) sell_block (0 = auto) sell_defer (1) nt (1) nt_rowwise (1) big_rows (4000000) xcd_remap (1)
@@ -237,6 +242,9 @@ GMG_API int gmg_set_options(gmg_handle_t h, int mode, int cycle, int maxiter, do
  *                    sells_boxsweep_kernel; 2: every level that qualifies; 0: off) pat_box_t (0: planes per chain from the level's size)
  *   reductions       red_fused (1: inside CG the second stage of every dot is done by the kernel that consumes the scalar and the
  *                    norm is reduced + posted to the host by one launch; 0: one reduce launch per dot.  Same bits either way)
+ *                    cg_split* (0: measured equal, profiles/xnext_ab_128.md; where red_fused applies: 1 = CG's x += alpha p runs in a kernel of its own behind the launch that posts
+ *                    the residual norm -- cg_update_r_kernel, cg_update_x_kernel -- and the stream is synchronised once at the end of
+ *                    the outermost solve; 0 = one cg_update_kernel.  Same bits either way)
  *                    gmres_fused* (1: where red_fused applies, a GMRES Arnoldi column runs as gmres_mgs_kernel launches -- each sums the
  *                    previous dot's partials, subtracts the projection and accumulates the next dot's partials in one pass -- and
  *                    gmres_normalize_kernel, the solution update as one gmres_combine_kernel; 0: a dot, a reduce and an axmy launch

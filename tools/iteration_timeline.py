@@ -9,16 +9,18 @@ con = sqlite3.connect(f[0])
 rows = con.execute("select start, end, grid_x, name from kernels order by start").fetchall()
 marks = [i for i, r in enumerate(rows) if "reduce_post_kernel" in r[3]]
 which = int(sys.argv[2]) if len(sys.argv) > 2 else 12
-# segments between two norms that hold a whole V-cycle (>= 20 sweep launches), counted from the end
-segs = [(marks[i], marks[i + 1]) for i in range(len(marks) - 1) if sum("sweep_kernel" in r[3] for r in rows[marks[i] + 1:marks[i + 1] + 1]) >= 20]
+# segments between two norms that hold a whole V-cycle (>= 19 finest sweep launches: 10 + 10, or 10 + 9 with pat_close), counted from the end
+segs = [(marks[i], marks[i + 1]) for i in range(len(marks) - 1) if sum("sweep_kernel" in r[3] for r in rows[marks[i] + 1:marks[i + 1] + 1]) >= 19]
 if len(sys.argv) <= 2:
     # default: the last iteration whose launches are not bracketed by the bench's own HIP events (gmg_profile_enable: two bubbles of
     # ~5.7 us per sampled launch -- bench.py's per-level profiling runs at the end of the trace, every prof_stride-th finest sweep
-    # of the timed solves): no idle gap above 2.5 us after the first launch
+    # of the timed solves): no idle gap above 2.5 us after the first sweep launch (with cg_split the host's round trip for the norm
+    # sits behind cg_update_x_kernel, in front of the first sweep)
     for w in range(8, len(segs)):
         a_, b_ = segs[-w]
         seq = rows[a_ + 1:b_ + 1]
-        if all(seq[i][0] - seq[i - 1][1] < 2500 for i in range(1, len(seq))):
+        i0 = next(i for i, r in enumerate(seq) if "sweep_kernel" in r[3]) + 1
+        if all(seq[i][0] - seq[i - 1][1] < 2500 for i in range(i0, len(seq))):
             which = w
             break
 a, b = segs[-which]
