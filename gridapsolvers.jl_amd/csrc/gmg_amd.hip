@@ -332,6 +332,17 @@ struct DevCSR {
     std::vsnprintf(op_sig, sizeof(op_sig), fmt, ap);
     va_end(ap);
   }
+  // the one-launch smoothing pass first launched on this operator (sells_smooth_kernel and its template arguments): appended to
+  // gmg_sweep_signature's answer, so that a test can assert which instantiation it exercised
+  mutable char smooth_sig[80] = {0};
+  void note_smooth(const char *fmt, ...) const __attribute__((format(printf, 2, 3)))
+  {
+    if (smooth_sig[0]) return;
+    va_list ap;
+    va_start(ap, fmt);
+    std::vsnprintf(smooth_sig, sizeof(smooth_sig), fmt, ap);
+    va_end(ap);
+  }
   bool present() const { return rowptr != nullptr; }
 };
 
@@ -761,6 +772,7 @@ struct gmg_solver {
   int pat_strict = 1;   // GMG_PAT_STRICT: fused sweeps keep the per-entry mask (exact zero products even for non-finite vectors); 0 = 8-byte table entries, 2-3 % faster
   int persist_wpb_min = 1;   // GMG_PERSIST_WPB: smallest workgroup (in waves) of a one-launch pass
   int persist = 1;      // GMG_PERSIST: small levels run a whole smoothing pass in one launch (sells_smooth_kernel)
+  int persist_regs = 1;  // GMG_PERSIST_REGS: one-launch passes of 9- / 27-point operators with a compile-time run count (sells_smooth_kernel<NR>)
   int persist_fenced = 0; // GMG_PERSIST_FENCED: progress words published with release / polled with acquire semantics (agent scope)
   int persist_max_slices = 0;  // GMG_PERSIST_MAX_SLICES (0: what one workgroup per CU holds)
   int n_cus = 0;
@@ -3182,14 +3194,28 @@ struct gmg_solver {
     const bool mk = pat_strict || !M.ptab8;
     const bool prof = (l == prof_level) && prof_used + 2 <= prof_ev.size();       // every pass: there are niter times fewer of them
     if (prof) HIP_CHECK(hipEventRecord(prof_ev[prof_used], stream));
+    // persist_regs: the run count as a compile-time constant (9- and 27-point operators) -- one load round trip per sweep; which
+    // (NS, MK, NR) exist is smooth_nr_form's answer (kernels.hpp), everything else keeps the runtime run count body
+    const int nr = persist_regs && smooth_nr_form(ns, mk, M.pat_nruns) ? M.pat_nruns : 0;
+    M.note_smooth("sells_smooth_kernel<NS=%d,TD=%d,MK=%d,NR=%d> wgs=%d wpb=%d", ns, td ? 1 : 0, mk ? 1 : 0, nr, nwg, wpb);
+#define GMG_SMOOTH_LAUNCH_MK(NSV, TDV, MKV, NRV)                                                               \
+    do {                                                                                                         \
+      if constexpr (NRV == 0 || smooth_nr_form(NSV, MKV, NRV))                                                   \
+        hipLaunchKernelGGL((sells_smooth_kernel<NSV, TDV, MKV, 0, NRV>), g, b, lds, stream, a);                  \
+    } while (0)
+#define GMG_SMOOTH_LAUNCH_NR(NSV, TDV, NRV)                                                                    \
+    do { if (mk) GMG_SMOOTH_LAUNCH_MK(NSV, TDV, true, NRV); else GMG_SMOOTH_LAUNCH_MK(NSV, TDV, false, NRV); } while (0)
 #define GMG_SMOOTH_LAUNCH(NSV, TDV)                                                                            \
     do {                                                                                                         \
-      if (mk) hipLaunchKernelGGL((sells_smooth_kernel<NSV, TDV, true>), g, b, lds, stream, a);                   \
-      else hipLaunchKernelGGL((sells_smooth_kernel<NSV, TDV, false>), g, b, lds, stream, a);                     \
+      if (nr == 9) GMG_SMOOTH_LAUNCH_NR(NSV, TDV, 9);                                                            \
+      else if (nr == 3) GMG_SMOOTH_LAUNCH_NR(NSV, TDV, 3);                                                       \
+      else GMG_SMOOTH_LAUNCH_NR(NSV, TDV, 0);                                                                    \
     } while (0)
     if (ns == 2) { if (td) GMG_SMOOTH_LAUNCH(2, true); else GMG_SMOOTH_LAUNCH(2, false); }
     else { if (td) GMG_SMOOTH_LAUNCH(1, true); else GMG_SMOOTH_LAUNCH(1, false); }
 #undef GMG_SMOOTH_LAUNCH
+#undef GMG_SMOOTH_LAUNCH_NR
+#undef GMG_SMOOTH_LAUNCH_MK
     HIP_CHECK(hipGetLastError());
     if (prof) {
       HIP_CHECK(hipEventRecord(prof_ev[prof_used + 1], stream));
@@ -4113,6 +4139,9 @@ struct gmg_solver {
     // (sc1) atomics, the publishing lane stores the word after the workgroup's s_waitcnt vmcnt(0) + barrier, the polling lanes read
     // it with agent-scope loads and a barrier precedes the gathers.  Off by default, kept as a switch.
     persist_fenced = opt_int("GMG_PERSIST_FENCED", 0);
+    // run offsets, gather indices and (one slice per wave) coefficients in registers, all gathers of a sweep in flight at once; 0: the
+    // runtime run count body, which re-reads the offsets and gathers three runs at a time (bit-identical: profiles/smooth_chain_mb.txt)
+    persist_regs = opt_int("GMG_PERSIST_REGS", 1);
     pat_strict = opt_int("GMG_PAT_STRICT", 1);
     pat_wide = opt_int("GMG_PAT_WIDE", 1);
     pat_tile = opt_int("GMG_PAT_TILE", 0);
@@ -6857,7 +6886,7 @@ const OptionKey kOptionKeys[] = {
   {"GMG_PAT_RB", false}, {"GMG_PAT_RSWEEP", false}, {"GMG_PAT_SHARED", false}, {"GMG_PAT_SMALL_WPB", false}, {"GMG_PAT_SMALL_WPB2", false},
   {"GMG_PAT_STRICT", false}, {"GMG_PAT_TILE", false}, {"GMG_PAT_TILE_LDS", false}, {"GMG_PAT_TILE_MIN", false}, {"GMG_PAT_TILE_ROWS", false},
   {"GMG_PAT_TILE_T", false}, {"GMG_PAT_UN", false}, {"GMG_PAT_WGS", false}, {"GMG_PAT_WIDE", false}, {"GMG_PAT_WIDE_LDS", false},
-  {"GMG_PAT_WIDE_ROUNDS", false}, {"GMG_PERSIST", false}, {"GMG_PERSIST_FENCED", false}, {"GMG_PERSIST_MAX_SLICES", false},
+  {"GMG_PAT_WIDE_ROUNDS", false}, {"GMG_PERSIST", false}, {"GMG_PERSIST_FENCED", false}, {"GMG_PERSIST_MAX_SLICES", false}, {"GMG_PERSIST_REGS", false},
   {"GMG_PERSIST_SHARED", false}, {"GMG_PROF_STRIDE", true}, {"GMG_REFRESH", true}, {"GMG_SELL", false}, {"GMG_SELL_BLOCK", false},
   {"GMG_SELL_DEFER", false}, {"GMG_SELL_MAXPAD", false}, {"GMG_SELL_UN", false}, {"GMG_SETUP_TIMING", true}, {"GMG_VDICT", false},
   {"GMG_XCD_REMAP", false}, {"GMG_XCD_REMAP_BIG", false}, {"GMG_X0_ZERO", true}, {"GMG_HOST_POLL", true}, {"GMG_HOST_CHUNK_BYTES", true}, {"GMG_PAT_FMA", false}, {"GMG_PAT_R2", false}, {"GMG_RED_FUSED", false}, {"GMG_GMRES_FUSED", true}, {"GMG_NULLSPACE_FUSED", true}, {"GMG_PAT_R2MV", false}, {"GMG_PAT_R2_OCC", false}, {"GMG_PAT_PAIR_P", false}, {"GMG_PAT_R2MV_DOT", false}, {"GMG_PERSIST_WPB", false}, {"GMG_HOST_TIMELINE", true}, {"GMG_PAT_R2MV_MIN", false}, {"GMG_PAT_BCAST", false}, {"GMG_PAT_R2_WGS", false}, {"GMG_PAT_ZWALK", false}, {"GMG_PAT_ZWALK_T", false}, {"GMG_PAT_ZWALK_ROWS", false}, {"GMG_PAT_ZWALK_MV", false}, {"GMG_PAT_ZWALK_WIDE", false}, {"GMG_PAT_ZWALK_WIDE_ROWS", false}, {"GMG_PAT_FUSE2", false}, {"GMG_PAT_FUSE2_W", false}, {"GMG_PAT_FUSE2_T", false}, {"GMG_PAT_FUSE2_ROWS", false}, {"GMG_PAT_FUSE2_BOX", false}, {"GMG_PAT_BOX", false}, {"GMG_PAT_WIDE_GRID", false}, {"GMG_PAT_BOX_T", false}, {"GMG_PAT_BOX_MIN_ROWS", false}, {"GMG_PAT_BOX_MAX_ROWS", false},
@@ -7817,7 +7846,9 @@ int gmg_sweep_signature(gmg_handle_t h, int lev, char *buf, int cap)
     REQUIRE(!h->inactive(lev), GMG_ERR_STATE, "this rank holds no part of that level (it lives on a rank subset, gmg_set_redistribution)");
     REQUIRE(buf && cap > 0, GMG_ERR_INVALID, "null buffer");
     const DevCSR &A = h->lev[lev].A;
-    std::snprintf(buf, (size_t)cap, "%s", A.sweep_sig[0] ? A.sweep_sig : A.op_sig);
+    const char *sig = A.sweep_sig[0] ? A.sweep_sig : A.op_sig;
+    if (A.smooth_sig[0]) std::snprintf(buf, (size_t)cap, "%s%s%s", sig, sig[0] ? " + " : "", A.smooth_sig);
+    else std::snprintf(buf, (size_t)cap, "%s", sig);
   });
 }
 

@@ -3274,12 +3274,30 @@ __device__ __forceinline__ void st_agent(double *p, double v)
 
 // DBG (tools/mb_smooth.hip only, never instantiated by the library): 1 no neighbour waits, 2 plain gather loads, 4 plain s stores,
 // 8 no taps, 16 no store drain / flag publish
-template <int NS, bool TD, bool MK, int DBG = 0>
+//
+// NR = 9 / 3 (27- and 9-point operators; the launcher's persist_regs): the run count is a compile-time constant and a sweep costs ONE
+// load round trip.  With a runtime run count (NR = 0) the `memory` clobber of the store drain and the barriers make every sweep
+// re-read the run offsets (a vector load), wait, form the addresses, gather three runs, wait, tap -- three times over: six dependent
+// memory latencies, plus 27 LDS coefficient reads per row.  Here the run offsets are read once into scalar registers, the clamped
+// gather indices min(max(row + off, 0), last) are formed once before the sweep loop (only the base pointer alternates), all NR (x NS)
+// gathers of a sweep are issued back to back behind the post-poll barrier, and with NS = 1 the row's 3 NR coefficients are copied
+// from the LDS table into registers once (NS = 2 would need 2 x 54 registers for them: it keeps reading the table).  Same taps in
+// the same order on the same values: bit-identical to NR = 0.  The masked redo and everything between two hand-offs' ends -- the
+// drain, the barrier, the flag store, the polls -- are those of NR = 0, statement for statement.
+// Registers (gfx950, -O3, no scratch in any of them; the limit is 128 for a 1024-thread workgroup), MK = 1 / MK = 0:
+//   NS = 1:  NR = 0  42 / 40    NR = 3  58 / 48    NR = 9  110 / 108
+//   NS = 2:  NR = 0  58 / 56    NR = 3  64 / 78    NR = 9  110 / not instantiated: without the masked redo's branch between the two
+//            slices the scheduler issues all 2 x 27 table reads at once -- 128 registers and 196 B of scratch; the launcher keeps NR = 0
+constexpr bool smooth_nr_form(int ns, bool mk, int nruns) { return (nruns == 9 || nruns == 3) && !(ns == 2 && !mk && nruns == 9); }
+template <int NS, bool TD, bool MK, int DBG = 0, int NR = 0>
 __global__ __launch_bounds__(1024) void sells_smooth_kernel(SellSmoothArgs a)
 {
   constexpr int K = 3, ROWS = 65 - K, RB = 3;
+  static_assert(NR == 0 || DBG == 0, "the ablations are those of the runtime-nruns body");
+  static_assert(NR == 0 || smooth_nr_form(NS, MK, NR), "see the register table: the launcher keeps NR = 0 there");
+  constexpr bool CREG = NR > 0 && NS == 1;                   // the row's coefficients live in registers
   extern __shared__ double sp_smem[];
-  const int nu = K * a.nruns;
+  const int nu = NR > 0 ? K * NR : K * a.nruns;
   const int tot = a.np * nu;
   // [np*nu] coefficients, dense (absent entries hold 0.0) | strict form (MK): [np*nu] high-word masks behind them, read only by a
   // slice whose sum came out non-finite (see sells_r2sweep_kernel: "all sums finite" proves that no mask was needed)
@@ -3316,6 +3334,23 @@ __global__ __launch_bounds__(1024) void sells_smooth_kernel(SellSmoothArgs a)
 #pragma unroll
     for (int i = 0; i < NS; ++i) dv[i] = s_dinv[pid[i]];
   }
+  // NR form: what a sweep needs besides the gathered values is loop-invariant
+  int gi[NR > 0 ? NS : 1][NR > 0 ? NR : 1];
+  double cf[CREG ? K * NR : 1];
+  if constexpr (NR > 0) {
+    int roff[NR];
+#pragma unroll
+    for (int q = 0; q < NR; ++q) roff[q] = __builtin_amdgcn_readfirstlane(a.run_off[q]);
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+#pragma unroll
+      for (int q = 0; q < NR; ++q) gi[i][q] = min(max(row[i] + roff[q], 0), last);
+    }
+    if constexpr (CREG) {
+#pragma unroll
+      for (int j = 0; j < K * NR; ++j) cf[j] = s_tab8[pid[0] * nu + j];
+    }
+  }
   const double *sin = a.s_a;
   double *sout = a.s_b;
   const int nb_lo = max(0, w - a.halo_wg), nb_hi = min((int)gridDim.x - 1, w + a.halo_wg);
@@ -3345,30 +3380,54 @@ __global__ __launch_bounds__(1024) void sells_smooth_kernel(SellSmoothArgs a)
       __syncthreads();
     }
     double acc[NS];
+    double G[NR > 0 ? NS : 1][NR > 0 ? NR : 1];
+    if constexpr (NR > 0) {                                  // every gather of the sweep in flight before the first tap
+#pragma unroll
+      for (int i = 0; i < NS; ++i) {
+#pragma unroll
+        for (int q = 0; q < NR; ++q) G[i][q] = ld_agent(sin + gi[i][q]);
+      }
+      __builtin_amdgcn_sched_barrier(0);                     // (or the scheduler sinks the last gathers below the first taps' waits)
+    }
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
-      double A[RB];
-#pragma unroll
-      for (int q = 0; q < RB; ++q) { const double *ga = sin + min(max(row[i] + a.run_off[q], 0), last); A[q] = (DBG & 2) ? *ga : ld_agent(ga); }
       const uint32_t *tm = s_msk + pid[i] * nu;
       const double *tv = s_tab8 + pid[i] * nu;
       double s = 0.0;
-      for (int r0 = 0; r0 < ((DBG & 8) ? RB : a.nruns); r0 += RB) {
-        double cur[RB];
+      if constexpr (NR > 0) {
 #pragma unroll
-        for (int q = 0; q < RB; ++q) cur[q] = A[q];
-        if (r0 + RB < a.nruns) {
-#pragma unroll
-          for (int q = 0; q < RB; ++q) { const double *ga = sin + min(max(row[i] + a.run_off[r0 + RB + q], 0), last); A[q] = (DBG & 2) ? *ga : ld_agent(ga); }
-        }
-#pragma unroll
-        for (int q = 0; q < RB; ++q) {
-          double c = cur[q];
+        for (int q = 0; q < NR; ++q) {
+          double c = G[i][q];
 #pragma unroll
           for (int t = 0; t < K; ++t) {
             if (t > 0) c = wave_shl1(c);
-            const int j = (r0 + q) * K + t;
-            s = s + tv[j] * c;
+            const int j = q * K + t;
+            double cj;
+            if constexpr (CREG) cj = cf[j]; else cj = tv[j];
+            s = s + cj * c;
+          }
+        }
+      } else {
+        double A[RB];
+#pragma unroll
+        for (int q = 0; q < RB; ++q) { const double *ga = sin + min(max(row[i] + a.run_off[q], 0), last); A[q] = (DBG & 2) ? *ga : ld_agent(ga); }
+        for (int r0 = 0; r0 < ((DBG & 8) ? RB : a.nruns); r0 += RB) {
+          double cur[RB];
+#pragma unroll
+          for (int q = 0; q < RB; ++q) cur[q] = A[q];
+          if (r0 + RB < a.nruns) {
+#pragma unroll
+            for (int q = 0; q < RB; ++q) { const double *ga = sin + min(max(row[i] + a.run_off[r0 + RB + q], 0), last); A[q] = (DBG & 2) ? *ga : ld_agent(ga); }
+          }
+#pragma unroll
+          for (int q = 0; q < RB; ++q) {
+            double c = cur[q];
+#pragma unroll
+            for (int t = 0; t < K; ++t) {
+              if (t > 0) c = wave_shl1(c);
+              const int j = (r0 + q) * K + t;
+              s = s + tv[j] * c;
+            }
           }
         }
       }

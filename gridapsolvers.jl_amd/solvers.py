@@ -749,8 +749,8 @@ class GMGNumericalSetup:
                     value_dictionary=bool(b.value), idx16=bool(c.value), stream_bytes_per_nnz=d.value, padding=e.value)
 
     def sweep_signature(self, lev=0):
-        buf = C.create_string_buffer(128)
-        abi.check(self.h, self._lib.gmg_sweep_signature(self.h, lev, buf, 128))
+        buf = C.create_string_buffer(256)
+        abi.check(self.h, self._lib.gmg_sweep_signature(self.h, lev, buf, 256))
         return buf.value.decode()
 
     def device_bytes(self):

@@ -254,7 +254,10 @@ GMG_API int gmg_set_options(gmg_handle_t h, int mode, int cycle, int maxiter, do
  *                    nullspace_project_kernel, and make_orthogonal! / Gram-Schmidt chain nullspace_mgs_kernel; 0: a dot per
  *                    vector, axpy_kernel / axmy_dev_kernel per term.  Same bits either way)
  *   one-launch pass  persist (1) persist_fenced (0) persist_max_slices (0 = one workgroup per CU) persist_shared (0)
- *                    persist_wpb (1: smallest workgroup, in waves)
+ *                    persist_wpb (1: smallest workgroup, in waves) persist_regs (1: passes of 9- / 27-point operators run
+ *                    sells_smooth_kernel with a compile-time run count -- run offsets, gather indices and, at one slice per wave, the
+ *                    row's coefficients in registers, one load round trip per sweep; 0 = the runtime run count body.  Same bits either
+ *                    way; gmg_sweep_signature names the instantiation that ran)
  *   coarsest level   coarse_host_max (1500) coarse_host_fallback_max (6000) coarse_auto_cg_min (20000: a dense-inverse request on a
  *                    coarsest level of at least this many dofs is served by the device CG-Jacobi solver instead) gj_mfma (1) gj_wide_min (4096)
  *   patch smoother   patch_dedup (1) patch_source_dedup (1) patch_operator (1)

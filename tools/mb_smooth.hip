@@ -88,6 +88,13 @@ int main(int argc, char **argv)
     printf("%-58s %8.2f us per launch  %6.2f us per sweep%s\n", label, ms * 1e3, ms * 1e3 / niter, e ? "  (TIMEOUT FLAG SET)" : ""); \
   } while (0)
   RUN(0, "product kernel (relaxed progress words)");
+  if (ns <= 2) {   // the compile-time run count form (persist_regs): run offsets, gather indices and (one slice per wave) coefficients in registers
+    const float ms = time_it([&] { a.epoch = epoch; epoch += niter;
+      if (ns == 1) hipLaunchKernelGGL((sells_smooth_kernel<1, true, true, 0, 9>), g, b, lds, 0, a);
+      else hipLaunchKernelGGL((sells_smooth_kernel<2, true, true, 0, 9>), g, b, lds, 0, a); });
+    uint32_t e = 0; CK(hipMemcpy(&e, err, 4, hipMemcpyDeviceToHost));
+    printf("%-58s %8.2f us per launch  %6.2f us per sweep%s\n", "product kernel, NR = 9: one load round trip per sweep", ms * 1e3, ms * 1e3 / niter, e ? "  (TIMEOUT FLAG SET)" : "");
+  }
   a.fenced = 1;
   RUN(0, "product kernel, release / acquire progress words");
   a.fenced = 0;
