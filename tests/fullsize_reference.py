@@ -102,13 +102,15 @@ def fma_taps(sig):
     return "FM=1" in sig
 
 
-def check_rows(y_rows, cols, vals, lengths, x, sig, what):
+def check_rows(y_rows, cols, vals, lengths, x, sig, what, bound_only=False, reference=None):
     """Device values of sampled rows against the row reference: bit for bit with the CSR-order sum when the level's kernels round
     products and sums separately (FM=0 in the signature), and within the bound in every case.  Returns the largest deviation from
-    the exact value as a fraction of the bound (and in ulps of the exact value)."""
-    seq, exact, bound = row_reference(cols, vals, lengths, x)
+    the exact value as a fraction of the bound (and in ulps of the exact value).
+    bound_only: the bound alone (a layout that sums a row in another order, such as the lane tree of the CSR-stream kernel);
+    reference: (seq, exact, bound) of these rows when the caller has them already."""
+    seq, exact, bound = row_reference(cols, vals, lengths, x) if reference is None else reference
     y_rows = np.asarray(y_rows, dtype=np.float64)
-    if not fma_taps(sig):
+    if not fma_taps(sig) and not bound_only:
         bad = np.nonzero(y_rows != seq)[0]
         assert bad.size == 0, f"{what} [{sig}]: {bad.size} of {y_rows.size} sampled rows differ from the CSR-order sum " \
                               f"(first at sample {bad[0]}: {y_rows[bad[0]]!r} vs {seq[bad[0]]!r})"
