@@ -480,6 +480,12 @@ struct Level {
   uint32_t *pflags = nullptr;     // persistent smoothing pass (sells_smooth_kernel): one progress word per workgroup, 64 B apart
   int pf_nwg = 0;
   uint32_t pf_epoch = 1;
+  // a transfer handed to the next one-launch pass of this level as its head (option persist_fold): 1 = the restriction that forms this
+  // level's residual (from fold_src, the finer level's r), 2 = the prolongation + correction + residual update (from fold_src, the
+  // coarser level's x).  Set by cycle(), taken by the smooth() call that follows.  fold_ran: which of them have run (gmg_sweep_signature)
+  int fold_pending = 0;
+  const double *fold_src = nullptr;
+  int fold_ran = 0;
   double *dx = nullptr;
   double *rcur = nullptr;         // buffer holding the current residual after a cycle
 };
@@ -773,6 +779,7 @@ struct gmg_solver {
   int persist_wpb_min = 1;   // GMG_PERSIST_WPB: smallest workgroup (in waves) of a one-launch pass
   int persist = 1;      // GMG_PERSIST: small levels run a whole smoothing pass in one launch (sells_smooth_kernel)
   int persist_regs = 1;  // GMG_PERSIST_REGS: one-launch passes of 9- / 27-point operators with a compile-time run count (sells_smooth_kernel<NR>)
+  int persist_fold = 7;  // GMG_PERSIST_FOLD: transfers run as the head of the one-launch pass they feed -- 1 restrictions, 2 prolongation + correction + r -= A dx, 4 also the restriction from a level that is not a one-launch level itself
   int persist_fenced = 0; // GMG_PERSIST_FENCED: progress words published with release / polled with acquire semantics (agent scope)
   int persist_max_slices = 0;  // GMG_PERSIST_MAX_SLICES (0: what one workgroup per CU holds)
   int n_cus = 0;
@@ -3122,11 +3129,21 @@ struct gmg_solver {
   void free_pattern(DevCSR &M);
   void patch_precond(Level &L, Smoother &S, const double *r, double omega, bool relax, double *dx, double *x);
 
+  // May the transfer T in front of the pass S of level l run as that pass's head?  One rank, a Jacobi pass that runs as one launch
+  // with T's table next to its own in LDS (T in the per-lane pattern form, its table in the LDS form).
+  bool fold_level(int l, const Smoother &S, const DevCSR &T)
+  {
+    if (!persist_fold || comm.nranks != 1 || S.kind != SM_JACOBI || !one_gather() || S.niter < 2) return false;
+    return smooth_persistent(l, S, nullptr, nullptr, nullptr, false, S.niter, true, false, 1, &T, nullptr);
+  }
   // One launch for the whole pass on small single-GPU levels in the shared-offset pattern form (see sells_smooth_kernel).
   // s_0 is in L.sbuf[0].  Returns false when the level does not qualify (the caller then runs sweep by sweep).
   // dry = true: only answer whether the pass WOULD run as one launch (nothing is allocated or launched)
   // close: the pass's residual has no reader -- the kernel stops one sweep early and adds the pending increment to x (r_out is not written)
-  bool smooth_persistent(int l, const Smoother &S, double *x, const double *r_in, double *r_out, bool x_zero, int niter, bool dry = false, bool close = false)
+  // fold / T / fsrc: the transfer T applied to fsrc runs as the head of the pass (1 restriction, 2 prolongation + correction, see
+  // SellSmoothArgs); its table goes to LDS behind the pass's own, a pass whose tables do not fit together is no one-launch pass
+  bool smooth_persistent(int l, const Smoother &S, double *x, const double *r_in, double *r_out, bool x_zero, int niter, bool dry = false, bool close = false,
+                         int fold = 0, const DevCSR *T = nullptr, const double *fsrc = nullptr)
   {
     Level &L = lev[l];
     const DevCSR &M = L.A;
@@ -3134,7 +3151,12 @@ struct gmg_solver {
     if (!persist || (comm.nranks > 1 && L.halo.present && !L.halo.ovl) || niter < 2) return false;
     if (!(M.sell && M.pat && M.pat_shared && !M.pat_coded && M.pat_k == 3 && M.pat_nruns % 3 == 0)) return false;
     const int nu = M.pat_k * M.pat_nruns;
-    const size_t lds = (size_t)M.pat_np * nu * 16 + (size_t)M.pat_np * 8 + 16;
+    const size_t lds_own = (size_t)M.pat_np * nu * 16 + (size_t)M.pat_np * 8 + 16;
+    size_t lds = lds_own;
+    if (fold) {
+      if (!(T && T->pat && T->sell && T->pat_generic && !T->pat_shared && T->plen && T->ppoff && T->ppval && T->nrows == M.nrows && T->pat_w > 0)) return false;
+      lds += ((size_t)T->pat_np * T->pat_w * 12 + (size_t)T->pat_np * 4 + 7) / 8 * 8;
+    }
     if (lds > 64 * 1024) return false;
     if (n_cus <= 0) {
       hipDeviceProp_t prop;
@@ -3188,7 +3210,12 @@ struct gmg_solver {
     a.niter = niter; a.x_zero = x_zero ? 1 : 0; a.close = close && niter >= 2 ? 1 : 0;
     a.r_in = r_in; a.r_out = r_out; a.x = x; a.s_a = L.sbuf[0]; a.s_b = L.sbuf[1];
     a.flags = L.pflags; a.epoch = L.pf_epoch; a.err = d_perr; a.err_dev = d_perr_dev; a.halo_wg = halo; a.fenced = persist_fenced;
-    L.pf_epoch += (uint32_t)niter;
+    if (fold) {
+      a.fold = fold; a.f_rowpid = T->rowpid; a.f_rowbase = T->rowbase; a.f_plen = T->plen; a.f_poff = T->ppoff; a.f_pval = T->ppval;
+      a.f_np = T->pat_np; a.f_W = T->pat_w; a.f_lds = (int)(lds_own / 8); a.f_x = fsrc; a.f_omega = 0.0;
+      L.fold_ran |= fold;
+    }
+    L.pf_epoch += (uint32_t)niter + (fold ? 1u : 0u);         // the publications the launch can make
     const dim3 g(nwg), b(64 * wpb);
     const bool td = a.pdinv != nullptr;
     const bool mk = pat_strict || !M.ptab8;
@@ -3276,6 +3303,7 @@ struct gmg_solver {
     if (again) {
       persist_tripped = false;
       ++persist_retries;
+      for (Level &Lf : lev) { Lf.fold_pending = 0; Lf.fold_src = nullptr; }   // (the solve may have been left between a cycle's steps)
       HIP_CHECK(hipStreamSynchronize(stream));
       if (inplace) copy(x_user, scratch_vec(6, lev[0].nvec), n);
       pending_out.clear();
@@ -3327,6 +3355,12 @@ struct gmg_solver {
     r_dead = r_dead && pat_close && comm.nranks == 1;
     const int64_t n = L.n;
     const bool r_internal = (r_in == L.rbuf[0] || r_in == L.rbuf[1]);
+    // the transfer cycle() left to this pass (fold_level said the pass runs as one launch: anything else below is a bug, not a fallback)
+    const int fold = L.fold_pending;
+    const double *fold_src = L.fold_src;
+    L.fold_pending = 0; L.fold_src = nullptr;
+    const DevCSR *fold_T = fold == 1 ? &lev[l - 1].R : fold == 2 ? &L.P : nullptr;
+    REQUIRE(!fold || (S.kind == SM_JACOBI && one_gather() && r_internal && fold_level(l, S, *fold_T)), GMG_ERR_STATE, "a folded transfer met a pass that does not run as one launch");
     if (S.niter <= 0) {
       if (x_zero) zero(x, n);
       if (!r_internal) { copy(L.rbuf[0], r_in, n); return L.rbuf[0]; }
@@ -3356,7 +3390,15 @@ struct gmg_solver {
           exchange(l, out);
         }
         const bool xz0 = x_zero && first;
-        const bool one_launch = smooth_persistent(l, S, x, cur, out, xz0, nb, true);
+        const bool one_launch = smooth_persistent(l, S, x, cur, out, xz0, nb, true, false, fold, fold_T, fold_src);
+        if (fold) {
+          // the head of the launch forms s_0 (and, for a restriction, r) itself: no s_0 kernel, one launch or an error
+          L.s0_ready = false;
+          REQUIRE(one_launch && smooth_persistent(l, S, x, cur, out, xz0, nb, false, r_dead, fold, fold_T, fold_src), GMG_ERR_STATE,
+                  "a folded transfer met a pass that does not run as one launch");
+          cur = out;
+          continue;
+        }
         if (rsw && !one_launch) {
           // sweeps that gather r itself (uniform 1/diag): no s vector, no scaled-Jacobi launch; r ping-pongs between the level's
           // two residual buffers (the gathers read r_k while the rows write r_{k+1}), the result is wherever the last sweep wrote
@@ -3594,6 +3636,12 @@ struct gmg_solver {
         continue;
       }
       if (comm.nranks > 1 && l + 1 == rep_from) restrict_replicate(l, r, C.rbuf[0]);
+      else if (l + 1 < nlev - 1 && (persist_fold & 1) && !L.r_split && fold_level(l + 1, C.pre, L.R) &&
+               ((persist_fold & 4) || smooth_persistent(l, L.pre, nullptr, nullptr, nullptr, false, L.pre.niter, true))) {
+        // rH = R rh (:484) is the head of the child's pre-smoothing pass: C.rbuf[0] and its s_0 are not written
+        C.fold_pending = 1; C.fold_src = r;
+        C.s0_ready = false;
+      }
       else if (l + 1 < nlev - 1 && emits_s0(C, C.pre, L.R)) {
         StepTimer tm(*this, "restrict+s0", l);
         spmv_set(L.R, r, C.rbuf[0], C.sbuf[0], C.dinv, C.pre.omega);   // :484 rH = R rh (+ the child's first s)
@@ -3614,6 +3662,11 @@ struct gmg_solver {
         patch_precond(L, L.pcorr, L.ptmp, 1.0, false, L.pcor, nullptr);
         hipLaunchKernelGGL(prolong_correct_kernel, dim3(grid_for(L.n)), dim3(256), 0, stream, L.n, L.pcor, L.dx, x);
         HIP_CHECK(hipGetLastError());
+      } else if ((persist_fold & 2) && !ovl_l && fold_level(l, L.post, L.P)) {
+        // :491-496 dxh = P dxH ; xh += dxh ; rh -= Ah dxh are the head of the pass that follows (the W / F re-smooth or the
+        // post-smoother, both L.post): L.dx is not written
+        L.fold_pending = 2; L.fold_src = C.x;
+        continue;
       } else
       { StepTimer tm(*this, "prolong", l); spmv_addto(L.P, C.x, L.dx, x); }                       // :491,494 dxh = P dxH ; xh += dxh
       if (ovl_l && L.ovl_skip_dx && !L.has_pcorr) spmv_sub(L.A, L.dx, r);                            // (every local row; the pass that follows opens with consistent!(r))
@@ -4142,6 +4195,7 @@ struct gmg_solver {
     // run offsets, gather indices and (one slice per wave) coefficients in registers, all gathers of a sweep in flight at once; 0: the
     // runtime run count body, which re-reads the offsets and gathers three runs at a time (bit-identical: profiles/smooth_chain_mb.txt)
     persist_regs = opt_int("GMG_PERSIST_REGS", 1);
+    persist_fold = opt_int("GMG_PERSIST_FOLD", 7);
     pat_strict = opt_int("GMG_PAT_STRICT", 1);
     pat_wide = opt_int("GMG_PAT_WIDE", 1);
     pat_tile = opt_int("GMG_PAT_TILE", 0);
@@ -6886,7 +6940,7 @@ const OptionKey kOptionKeys[] = {
   {"GMG_PAT_RB", false}, {"GMG_PAT_RSWEEP", false}, {"GMG_PAT_SHARED", false}, {"GMG_PAT_SMALL_WPB", false}, {"GMG_PAT_SMALL_WPB2", false},
   {"GMG_PAT_STRICT", false}, {"GMG_PAT_TILE", false}, {"GMG_PAT_TILE_LDS", false}, {"GMG_PAT_TILE_MIN", false}, {"GMG_PAT_TILE_ROWS", false},
   {"GMG_PAT_TILE_T", false}, {"GMG_PAT_UN", false}, {"GMG_PAT_WGS", false}, {"GMG_PAT_WIDE", false}, {"GMG_PAT_WIDE_LDS", false},
-  {"GMG_PAT_WIDE_ROUNDS", false}, {"GMG_PERSIST", false}, {"GMG_PERSIST_FENCED", false}, {"GMG_PERSIST_MAX_SLICES", false}, {"GMG_PERSIST_REGS", false},
+  {"GMG_PAT_WIDE_ROUNDS", false}, {"GMG_PERSIST", false}, {"GMG_PERSIST_FENCED", false}, {"GMG_PERSIST_FOLD", false}, {"GMG_PERSIST_MAX_SLICES", false}, {"GMG_PERSIST_REGS", false},
   {"GMG_PERSIST_SHARED", false}, {"GMG_PROF_STRIDE", true}, {"GMG_REFRESH", true}, {"GMG_SELL", false}, {"GMG_SELL_BLOCK", false},
   {"GMG_SELL_DEFER", false}, {"GMG_SELL_MAXPAD", false}, {"GMG_SELL_UN", false}, {"GMG_SETUP_TIMING", true}, {"GMG_VDICT", false},
   {"GMG_XCD_REMAP", false}, {"GMG_XCD_REMAP_BIG", false}, {"GMG_X0_ZERO", true}, {"GMG_HOST_POLL", true}, {"GMG_HOST_CHUNK_BYTES", true}, {"GMG_PAT_FMA", false}, {"GMG_PAT_R2", false}, {"GMG_RED_FUSED", false}, {"GMG_GMRES_FUSED", true}, {"GMG_NULLSPACE_FUSED", true}, {"GMG_PAT_R2MV", false}, {"GMG_PAT_R2_OCC", false}, {"GMG_PAT_PAIR_P", false}, {"GMG_PAT_R2MV_DOT", false}, {"GMG_PERSIST_WPB", false}, {"GMG_HOST_TIMELINE", true}, {"GMG_PAT_R2MV_MIN", false}, {"GMG_PAT_BCAST", false}, {"GMG_PAT_R2_WGS", false}, {"GMG_PAT_ZWALK", false}, {"GMG_PAT_ZWALK_T", false}, {"GMG_PAT_ZWALK_ROWS", false}, {"GMG_PAT_ZWALK_MV", false}, {"GMG_PAT_ZWALK_WIDE", false}, {"GMG_PAT_ZWALK_WIDE_ROWS", false}, {"GMG_PAT_FUSE2", false}, {"GMG_PAT_FUSE2_W", false}, {"GMG_PAT_FUSE2_T", false}, {"GMG_PAT_FUSE2_ROWS", false}, {"GMG_PAT_FUSE2_BOX", false}, {"GMG_PAT_BOX", false}, {"GMG_PAT_WIDE_GRID", false}, {"GMG_PAT_BOX_T", false}, {"GMG_PAT_BOX_MIN_ROWS", false}, {"GMG_PAT_BOX_MAX_ROWS", false},
@@ -7847,7 +7901,8 @@ int gmg_sweep_signature(gmg_handle_t h, int lev, char *buf, int cap)
     REQUIRE(buf && cap > 0, GMG_ERR_INVALID, "null buffer");
     const DevCSR &A = h->lev[lev].A;
     const char *sig = A.sweep_sig[0] ? A.sweep_sig : A.op_sig;
-    if (A.smooth_sig[0]) std::snprintf(buf, (size_t)cap, "%s%s%s", sig, sig[0] ? " + " : "", A.smooth_sig);
+    const int fr = h->lev[lev].fold_ran;
+    if (A.smooth_sig[0]) std::snprintf(buf, (size_t)cap, "%s%s%s folds=%s", sig, sig[0] ? " + " : "", A.smooth_sig, fr == 3 ? "R+P" : fr == 1 ? "R" : fr == 2 ? "P" : "none");
     else std::snprintf(buf, (size_t)cap, "%s", sig);
   });
 }

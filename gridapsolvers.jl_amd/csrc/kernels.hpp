@@ -3261,6 +3261,18 @@ struct SellSmoothArgs {
   int fenced;               // progress words: release store / acquire after the poll (agent scope) on top of the explicit store drain
   uint32_t *err_dev;        // device-memory twin of *err (read at the end of the pass: a host-mapped word would cost a PCIe round trip)
   int close;                // the pass's r has no reader (niter >= 2): the last sweep's A s is not formed, x += s_{niter-1} from registers, r_out not written
+  // the transfer in front of the pass as its head (the launcher's persist_fold): a SELL-P operator in the per-lane pattern form
+  // (SellPArgs), its table staged into LDS behind the pass's own tables
+  int fold;                 // 0: none | 1: r = T f_x (restriction), s_0 = omega*(Dinv r) | 2: s = T f_x (prolongation), one more loop step
+  const uint16_t *f_rowpid;
+  const int32_t *f_rowbase; // or nullptr: offsets relative to the row index
+  const int32_t *f_plen;
+  const int32_t *f_poff;    // byte offsets
+  const double *f_pval;
+  int f_np, f_W;
+  int f_lds;                // where the table starts in LDS, in doubles
+  const double *f_x;        // the vector T gathers from: complete before the launch (plain loads)
+  double f_omega;           // fold == 2: s = f_omega != 0 ? f_omega * (T f_x) : T f_x, as sellp_kernel<EPI_ADDTO>
 };
 
 __device__ __forceinline__ double ld_agent(const double *p)
@@ -3270,6 +3282,29 @@ __device__ __forceinline__ double ld_agent(const double *p)
 __device__ __forceinline__ void st_agent(double *p, double v)
 {
   __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// One row of a folded transfer (sells_smooth_kernel's head): the row sum of sellp_kernel, entries left to right, FU gathers in flight
+// per round -- the offsets of a round are read from the LDS table first, its gathers issued back to back, the values read as they are
+// used.  Entries past the end of the row (or of the table row: W need not be a multiple of FU) are padding: (offset 0, value 0.0), the
+// high word of the gathered value cleared, so they add an exact +0.0.
+template <int FU>
+__device__ __forceinline__ double fold_row_sum(const double *tv, const int32_t *to, int W, int len, int lmax, uint32_t base8, const double *__restrict__ x)
+{
+  double s = 0.0;
+#pragma unroll 1
+  for (int j = 0; j < lmax; j += FU) {
+    double g[FU];
+#pragma unroll
+    for (int u = 0; u < FU; ++u) g[u] = ld_off(x, base8 + (uint32_t)to[min(j + u, W - 1)]);
+#pragma unroll
+    for (int u = 0; u < FU; ++u) {
+      double gu = g[u], vu = tv[min(j + u, W - 1)];
+      if (!(j + u < len)) { gu = __hiloint2double(0, __double2loint(gu)); vu = 0.0; }
+      s = s + vu * gu;
+    }
+  }
+  return s;
 }
 
 // DBG (tools/mb_smooth.hip only, never instantiated by the library): 1 no neighbour waits, 2 plain gather loads, 4 plain s stores,
@@ -3288,6 +3323,21 @@ __device__ __forceinline__ void st_agent(double *p, double v)
 //   NS = 1:  NR = 0  42 / 40    NR = 3  58 / 48    NR = 9  110 / 108
 //   NS = 2:  NR = 0  58 / 56    NR = 3  64 / 78    NR = 9  110 / not instantiated: without the masked redo's branch between the two
 //            slices the scheduler issues all 2 x 27 table reads at once -- 128 registers and 196 B of scratch; the launcher keeps NR = 0
+// With the folded head (a.fold, below) the peak of most instantiations is its round of 27 gathers, still without scratch:
+//   NS = 1:  NR = 0  88 / 88    NR = 3  88 / 88     NR = 9  128 / 128 (TD = 0: 126 / 126)
+//   NS = 2:  NR = 0  105 / 105  NR = 3  104 / 104   NR = 9  113 / not instantiated
+//
+// a.fold (the launcher's persist_fold): the transfer in front of the pass runs as its head instead of as launches of its own -- a
+// wave-uniform runtime branch, no further instantiations.  The workgroups own exactly the rows the transfer produces:
+//   1  restriction: r = R r_fine per owned row instead of the load of r_in, s_0 = omega*(Dinv r) -- what sellp_kernel<EPI_SET> and its
+//      s emission write; the level's r buffer and s_0 are never stored
+//   2  prolongation + correction + residual update: s = P dxH, then ONE MORE step of the loop -- x += s; r -= A s; s' = omega*(Dinv r)
+//      is dx = P dxH; x += dx; r -= A dx followed by the post pass's s_0 (sellp_kernel<EPI_ADDTO>, sells_kernel<EPI_SUB> with its s
+//      emission: the same taps in the same order, the same masked redo); dx is never stored
+// Either head is published like a sweep's s (s_a, drain, barrier, flag = epoch + 1), sweep 0 waits for the neighbours' heads, and all
+// later publications move up by one: a folded launch can make niter + 1 of them, which is what the launcher adds to the epoch.  The
+// gathered vector of the head was completed by an earlier kernel (plain loads).  Nothing but s_a / s_b is stored before the final
+// err_dev check: the time-out protocol is unchanged.
 constexpr bool smooth_nr_form(int ns, bool mk, int nruns) { return (nruns == 9 || nruns == 3) && !(ns == 2 && !mk && nruns == 9); }
 template <int NS, bool TD, bool MK, int DBG = 0, int NR = 0>
 __global__ __launch_bounds__(1024) void sells_smooth_kernel(SellSmoothArgs a)
@@ -3313,6 +3363,8 @@ __global__ __launch_bounds__(1024) void sells_smooth_kernel(SellSmoothArgs a)
   int pid[NS], row[NS];
   bool own[NS];
   double r[NS], xr[NS], so[NS], dv[NS];
+  int fpid[NS];                                              // folded transfer: the row's pattern and base column, requested with the
+  uint32_t fbase8[NS];                                       // row-wise loads of the pass
 #pragma unroll
   for (int i = 0; i < NS; ++i) {
     const int slice = w * (wpb * NS) + i * wpb + wave;
@@ -3320,20 +3372,62 @@ __global__ __launch_bounds__(1024) void sells_smooth_kernel(SellSmoothArgs a)
     own[i] = slice < a.nslices && lane < ROWS && row[i] <= lastrow;
     const int rc = min(row[i], lastrow);
     pid[i] = (int)a.rowpid[rc];
-    r[i] = a.r_in[rc];
+    r[i] = 0.0; so[i] = 0.0;
+    if (a.fold != 1) r[i] = a.r_in[rc];                      // (fold 1: r is formed below)
     { const double xl = a.x[rc]; xr[i] = a.x_zero ? 0.0 : xl; }
-    so[i] = a.s_a[rc];
+    if (!a.fold) so[i] = a.s_a[rc];
     dv[i] = TD ? 0.0 : a.dinv[rc];
+    fpid[i] = 0; fbase8[i] = 0u;
+    if (a.fold) { fpid[i] = (int)a.f_rowpid[rc]; fbase8[i] = 8u * (uint32_t)(a.f_rowbase ? a.f_rowbase[rc] : rc); }
   }
   if (MK) { for (int i = threadIdx.x; i < tot; i += blockDim.x) { const PatEntry en = a.tab[i]; s_tab8[i] = en.v; s_msk[i] = en.m; } }
   else { for (int i = threadIdx.x; i < tot; i += blockDim.x) s_tab8[i] = a.tab8[i]; }
   if (TD)
     for (int i = threadIdx.x; i < a.np; i += blockDim.x) s_dinv[i] = a.pdinv[i];
+  if (a.fold) {
+    const int ftot = a.f_np * a.f_W;
+    double *w_val = sp_smem + a.f_lds;
+    int32_t *w_off = reinterpret_cast<int32_t *>(w_val + ftot);
+    int32_t *w_len = w_off + ftot;
+    for (int i = threadIdx.x; i < ftot; i += blockDim.x) { w_val[i] = a.f_pval[i]; w_off[i] = a.f_poff[i]; }
+    for (int i = threadIdx.x; i < a.f_np; i += blockDim.x) w_len[i] = a.f_plen[i];
+  }
   __syncthreads();
   if (TD) {
 #pragma unroll
     for (int i = 0; i < NS; ++i) dv[i] = s_dinv[pid[i]];
   }
+  // Folded transfer (wave-uniform branch, before the NR form's registers become live): the rows of sellp_kernel, one per lane of the
+  // pass's own 62-row slices (the two halo lanes and the slices past the end compute a row they do not own and store nothing), see
+  // fold_row_sum.  Rows of up to 9 entries (prolongations) take one round of gathers, longer ones (restrictions) rounds of 27.
+  // The result is published like the s of a sweep -- s_a, drain, barrier, flag = epoch + 1 -- so every sweep's numbers move up by one.
+  if (a.fold) {
+    const int W = a.f_W;
+    const double *f_val = sp_smem + a.f_lds;
+    const int32_t *f_off = reinterpret_cast<const int32_t *>(f_val + a.f_np * W);
+    const int32_t *f_len = f_off + a.f_np * W;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      const int fp = fpid[i];
+      const int len = f_len[fp];
+      int lmax = len;                                        // longest row of the wave
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) lmax = max(lmax, __shfl_xor(lmax, o));
+      lmax = __builtin_amdgcn_readfirstlane(lmax);
+      const double s = lmax > 9 ? fold_row_sum<27>(f_val + fp * W, f_off + fp * W, W, len, lmax, fbase8[i], a.f_x)
+                                : fold_row_sum<9>(f_val + fp * W, f_off + fp * W, W, len, lmax, fbase8[i], a.f_x);
+      if (a.fold == 1) { r[i] = s; so[i] = omega * (dv[i] * s); }
+      else so[i] = a.f_omega != 0.0 ? a.f_omega * s : s;
+      if (own[i]) st_agent(a.s_a + row[i], so[i]);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      if (a.fenced) __hip_atomic_store(a.flags + (size_t)w * 16, a.epoch + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+      else __hip_atomic_store(a.flags + (size_t)w * 16, a.epoch + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  const uint32_t pb = a.fold ? 1u : 0u;                      // publications before sweep 0
   // NR form: what a sweep needs besides the gathered values is loop-invariant
   int gi[NR > 0 ? NS : 1][NR > 0 ? NR : 1];
   double cf[CREG ? K * NR : 1];
@@ -3359,13 +3453,14 @@ __global__ __launch_bounds__(1024) void sells_smooth_kernel(SellSmoothArgs a)
   // added.  The epoch still advances by niter per launch although the workgroups now publish epoch + niter - 2 at most: the words
   // only grow and are compared by signed difference, so the next launch (which waits for epoch + niter + k, k >= 1) just sees words
   // that are further behind -- exactly what it sees of a neighbour that has not started yet.
-  const int nk = a.close ? a.niter - 1 : a.niter;
+  // fold 2: the correction is one more step of the loop in front of the sweeps (x += s; r -= A s; s' = omega*(Dinv r) with s = P dxH)
+  const int nk = (a.fold == 2 ? a.niter + 1 : a.niter) - (a.close ? 1 : 0);
   for (int k = 0; k < nk; ++k) {
-    if (k > 0 && !(DBG & 1)) {
+    if ((k > 0 || pb) && !(DBG & 1)) {                       // (a folded head was published by this launch: sweep 0 waits for it too)
       // neighbours' sweep k-1 published?  one lane per neighbour, relaxed agent-scope polls
       if (wave == 0 && nb_lo + lane <= nb_hi && nb_lo + lane != w) {
         const uint32_t *f = a.flags + (size_t)(nb_lo + lane) * 16;
-        const uint32_t want = a.epoch + (uint32_t)k;
+        const uint32_t want = a.epoch + (uint32_t)k + pb;
         unsigned spins = 0;
         while ((int32_t)(__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want) < 0) {
           if (++spins > (1u << 22)) {
@@ -3461,8 +3556,8 @@ __global__ __launch_bounds__(1024) void sells_smooth_kernel(SellSmoothArgs a)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // every storing wave: the stores have left the CU ...
       __syncthreads();
       if (threadIdx.x == 0) {                                // ... before the flag
-        if (a.fenced) __hip_atomic_store(a.flags + (size_t)w * 16, a.epoch + (uint32_t)(k + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        else __hip_atomic_store(a.flags + (size_t)w * 16, a.epoch + (uint32_t)(k + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (a.fenced) __hip_atomic_store(a.flags + (size_t)w * 16, a.epoch + (uint32_t)(k + 1) + pb, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        else __hip_atomic_store(a.flags + (size_t)w * 16, a.epoch + (uint32_t)(k + 1) + pb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
     const double *t = sin; sin = sout; sout = const_cast<double *>(t);

@@ -258,6 +258,11 @@ GMG_API int gmg_set_options(gmg_handle_t h, int mode, int cycle, int maxiter, do
  *                    sells_smooth_kernel with a compile-time run count -- run offsets, gather indices and, at one slice per wave, the
  *                    row's coefficients in registers, one load round trip per sweep; 0 = the runtime run count body.  Same bits either
  *                    way; gmg_sweep_signature names the instantiation that ran)
+ *                    persist_fold (7: bit mask of the transfers that run as the head of the one-launch pass they feed instead of
+ *                    as launches of their own -- 1 the restriction in front of a pre-smoothing pass, 2 prolongation + correction +
+ *                    r -= A dx in front of a post-smoothing pass, 4 bit 1 also where the finer level is no one-launch level; one
+ *                    rank, transfer tables in the LDS form that fit next to the pass's own; 0 = separate launches.  Same bits
+ *                    either way; gmg_sweep_signature ends in folds=R+P / R / P / none for a level with a one-launch pass)
  *   coarsest level   coarse_host_max (1500) coarse_host_fallback_max (6000) coarse_auto_cg_min (20000: a dense-inverse request on a
  *                    coarsest level of at least this many dofs is served by the device CG-Jacobi solver instead) gj_mfma (1) gj_wide_min (4096)
  *   patch smoother   patch_dedup (1) patch_source_dedup (1) patch_operator (1)
