@@ -346,7 +346,7 @@ struct DevCSR {
   bool present() const { return rowptr != nullptr; }
 };
 
-enum SmootherKind { SM_JACOBI = 0, SM_PATCH = 1 };
+enum SmootherKind { SM_JACOBI = 0, SM_PATCH = 1, SM_GAUSS_SEIDEL = 2 };
 
 struct Smoother {
   int kind = SM_JACOBI;
@@ -354,6 +354,7 @@ struct Smoother {
   double omega = 1.0;         // RichardsonSmoothers.jl:28 default
   // patch data (host copy kept until setup; shared between the copies of a smoother)
   int patch_kind = GMG_PATCH_LU;
+  int gs_type = GMG_GS_SYMMETRIC;   // SM_GAUSS_SEIDEL: which passes run (the tables belong to the level: Level::gs)
   struct Tables {
     std::vector<int64_t> pptr;
     std::vector<int32_t> prow;     // patch_rows: b[rows_p] is the local right-hand side   (PatchSolvers.jl:237-240)
@@ -412,6 +413,8 @@ struct GhostFix {
   uint8_t *scode = nullptr;
 };
 
+struct GsLevel;                    // gs.inc.hpp
+
 struct Level {
   // s = omega*(Dinv*r) already written into sbuf[0] by the kernel that produced r (restriction / r -= A dx)
   bool s0_ready = false;
@@ -453,6 +456,7 @@ struct Level {
   DevCSR G;
   double *ptmp = nullptr, *pcor = nullptr;
   bool post_shares_pre = true;
+  std::shared_ptr<GsLevel> gs;    // level-set schedule + triangle tables of the level's Gauss-Seidel smoother(s), one copy for pre and post
   int64_t n = 0;                  // owned rows
   int64_t nvec = 0;               // vector length = owned + ghost
   HaloPlan halo;                  // neighbour exchange plan (multi-GPU)
@@ -489,6 +493,7 @@ struct Level {
   double *dx = nullptr;
   double *rcur = nullptr;         // buffer holding the current residual after a cycle
 };
+const char *gs_tag(const Level &L);   // gs.inc.hpp: the directions the level's Gauss-Seidel tables hold (gmg_sweep_signature)
 
 // ConvergenceLog + SolverTolerances (ConvergenceLogs.jl:42-150, SolverTolerances.jl:97-128)
 struct ConvLog {
@@ -914,6 +919,7 @@ struct gmg_solver {
       L.sbuf[0] = L.sbuf[1] = nullptr;
       L.pflags = nullptr; L.pf_nwg = 0; L.pf_epoch = 1;
       for (Smoother *sp : {&L.pre, &L.post, &L.pcorr}) sp->reset_device();
+      L.gs.reset();
       L.s0_ready = false;
     }
     d_Ainv = d_partials = d_scalars = nullptr;
@@ -3128,6 +3134,10 @@ struct gmg_solver {
   void build_patch_operator(Level &L, Smoother &S);
   void free_pattern(DevCSR &M);
   void patch_precond(Level &L, Smoother &S, const double *r, double omega, bool relax, double *dx, double *x);
+  // Gauss-Seidel smoother (gs.inc.hpp)
+  void build_gs(int l, bool values_only = false);
+  void gs_solve(Level &L, int dir, const double *r, double *dx);
+  void gs_pass(int l, Smoother &S, double *x, double *r, bool x_zero);
 
   // May the transfer T in front of the pass S of level l run as that pass's head?  One rank, a Jacobi pass that runs as one launch
   // with T's table next to its own in LDS (T in the per-lane pattern form, its table in the LDS form).
@@ -3479,10 +3489,11 @@ struct gmg_solver {
       }
       return out;
     }
-    // patch smoother: r updated in place
+    // Gauss-Seidel / patch smoother: r updated in place
     double *r = nullptr;
     if (r_internal) r = const_cast<double *>(r_in);
     else { r = L.rbuf[0]; copy(r, r_in, n); }
+    if (S.kind == SM_GAUSS_SEIDEL) { gs_pass(l, S, x, r, x_zero); return r; }   // (the first pass writes x where x_zero holds)
     if (x_zero) zero(x, n);
     // Overlapping layout (gmg_set_partition_overlap): consistent!(r) once per block of `depth` sweeps; inside a block every local row
     // is swept with the patches of the local box -- no assemble!, no exchange of dx (ghost layers are recomputed redundantly and stay
@@ -5810,6 +5821,9 @@ void gmg_solver::setup()
     std::fprintf(stderr, "[gmg_setup] level %d %-28s %8.1f ms\n", l, what, std::chrono::duration<double, std::milli>(now - t_last).count());
     t_last = now;
   };
+  for (int l = 0; l < nlev - 1; ++l)
+    REQUIRE(comm.nranks == 1 || (lev[l].pre.kind != SM_GAUSS_SEIDEL && lev[l].post.kind != SM_GAUSS_SEIDEL), GMG_ERR_UNSUPPORTED,
+            "Gauss-Seidel smoothers are single-GPU: this handle's communicator has more than one rank (real or loopback)");
   // patch smoothers / patch corrections with patches of more than 64 dofs take their blocks from the level's CSR (one thread block
   // per patch): a level kept in row-pattern form only gets its rows back
   for (int l = 0; l < nlev - 1; ++l) {
@@ -6056,6 +6070,7 @@ void gmg_solver::setup()
       if (L.pre.kind == SM_PATCH) build_patch(L, L.pre);
       if (L.post_shares_pre) L.post = L.pre;
       else if (L.post.kind == SM_PATCH) build_patch(L, L.post);
+      if (L.pre.kind == SM_GAUSS_SEIDEL || L.post.kind == SM_GAUSS_SEIDEL) build_gs(l);
       drop_csr_stream(L.P);
       drop_csr_stream(L.R);
       lap("D^-1, patch blocks", l);
@@ -6187,6 +6202,7 @@ void gmg_solver::refresh_values()
         if (L.pre.kind == SM_PATCH) build_patch(L, L.pre, true);
         if (L.post_shares_pre) L.post = L.pre;
         else if (L.post.kind == SM_PATCH) build_patch(L, L.post, true);
+        if (L.pre.kind == SM_GAUSS_SEIDEL || L.post.kind == SM_GAUSS_SEIDEL) build_gs(l, true);
       } else if (coarse_eff == GMG_COARSE_DENSE_INVERSE) {
         release(d_Ainv, (size_t)n * (size_t)n);
         build_coarse();
@@ -7365,6 +7381,11 @@ int gmg_precond_apply(gmg_handle_t h, int lev, int which, const double *r, doubl
     if (S.kind == SM_JACOBI) {
       hipLaunchKernelGGL(jacobi_apply_kernel, dim3(gmg_solver::grid_for(L.n)), dim3(256), 0, h->stream, L.n, L.dinv, dr, out);
       HIP_CHECK(hipGetLastError());
+    } else if (S.kind == SM_GAUSS_SEIDEL) {
+      // ldiv!(x, ns, b), SymGaussSeidelSmoothers.jl:210-214: x = 0 ; aux = copy(b) ; solve!(x, ns, aux) with all niter iterations
+      double *rr = h->scratch_vec(2, h->lev[0].nvec);
+      h->copy(rr, dr, L.n);
+      h->gs_pass(lev, S, out, rr, true);
     } else if (h->comm.nranks > 1 && L.halo.present) {
       // solve!(x::PVector, ns::PatchNS, b::PVector), PatchSolvers.jl:227-236: consistent!(b), local solves, assemble!(x)
       double *rr = h->scratch_vec(2, h->lev[0].nvec), *oo = h->scratch_vec(3, h->lev[0].nvec);
@@ -7904,6 +7925,10 @@ int gmg_sweep_signature(gmg_handle_t h, int lev, char *buf, int cap)
     const int fr = h->lev[lev].fold_ran;
     if (A.smooth_sig[0]) std::snprintf(buf, (size_t)cap, "%s%s%s folds=%s", sig, sig[0] ? " + " : "", A.smooth_sig, fr == 3 ? "R+P" : fr == 1 ? "R" : fr == 2 ? "P" : "none");
     else std::snprintf(buf, (size_t)cap, "%s", sig);
+    if (h->lev[lev].gs) {                                    // a level with a Gauss-Seidel smoother: which directions have tables
+      const size_t len = std::strlen(buf);
+      if (len + 1 < (size_t)cap) std::snprintf(buf + len, (size_t)cap - len, " gs=%s", gs_tag(h->lev[lev]));
+    }
   });
 }
 
@@ -7988,3 +8013,4 @@ int gmg_device_bytes(gmg_handle_t h, int64_t *bytes)
 } // extern "C"
 
 #include "block.inc.hpp"
+#include "gs.inc.hpp"

@@ -32,7 +32,7 @@ using Gridap
 using Gridap.Algebra
 using GridapSolvers
 using GridapSolvers.SolverInterfaces: ConvergenceLog, SolverTolerances
-using GridapSolvers.LinearSolvers: RichardsonSmoother, JacobiLinearSolver
+using GridapSolvers.LinearSolvers: RichardsonSmoother, JacobiLinearSolver, GaussSeidelSmoother, LinearSolverFromSmoother
 
 export HipGMGLinearSolver, HipCGSolver, HipFGMRESSolver, HipMINRESSolver, PatchTable, HipPatchProlongation
 export HipRichardsonLinearSolver, HipBlockTriangularSolver, HipBlockDiagonalSolver, HipBlockFGMRESSolver, block_mul!, block_cg_solve!
@@ -48,6 +48,7 @@ const GMG_CSR, GMG_CSC = Cint(0), Cint(1)
 const GMG_MEM_HOST, GMG_MEM_DEVICE = Cint(0), Cint(1)
 const GMG_PRE, GMG_POST, GMG_PRE_AND_POST = Cint(0), Cint(1), Cint(2)
 const GMG_PATCH_LU, GMG_PATCH_NOPIVOT = Cint(0), Cint(1)
+const GMG_GS_SYMMETRIC, GMG_GS_FORWARD, GMG_GS_BACKWARD = Cint(0), Cint(1), Cint(2)
 
 struct GmgResult
   niters::Int32
@@ -279,6 +280,14 @@ function _set_smoother(h, lev, which, sm::RichardsonSmoother)
   end
 end
 
+# GaussSeidelSmoother(niter,ω,type) / SymGaussSeidelSmoother(niter,ω), SymGaussSeidelSmoothers.jl:105-121: the reference's own type.
+# The triangular solves run on the device over the level sets of the matrix graph, bit for bit the reference's loops.
+function _set_smoother(h, lev, which, sm::GaussSeidelSmoother)
+  t = sm.type === :symmetric ? GMG_GS_SYMMETRIC : sm.type === :forward ? GMG_GS_FORWARD : GMG_GS_BACKWARD
+  check(h, ccall((:gmg_set_smoother_gauss_seidel, libgmgamd), Cint, (Ptr{Cvoid},Cint,Cint,Cint,Float64,Cint),
+                 h, lev, which, sm.niter, sm.ω, t))
+end
+
 # numerical_setup(ss,A): GMGLinearSolvers.jl:183-210
 function Gridap.Algebra.numerical_setup(ss::HipGMGSymbolicSetup, mat::AbstractMatrix)
   s = ss.solver
@@ -456,7 +465,8 @@ end
 
 # GMRESSolver(m;Pr,Pl,...) on the device: GMRESSolvers.jl:25-29 (defaults), :132-210 (solve!).  A side is `nothing`, a
 # HipGMGLinearSolver, or (nothing | :jacobi | :smoother, gmg): nothing / JacobiLinearSolver() / LinearSolverFromSmoother(finest
-# pre-smoother) on the matrix of gmg's handle.  Both sides live on one handle and its GMG serves on one side only; at least one side
+# pre-smoother) on the matrix of gmg's handle; the smoother form may also be written as the reference writes it,
+# (LinearSolverFromSmoother(gmg.pre_smoothers[1]), gmg), with a RichardsonSmoother or a GaussSeidelSmoother inside.  Both sides live on one handle and its GMG serves on one side only; at least one side
 # names the handle (Pr=(nothing,gmg): the unpreconditioned solver).
 struct HipGMRESSolver{A} <: Gridap.Algebra.LinearSolver
   m       :: Int
@@ -470,6 +480,11 @@ end
 _gmres_side(::Nothing) = (Cint(0), nothing)
 _gmres_side(P::HipGMGLinearSolver) = (Cint(1), P)
 function _gmres_side(P::Tuple{Any,HipGMGLinearSolver})
+  if P[1] isa LinearSolverFromSmoother
+    (P[1].smoother isa Union{RichardsonSmoother,GaussSeidelSmoother} && P[1].smoother === P[2].pre_smoothers[1]) ||
+      error("LinearSolverFromSmoother must wrap the GMG's finest pre-smoother")
+    return (Cint(3), P[2])
+  end
   k = P[1] === nothing ? 0 : P[1] === :jacobi ? 2 : P[1] === :smoother ? 3 : error("a GMRES side is nothing, gmg, or (nothing | :jacobi | :smoother, gmg)")
   return (Cint(k), P[2])
 end

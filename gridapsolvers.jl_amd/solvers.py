@@ -37,7 +37,7 @@ import numpy as np
 from . import abi
 
 __all__ = [
-    "JacobiLinearSolver", "RichardsonSmoother", "PatchSolver", "BlockJacobiSolver", "LUSolver",
+    "JacobiLinearSolver", "RichardsonSmoother", "GaussSeidelSmoother", "SymGaussSeidelSmoother", "PatchSolver", "BlockJacobiSolver", "LUSolver",
     "GMGLinearSolver", "CGSolver", "FGMRESSolver", "MINRESSolver", "GMRESSolver", "ConvergenceLog", "PatchProlongationOperator",
     "RichardsonLinearSolver", "BlockDiagonalSolver", "BlockTriangularSolver", "SchurComplementSolver", "LinearSystemBlock", "MatrixBlock", "LinearSolverFromSmoother",
     "NullSpace", "NullspaceSolver", "is_orthonormal", "is_orthogonal", "make_orthonormal_", "gram_schmidt_", "modified_gram_schmidt_",
@@ -116,12 +116,31 @@ class RichardsonSmoother:
         self.M, self.niter, self.omega = M, int(niter), float(omega)
 
 
+class GaussSeidelSmoother:
+    """GaussSeidelSmoother(niter=1, omega=1.0, type=:symmetric) -- SymGaussSeidelSmoothers.jl:105-118."""
+    _TYPES = {"symmetric": abi.GS_SYMMETRIC, "forward": abi.GS_FORWARD, "backward": abi.GS_BACKWARD}
+
+    def __init__(self, niter=1, omega=1.0, type="symmetric"):
+        if type not in self._TYPES:
+            raise ValueError("The type must be :symmetric, :forward or :backward.")
+        if not int(niter) > 0:
+            raise ValueError("The number of iterations must be a positive integer.")
+        if not float(omega) > 0.0:
+            raise ValueError("The relaxation parameter must be a positive real number.")
+        self.niter, self.omega, self.type = int(niter), float(omega), type
+
+
+def SymGaussSeidelSmoother(niter=1, omega=1.0):
+    """SymGaussSeidelSmoother(niter, omega) = GaussSeidelSmoother(niter, omega, :symmetric) -- SymGaussSeidelSmoothers.jl:121."""
+    return GaussSeidelSmoother(niter, omega, "symmetric")
+
+
 class LinearSolverFromSmoother:
     """LinearSolverFromSmoother(smoother) -- LinearSolverFromSmoothers.jl:2-4: x = 0; r = copy(b); solve!(x,smoother,r)."""
 
     def __init__(self, smoother):
-        if not isinstance(smoother, RichardsonSmoother):
-            raise TypeError("smoother must be a RichardsonSmoother")
+        if not isinstance(smoother, (RichardsonSmoother, GaussSeidelSmoother)):
+            raise TypeError("smoother must be a RichardsonSmoother or a GaussSeidelSmoother")
         self.smoother = smoother
 
 
@@ -596,8 +615,11 @@ class GMGNumericalSetup:
 
     def _set_smoother(self, l, which, sm):
         lib, h = self._lib, self.h
+        if isinstance(sm, GaussSeidelSmoother):
+            abi.check(h, lib.gmg_set_smoother_gauss_seidel(h, l, which, sm.niter, sm.omega, sm._TYPES[sm.type]))
+            return
         if not isinstance(sm, RichardsonSmoother):
-            raise TypeError("smoothers must be RichardsonSmoother objects")
+            raise TypeError("smoothers must be RichardsonSmoother or GaussSeidelSmoother objects")
         if isinstance(sm.M, JacobiLinearSolver):
             abi.check(h, lib.gmg_set_smoother_jacobi(h, l, which, sm.niter, sm.omega))
         else:
@@ -757,6 +779,13 @@ class GMGNumericalSetup:
         v = C.c_int64(0)
         abi.check(self.h, self._lib.gmg_device_bytes(self.h, C.byref(v)))
         return v.value
+
+    def gs_schedule(self, lev=0, forward=True):
+        """gmg_get_gs_schedule: what the setup of the level's Gauss-Seidel smoother built for one direction ->
+        dict(nsets, max_set_rows, nlaunches, nwide); GmgError (ERR_STATE) when no smoother of the level uses that direction."""
+        v = [C.c_int64(0) for _ in range(4)]
+        abi.check(self.h, self._lib.gmg_get_gs_schedule(self.h, lev, 0 if forward else 1, *[C.byref(q) for q in v]))
+        return dict(zip(("nsets", "max_set_rows", "nlaunches", "nwide"), (q.value for q in v)))
 
 
 def _set_block(fn, h, i, j, M):

@@ -168,6 +168,28 @@ GMG_API int gmg_set_smoother_patch_matrices(gmg_handle_t h, int lev, int which, 
                                             const void *patch_cols, int index_base, int index_bytes,
                                             const double *blocks, int blocks_are_factors, const int32_t *pivots);
 
+/* GaussSeidelSmoother(niter, omega, type), SymGaussSeidelSmoothers.jl:105-121 (SymGaussSeidelSmoother(niter, omega) is the symmetric
+ * type).  solve!, :175-208, repeats niter times: forward pass (types forward, symmetric) dx = L \ r ; dx .= omega dx ; x .+= dx ;
+ * r .-= A dx, then the same backward pass with U (types backward, symmetric); L / U = lower / upper triangle with the diagonal.
+ * niter <= 0, omega <= 0 or an unknown type: GMG_ERR_INVALID (the constructor's @check, :113-115).
+ * The triangular solves run on the device over the level sets of the dependency graph, one row per lane, each row summed in the
+ * order of the reference's forward_sub! / backward_sub! and divided by the stored diagonal: bit for bit the sequential loops.
+ * gmg_setup sorts the columns inside the rows if need be, builds the level sets and the tables of the directions the level's
+ * smoothers use (one copy for pre and post; counted by gmg_device_bytes) and fixes the launch plan from the set sizes: consecutive
+ * sets of at most 1024 rows share one launch of one workgroup, a larger set gets a launch of its own.  No launch waits on another
+ * workgroup.  A missing or zero diagonal entry: GMG_ERR_SINGULAR at gmg_setup (SingularException, :31-33).  gmg_update_values +
+ * gmg_setup keep the schedule and refill the values where the level's layout refreshes in place (any other path is a full setup
+ * that rebuilds them; the results are the same bits).  gmg_smooth is solve!; gmg_precond_apply is ldiv!, :210-214 (x = 0, a copy
+ * of r, all niter iterations).  Single GPU: GMG_ERR_UNSUPPORTED at gmg_setup on a communicator of more than one rank (real or
+ * loopback).  gmg_model_bytes is not extended: on a handle with such a smoother its byte model still counts Jacobi sweeps.
+ * gmg_sweep_signature of a level with such a smoother ends in " gs=F+B", " gs=F" or " gs=B" (the directions that have tables). */
+enum gmg_gs_type { GMG_GS_SYMMETRIC = 0, GMG_GS_FORWARD = 1, GMG_GS_BACKWARD = 2 };
+GMG_API int gmg_set_smoother_gauss_seidel(gmg_handle_t h, int lev, int which, int niter, double omega, int type);
+/* The schedule gmg_setup built: dir 0 forward, 1 backward (GMG_ERR_STATE if no smoother of the level uses that direction):
+ * number of level sets, rows of the largest, launches per triangular solve and how many of them are one-set launches. */
+GMG_API int gmg_get_gs_schedule(gmg_handle_t h, int lev, int dir, int64_t *nsets, int64_t *max_set_rows,
+                                int64_t *nlaunches, int64_t *nwide);
+
 /* Patch-corrected prolongation  y = P x - sum_p R_p^T A_pp^-1 R_p (A P x)  over the given patches
  * (PatchProlongationOperator, PatchBasedSmoothers/PatchTransferOperators.jl:153-172 with rhs = lhs = the
  * level operator; used by the reference for grad-div problems, test/Applications/StokesGMG.jl:125-133).
