@@ -21,6 +21,7 @@ LEVEL_KRYLOV = -1          # GMG_LEVEL_KRYLOV: the separate Krylov operator of a
 COARSE_DENSE_INVERSE, COARSE_CG_JACOBI, COARSE_HOST_CALLBACK = 0, 1, 2
 BLOCK_DIAGONAL, BLOCK_LOWER, BLOCK_UPPER, BLOCK_SCHUR = 0, 1, 2, 3
 BLOCK_GMG, BLOCK_CG_JACOBI, BLOCK_LU, BLOCK_JACOBI = 1, 2, 3, 4
+BLOCK_SLOT_SYSTEM, BLOCK_SLOT_PRECOND, BLOCK_SLOT_DIAG_MATRIX = 0, 1, 2
 
 
 class Result(C.Structure):
@@ -164,6 +165,10 @@ SYMBOLS = {
     "gmg_block_set_diag_matrix": [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_int, C.c_int, C.c_int],
     "gmg_block_setup": [C.c_void_p],
+    "gmg_block_update_values": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p],
+    "gmg_block_update_values_csc": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int],
+    "gmg_block_refresh_diag_solver": [C.c_void_p, C.c_int],
+    "gmg_block_get_setup_info": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
     "gmg_block_precond_apply": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
     "gmg_block_apply_system": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
     "gmg_block_fgmres_solve": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

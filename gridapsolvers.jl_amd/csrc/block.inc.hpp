@@ -20,6 +20,14 @@ struct BlockDiag {
   double atol = 1e-12, rtol = 1e-6;
   double *w = nullptr, *p = nullptr, *z = nullptr, *r = nullptr;   // CGSolvers.jl:42-48
   ConvLog log;
+  bool refresh = false;         // gmg_block_refresh_diag_solver: NonlinearSystemBlock, set up again at the next gmg_block_setup
+};
+
+// what gmg_block_update_values[_csc] needs to know about one stored block besides its host copy
+struct BlockMeta {
+  int layout = GMG_CSR;            // layout the block was set with
+  bool dirty = false;              // values changed since the last gmg_block_setup
+  std::vector<uint32_t> csc_perm;  // gmg_block_update_values_csc: CSR position of every CSC entry, recorded by the first call
 };
 
 struct gmg_block_solver {
@@ -36,6 +44,13 @@ struct gmg_block_solver {
   std::vector<double *> fg_V, fg_Z;
   bool setup_done = false;
   std::string err;
+  // numerical_setup!(ns,A) (BlockTriangularSolvers.jl:156-186, BlockDiagonalSolvers.jl:153-163): what changed since the last setup
+  std::map<std::pair<int, int>, BlockMeta> msys, mpre;
+  std::vector<BlockMeta> mdiag;    // of BlockDiag::hM
+  bool was_setup = false;          // the device state of the last gmg_block_setup is whole
+  bool structure_dirty = true;     // anything but values changed since then
+  int info_kind = 0;               // gmg_block_get_setup_info: 1 = full, 2 = in place
+  int64_t info_blocks = 0, info_value_bytes = 0;
   // distributed runs (one handle per rank): block vectors hold the OWNED entries of every block; a block whose columns reach
   // into other ranks' entries gets an exchange plan and a work vector with ghost space ([own | ghost], as on GMG levels)
   std::vector<HaloPlan> plan;
@@ -64,18 +79,147 @@ struct gmg_block_solver {
       }
   }
 
+  void touch() { setup_done = false; structure_dirty = true; }
+  BlockMeta &meta_of(int slot, int i, int j) { return slot == GMG_BLOCK_SLOT_SYSTEM ? msys[{i, j}] : slot == GMG_BLOCK_SLOT_PRECOND ? mpre[{i, j}] : mdiag[(size_t)i]; }
+
+  // gmg_block_setup: in place when only values changed and every changed block is stored with explicit values, else in full
   void setup()
   {
     HIP_CHECK(hipSetDevice(eng.device));
+    if (can_refresh()) refresh();
+    else full_setup();
+    for (auto &kv : msys) kv.second.dirty = false;
+    for (auto &kv : mpre) kv.second.dirty = false;
+    for (auto &m : mdiag) m.dirty = false;
+    for (auto &D : diag) D.refresh = false;
+  }
+
+  // the device form of a dirty block (nullptr: it has none, e.g. the matrix of an LU block)
+  DevCSR *dirty_dev(int slot, int i, int j)
+  {
+    if (slot == GMG_BLOCK_SLOT_DIAG_MATRIX) return (diag[i].kind == GMG_BLOCK_CG_JACOBI || diag[i].kind == GMG_BLOCK_JACOBI) ? &diag[i].M : nullptr;
+    auto &m = slot == GMG_BLOCK_SLOT_SYSTEM ? sys : pre;
+    auto it = m.find({i, j});
+    return it == m.end() ? nullptr : &it->second;
+  }
+  template <typename F>
+  void for_each_dirty(F &&f)                                 // f(slot, i, j, host copy)
+  {
+    for (auto &kv : msys) if (kv.second.dirty) f((int)GMG_BLOCK_SLOT_SYSTEM, kv.first.first, kv.first.second, hsys.at(kv.first));
+    for (auto &kv : mpre) if (kv.second.dirty) f((int)GMG_BLOCK_SLOT_PRECOND, kv.first.first, kv.first.second, hpre.at(kv.first));
+    for (int i = 0; i < nb; ++i) if (mdiag[(size_t)i].dirty && diag[i].hasM) f((int)GMG_BLOCK_SLOT_DIAG_MATRIX, i, i, diag[i].hM);
+  }
+  // the matrix a Jacobi / CG-Jacobi / LU block is set up on: its own (MatrixBlock) or the system's (i,i)
+  int diag_slot(int i) const { return diag[i].hasM ? GMG_BLOCK_SLOT_DIAG_MATRIX : GMG_BLOCK_SLOT_SYSTEM; }
+
+  bool can_refresh()
+  {
+    if (!was_setup || structure_dirty || eng.comm.nranks != 1 || !eng.opt_int("GMG_REFRESH", 1)) return false;
+    // a marked Jacobi block takes D^-1 from the refill of its matrix: that matrix is written again whether or not it changed
+    for (int i = 0; i < nb; ++i)
+      if (diag[i].refresh && (diag[i].kind == GMG_BLOCK_CG_JACOBI || diag[i].kind == GMG_BLOCK_JACOBI)) meta_of(diag_slot(i), i, i).dirty = true;
+    bool ok = true;
+    for_each_dirty([&](int slot, int i, int j, const HostCSR &) {
+      const DevCSR *M = dirty_dev(slot, i, j);
+      if (M && !M->explicit_values()) ok = false;            // dictionary / row-pattern layout: chosen from the values
+    });
+    return ok;
+  }
+
+  // numerical_setup!(ns,A) in place: every layout, work vector, Krylov basis, exchange plan and attachment stays; the values of the
+  // dirty blocks are copied to the device and refilled, the MARKED diagonal solvers (NonlinearSystemBlock) are set up again, the
+  // others keep their D^-1 / inverse (LinearSystemBlock / MatrixBlock: BlockSolverInterfaces.jl:104-118,232-236)
+  void refresh()
+  {
+    const bool timing = eng.opt_int("GMG_SETUP_TIMING", 0) != 0;
+    const auto t_begin = std::chrono::steady_clock::now();
+    gmg_solver::RefillStage st;
+    st.timed = timing;
+    double solver_ms = 0.0;
+    info_kind = 2; info_blocks = 0; info_value_bytes = 0;
+    setup_done = false;
+    try {
+      for_each_dirty([&](int slot, int i, int j, const HostCSR &H) {
+        DevCSR *M = dirty_dev(slot, i, j);
+        if (!M) return;
+        double *dinv = nullptr;
+        if (i == j && diag[i].refresh && slot == diag_slot(i) && diag[i].dinv) dinv = diag[i].dinv;
+        int nzero = 0;
+        if (st.d_nzero) HIP_CHECK(hipMemsetAsync(st.d_nzero, 0, sizeof(int), eng.stream));
+        eng.refill_values(*M, H.val.data(), dinv, st);
+        if (dinv) {
+          HIP_CHECK(hipMemcpyAsync(&nzero, st.d_nzero, sizeof(int), hipMemcpyDeviceToHost, eng.stream));
+          HIP_CHECK(hipStreamSynchronize(eng.stream));
+          REQUIRE(nzero == 0, GMG_ERR_SINGULAR, "zero diagonal entry in block " + std::to_string(i));
+        }
+        info_blocks += 1; info_value_bytes += (int64_t)sizeof(double) * H.nnz();
+      });
+      const auto t_solvers = std::chrono::steady_clock::now();
+      for (int i = 0; i < nb; ++i) {
+        BlockDiag &D = diag[i];
+        if (!D.refresh) continue;
+        if (D.kind == GMG_BLOCK_GMG)                         // the caller has refreshed the GMG handle itself (gmg_update_values* + gmg_setup)
+          REQUIRE(D.g && D.g->setup_done, GMG_ERR_STATE, "the GMG handle of block " + std::to_string(i) + " is not set up");
+        else if (D.kind == GMG_BLOCK_LU) {
+          HIP_CHECK(hipStreamSynchronize(eng.stream));
+          eng.release(D.Minv, (size_t)bsize(i) * (size_t)bsize(i));
+          D.Minv = eng.build_dense_inverse(D.hasM ? D.hM : hsys.at({i, i}), "diagonal block " + std::to_string(i));
+        }
+      }
+      HIP_CHECK(hipStreamSynchronize(eng.stream));
+      solver_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_solvers).count();
+    } catch (...) {
+      eng.refill_release(st);
+      structure_dirty = true;                                // half-written: the next gmg_block_setup is a full one
+      throw;
+    }
+    eng.refill_release(st);
+    setup_done = true;
+    if (timing)
+      std::fprintf(stderr, "[gmg_block_setup] in place: %lld blocks, copy %8.1f ms, refill (+ D^-1) %8.1f ms, inverses %8.1f ms, total %8.1f ms\n",
+                   (long long)info_blocks, st.copy_ms, st.fill_ms, solver_ms,
+                   std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
+  }
+
+  void full_setup()
+  {
+    const bool timing = eng.opt_int("GMG_SETUP_TIMING", 0) != 0;
+    const auto t_begin = std::chrono::steady_clock::now();
     if (kind == GMG_BLOCK_SCHUR) {
       REQUIRE(!distributed(), GMG_ERR_UNSUPPORTED, "the Schur complement solver is single-GPU (no partitioned application)");
       // SchurComplementSolvers.jl:16-19: B and C are arguments of the solver; here the precond block or, without one, the system's
       REQUIRE(hpre.count({0, 1}) || hsys.count({0, 1}), GMG_ERR_STATE, "Schur complement solver: block (0,1) (B) is missing: no precond block and no system block");
       REQUIRE(hpre.count({1, 0}) || hsys.count({1, 0}), GMG_ERR_STATE, "Schur complement solver: block (1,0) (C) is missing: no precond block and no system block");
     }
+    // State that numerical_setup! keeps (the reference's work caches): y -- the initial guesses of the CG block solvers and the
+    // Schur solver's du -- on every later setup; and, when only values changed (the fallback of the in-place path), D^-1 / the
+    // inverse of the diagonal solvers that are NOT marked, so that both paths of gmg_block_setup give the same bits.
+    const bool values_only = was_setup && !structure_dirty;
+    std::vector<double> keep_y;
+    std::vector<std::vector<double>> keep_solver((size_t)nb);
+    if (y) {
+      HIP_CHECK(hipStreamSynchronize(eng.stream));
+      keep_y.resize((size_t)N());
+      if (N() > 0) HIP_CHECK(hipMemcpy(keep_y.data(), y, sizeof(double) * (size_t)N(), hipMemcpyDeviceToHost));
+      if (values_only)
+        for (int i = 0; i < nb; ++i) {
+          const BlockDiag &D = diag[i];
+          const double *src = D.kind == GMG_BLOCK_LU ? D.Minv : (D.kind == GMG_BLOCK_CG_JACOBI || D.kind == GMG_BLOCK_JACOBI) ? D.dinv : nullptr;
+          if (D.refresh || !src) continue;
+          keep_solver[(size_t)i].resize(D.kind == GMG_BLOCK_LU ? (size_t)bsize(i) * (size_t)bsize(i) : (size_t)bsize(i));
+          if (!keep_solver[(size_t)i].empty())
+            HIP_CHECK(hipMemcpy(keep_solver[(size_t)i].data(), src, sizeof(double) * keep_solver[(size_t)i].size(), hipMemcpyDeviceToHost));
+        }
+    }
+    was_setup = false;
     detach();
     eng.free_all();
+    w = y = tmp = nullptr;
+    for (auto &D : diag) { D.dinv = D.Minv = nullptr; D.M = DevCSR(); }
     sys.clear(); pre.clear();
+    info_kind = 1; info_blocks = 0; info_value_bytes = 0;
+    for (auto &kv : hsys) { info_blocks += 1; info_value_bytes += (int64_t)sizeof(double) * kv.second.nnz(); }
+    for (auto &kv : hpre) { info_blocks += 1; info_value_bytes += (int64_t)sizeof(double) * kv.second.nnz(); }
     eng.read_tuning();
     eng.init_reductions();
     int64_t nmax = 1;
@@ -126,8 +270,8 @@ struct gmg_block_solver {
       DevCSR &M = D.hasM ? (D.M = eng.upload_csr(*src)) : sys[{i, i}];
       int nzero = 0;
       D.dinv = eng.build_inv_diag(M, nzero);
-      REQUIRE(nzero == 0, GMG_ERR_SINGULAR, "zero diagonal entry in block " + std::to_string(i));
-      if (D.hasM) eng.drop_csr_stream(D.M);
+      REQUIRE(nzero == 0 || !keep_solver[(size_t)i].empty(), GMG_ERR_SINGULAR, "zero diagonal entry in block " + std::to_string(i));
+      if (D.hasM) { eng.drop_csr_stream(D.M); info_blocks += 1; info_value_bytes += (int64_t)sizeof(double) * src->nnz(); }
       if (D.kind == GMG_BLOCK_CG_JACOBI) { D.w = eng.dvec(n); D.p = eng.dvec(n); D.z = eng.dvec(n); D.r = eng.dvec(n); }
     }
     for (auto &kv : sys) eng.drop_csr_stream(kv.second);
@@ -139,8 +283,18 @@ struct gmg_block_solver {
     kw = eng.dvec(n); kp = eng.dvec(n); kz = eng.dvec(n); kr = eng.dvec(n);
     st_b = eng.dvec(n); st_x = eng.dvec(n);
     fg_V.clear(); fg_Z.clear();
+    if (!keep_y.empty()) HIP_CHECK(hipMemcpyAsync(y, keep_y.data(), sizeof(double) * keep_y.size(), hipMemcpyHostToDevice, eng.stream));
+    for (int i = 0; i < nb; ++i)
+      if (!keep_solver[(size_t)i].empty())
+        HIP_CHECK(hipMemcpyAsync(diag[i].kind == GMG_BLOCK_LU ? diag[i].Minv : diag[i].dinv, keep_solver[(size_t)i].data(),
+                                 sizeof(double) * keep_solver[(size_t)i].size(), hipMemcpyHostToDevice, eng.stream));
     HIP_CHECK(hipStreamSynchronize(eng.stream));
     setup_done = true;
+    was_setup = true;
+    structure_dirty = false;
+    if (timing)
+      std::fprintf(stderr, "[gmg_block_setup] full: %lld blocks, total %8.1f ms\n", (long long)info_blocks,
+                   std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
   }
 
   const DevCSR *sys_block(int i, int j) const
@@ -295,7 +449,7 @@ struct gmg_block_solver {
 static void block_forget(gmg_block_solver *B, gmg_solver *g)
 {
   for (auto &D : B->diag)
-    if (D.g == g) { D.g = nullptr; D.kind = 0; B->setup_done = false; }
+    if (D.g == g) { D.g = nullptr; D.kind = 0; B->touch(); }
   g->attached_to = nullptr;
   if (g->stream == B->eng.stream) {
     (void)hipStreamSynchronize(B->eng.stream);
@@ -363,6 +517,7 @@ int gmg_block_create(gmg_block_handle_t *out, int nblocks, const int64_t *block_
       s->off[i + 1] = s->off[i] + block_sizes[i];
     }
     s->diag.resize(nblocks);
+    s->mdiag.resize(nblocks);
     s->coeff.assign((size_t)nblocks * nblocks, 1.0);
     hipError_t e = hipStreamCreateWithFlags(&s->eng.stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
@@ -408,7 +563,7 @@ int gmg_block_comm_init_rccl(gmg_block_handle_t h, const char *rccl_path, const 
   if (!h) return GMG_ERR_INVALID;
   const int st = gmg_comm_init_rccl(&h->eng, rccl_path, unique_id128, rank, nranks);
   if (st != GMG_OK) h->err = h->eng.err;
-  h->setup_done = false;
+  h->touch();
   return st;
 }
 int gmg_block_comm_init_host(gmg_block_handle_t h, int rank, int nranks, gmg_host_exchange_fn xfn, gmg_host_allreduce_fn rfn, void *ctx)
@@ -416,7 +571,7 @@ int gmg_block_comm_init_host(gmg_block_handle_t h, int rank, int nranks, gmg_hos
   if (!h) return GMG_ERR_INVALID;
   const int st = gmg_comm_init_host(&h->eng, rank, nranks, xfn, rfn, ctx);
   if (st != GMG_OK) h->err = h->eng.err;
-  h->setup_done = false;
+  h->touch();
   return st;
 }
 int gmg_block_comm_set_loopback(gmg_block_handle_t h, int virtual_nranks)
@@ -424,7 +579,7 @@ int gmg_block_comm_set_loopback(gmg_block_handle_t h, int virtual_nranks)
   if (!h) return GMG_ERR_INVALID;
   const int st = gmg_comm_set_loopback(&h->eng, virtual_nranks);
   if (st != GMG_OK) h->err = h->eng.err;
-  h->setup_done = false;
+  h->touch();
   return st;
 }
 int gmg_block_set_partition(gmg_block_handle_t h, int j, int64_t n_own, int64_t n_ghost, int nnbr, const int32_t *nbr_rank,
@@ -436,7 +591,7 @@ int gmg_block_set_partition(gmg_block_handle_t h, int j, int64_t n_own, int64_t 
     REQUIRE(n_own == h->bsize(j), GMG_ERR_INVALID, "n_own must equal the block size given to gmg_block_create");
     if (h->plan.size() < (size_t)h->nb) h->plan.resize((size_t)h->nb);
     fill_plan(h->plan[j], h->eng.comm, n_own, n_ghost, nnbr, nbr_rank, snd_ptr, snd_idx, rcv_ptr);
-    h->setup_done = false;
+    h->touch();
   });
 }
 
@@ -447,7 +602,9 @@ int gmg_block_set_system_block(gmg_block_handle_t h, int i, int j, int64_t nrows
     check_block(h, i); check_block(h, j);
     REQUIRE(nrows == h->bsize(i) && ncols == h->ncols_of(j), GMG_ERR_INVALID, "block shape does not match the block sizes (columns = own + ghost entries of block j)");
     h->hsys[{i, j}] = convert_input(nrows, ncols, nnz, ptr, idx, val, layout, index_base, index_bytes);
-    h->setup_done = false;
+    h->msys[{i, j}] = BlockMeta();
+    h->msys[{i, j}].layout = layout;
+    h->touch();
   });
 }
 
@@ -459,7 +616,9 @@ int gmg_block_set_precond_block(gmg_block_handle_t h, int i, int j, int64_t nrow
     REQUIRE(i != j, GMG_ERR_INVALID, "diagonal blocks are given with gmg_block_set_diag_*");
     REQUIRE(nrows == h->bsize(i) && ncols == h->ncols_of(j), GMG_ERR_INVALID, "block shape does not match the block sizes (columns = own + ghost entries of block j)");
     h->hpre[{i, j}] = convert_input(nrows, ncols, nnz, ptr, idx, val, layout, index_base, index_bytes);
-    h->setup_done = false;
+    h->mpre[{i, j}] = BlockMeta();
+    h->mpre[{i, j}].layout = layout;
+    h->touch();
   });
 }
 
@@ -467,7 +626,9 @@ int gmg_block_set_coeff(gmg_block_handle_t h, int i, int j, double c)
 {
   return guarded_b(h, [&] {
     check_block(h, i); check_block(h, j);
-    h->coeff[(size_t)i * h->nb + j] = c;
+    double &cij = h->coeff[(size_t)i * h->nb + j];
+    if ((cij == 0.0) != (c == 0.0)) h->structure_dirty = true;   // a block enters or leaves the application: the next setup is a full one
+    cij = c;
   });
 }
 
@@ -483,7 +644,7 @@ int gmg_block_set_diag_gmg(gmg_block_handle_t h, int i, gmg_handle_t g)
     }
     D = BlockDiag();
     D.kind = GMG_BLOCK_GMG; D.g = g;
-    h->setup_done = false;
+    h->touch();
   });
 }
 
@@ -501,7 +662,7 @@ int gmg_block_set_diag_solver(gmg_block_handle_t h, int i, int kind, int maxiter
     D = BlockDiag();
     if (had) { D.hM = std::move(keep); D.hasM = true; }
     D.kind = kind; D.maxiter = maxiter; D.atol = atol; D.rtol = rtol;
-    h->setup_done = false;
+    h->touch();
   });
 }
 
@@ -513,7 +674,9 @@ int gmg_block_set_diag_matrix(gmg_block_handle_t h, int i, int64_t n, int64_t nn
     REQUIRE(n == h->bsize(i), GMG_ERR_INVALID, "matrix size does not match the block size");
     h->diag[i].hM = convert_input(n, h->ncols_of(i), nnz, ptr, idx, val, layout, index_base, index_bytes);   // distributed: own rows x [own | ghost]
     h->diag[i].hasM = true;
-    h->setup_done = false;
+    h->mdiag[(size_t)i] = BlockMeta();
+    h->mdiag[(size_t)i].layout = layout;
+    h->touch();
   });
 }
 
@@ -522,6 +685,86 @@ int gmg_block_setup(gmg_block_handle_t h)
   return guarded_b(h, [&] {
     REQUIRE(h, GMG_ERR_INVALID, "null handle");
     h->setup();
+  });
+}
+
+// ---- numerical_setup!(ns,A) on a block handle: BlockTriangularSolvers.jl:156-186, BlockDiagonalSolvers.jl:153-163 ---------------
+namespace {
+// the host copy and the record of block (slot,i,j); GMG_ERR_STATE before the first setup, GMG_ERR_INVALID when it is absent
+void block_for_update(gmg_block_handle_t h, int slot, int i, int j, HostCSR *&H, BlockMeta *&meta)
+{
+  REQUIRE(h, GMG_ERR_INVALID, "null handle");
+  REQUIRE(h->was_setup, GMG_ERR_STATE, "gmg_block_update_values before the first gmg_block_setup (numerical_setup missing)");
+  REQUIRE(slot == GMG_BLOCK_SLOT_SYSTEM || slot == GMG_BLOCK_SLOT_PRECOND || slot == GMG_BLOCK_SLOT_DIAG_MATRIX, GMG_ERR_INVALID, "bad block slot");
+  check_block(h, i);
+  if (slot == GMG_BLOCK_SLOT_DIAG_MATRIX) {
+    REQUIRE(h->diag[i].hasM, GMG_ERR_INVALID, "diagonal block " + std::to_string(i) + " has no matrix of its own (gmg_block_set_diag_matrix)");
+    H = &h->diag[i].hM; meta = &h->mdiag[(size_t)i];
+    return;
+  }
+  check_block(h, j);
+  auto &hm = slot == GMG_BLOCK_SLOT_SYSTEM ? h->hsys : h->hpre;
+  auto it = hm.find({i, j});
+  REQUIRE(it != hm.end(), GMG_ERR_INVALID, "block (" + std::to_string(i) + "," + std::to_string(j) + ") is absent");
+  H = &it->second; meta = &(slot == GMG_BLOCK_SLOT_SYSTEM ? h->msys : h->mpre)[{i, j}];
+}
+} // namespace
+
+int gmg_block_update_values(gmg_block_handle_t h, int slot, int i, int j, const double *val)
+{
+  return guarded_b(h, [&] {
+    HostCSR *H = nullptr;
+    BlockMeta *meta = nullptr;
+    block_for_update(h, slot, i, j, H, meta);
+    REQUIRE(val, GMG_ERR_INVALID, "null values");
+    std::memcpy(H->val.data(), val, sizeof(double) * (size_t)H->nnz());   // the 0-based CSR order held by the handle
+    meta->dirty = true;
+    h->setup_done = false;                                  // structure untouched: gmg_block_setup takes the in-place path when it can
+  });
+}
+
+int gmg_block_update_values_csc(gmg_block_handle_t h, int slot, int i, int j, const void *colptr, const void *rowidx,
+                                const double *val, int index_base, int index_bytes)
+{
+  return guarded_b(h, [&] {
+    HostCSR *Hp = nullptr;
+    BlockMeta *meta = nullptr;
+    block_for_update(h, slot, i, j, Hp, meta);
+    HostCSR &H = *Hp;
+    REQUIRE(val, GMG_ERR_INVALID, "null values");
+    REQUIRE(meta->layout == GMG_CSC, GMG_ERR_STATE, "gmg_block_update_values_csc: this block was not set in GMG_CSC layout");
+    REQUIRE(index_bytes == 4 || index_bytes == 8, GMG_ERR_INVALID, "index_bytes must be 4 or 8");
+    REQUIRE(index_base == 0 || index_base == 1, GMG_ERR_INVALID, "index_base must be 0 or 1");
+    if (colptr)                                             // a pattern of another size is refused on every call, recorded or not
+      REQUIRE(read_index(colptr, 0, index_bytes) == index_base && read_index(colptr, H.ncols, index_bytes) - index_base == H.nnz(), GMG_ERR_INVALID,
+              "gmg_block_update_values_csc: the column pointers do not describe the pattern this block was set with");
+    std::vector<double> v;
+    csc_values_to_csr(v, H.ptr, H.nrows, H.ncols, meta->csc_perm, colptr, rowidx, val, index_base, index_bytes, "gmg_block_update_values_csc", "block");
+    H.val.swap(v);
+    meta->dirty = true;
+    h->setup_done = false;
+  });
+}
+
+int gmg_block_refresh_diag_solver(gmg_block_handle_t h, int i)
+{
+  return guarded_b(h, [&] {
+    check_block(h, i);
+    REQUIRE(h->was_setup, GMG_ERR_STATE, "gmg_block_refresh_diag_solver before the first gmg_block_setup (numerical_setup missing)");
+    REQUIRE(h->diag[i].kind != 0, GMG_ERR_STATE, "no solver set for diagonal block " + std::to_string(i));
+    h->diag[i].refresh = true;
+    h->setup_done = false;
+  });
+}
+
+int gmg_block_get_setup_info(gmg_block_handle_t h, int *kind, int64_t *blocks_refreshed, int64_t *value_bytes, int64_t *device_bytes)
+{
+  return guarded_b(h, [&] {
+    REQUIRE(h, GMG_ERR_INVALID, "null handle");
+    if (kind) *kind = h->info_kind;
+    if (blocks_refreshed) *blocks_refreshed = h->info_blocks;
+    if (value_bytes) *value_bytes = h->info_value_bytes;
+    if (device_bytes) *device_bytes = h->eng.dev_bytes;
   });
 }
 

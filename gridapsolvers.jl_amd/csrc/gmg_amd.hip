@@ -310,6 +310,10 @@ struct DevCSR {
   uint16_t *orowpid = nullptr;
   int32_t *orowbase = nullptr, *opoff = nullptr;
   int opat_np = 0, opat_w = 0;
+  // numerical_setup!: the layout stores every value explicitly (CSR-stream, or SELL-64 / SELL-O with its own value stream), so new
+  // values on the same pattern can be written in place.  Dictionary / row-pattern / packed layouts were chosen FROM the values.
+  // The one rule of gmg_solver::can_refresh (levels) and gmg_block_solver::can_refresh (blocks).
+  bool explicit_values() const { return rowptr && (sell ? (sval && !pat && !vdict && !comp_idx) : val != nullptr); }
   // kernel + template arguments of the fused sweep last launched on this operator (x-update variant excluded): bench.py only
   // attaches committed PMC traffic to a kernel whose signature matches the profiled one (gmg_sweep_signature)
   mutable char sweep_sig[112] = {0};
@@ -4304,6 +4308,15 @@ struct gmg_solver {
   KrylovOps level0_ops(int use_precond);
   bool can_refresh() const;
   void refresh_values();
+  struct RefillStage {               // staging buffer of refill_values (SELL layouts), grown on demand; not part of `allocs`
+    double *d_val = nullptr;
+    size_t cap = 0;
+    int *d_nzero = nullptr;
+    double copy_ms = 0.0, fill_ms = 0.0;   // measured (with stream syncs) only when `timed`
+    bool timed = false;
+  };
+  void refill_values(DevCSR &A, const double *hval, double *dinv, RefillStage &st);
+  void refill_release(RefillStage &st);
   void setup();
   void build_coarse();
   double *build_dense_inverse(const HostCSR &A, const std::string &what);
@@ -6146,11 +6159,61 @@ bool gmg_solver::can_refresh() const
     const Level &L = lev[l];
     if (!L.values_dirty) continue;
     if (L.sA) return false;
-    const DevCSR &A = L.A;
-    if (A.sell && (A.pat || A.vdict || A.comp_idx || !A.sval)) return false;
-    if (!A.rowptr) return false;
+    if (!L.A.explicit_values()) return false;
   }
   return true;
+}
+
+// New values into ONE operator stored with explicit values (DevCSR::explicit_values): one host-to-device copy and, for SELL
+// layouts, the refill of the slices; D^-1 of the refreshed rows when `dinv` is given (zero diagonals are counted in *st.d_nzero,
+// which the caller has cleared).  Shared by the level path (refresh_values) and the block path (gmg_block_solver::refresh).
+void gmg_solver::refill_values(DevCSR &A, const double *hval, double *dinv, RefillStage &st)
+{
+  const int64_t nnz = A.nnz, n = A.nrows;
+  if (!st.d_nzero) {
+    HIP_CHECK(hipMalloc((void **)&st.d_nzero, sizeof(int)));
+    HIP_CHECK(hipMemsetAsync(st.d_nzero, 0, sizeof(int), stream));
+  }
+  auto t0 = std::chrono::steady_clock::now();
+  auto lap = [&](double &acc) {
+    if (!st.timed) return;
+    HIP_CHECK(hipStreamSynchronize(stream));
+    const auto now = std::chrono::steady_clock::now();
+    acc += std::chrono::duration<double, std::milli>(now - t0).count();
+    t0 = now;
+  };
+  const int grid = (int)std::max<int64_t>(1, (n + 255) / 256);
+  if (!A.sell) {
+    // CSR-stream layout: the value array itself is streamed
+    HIP_CHECK(hipMemcpyAsync(A.val, hval, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, stream));
+    lap(st.copy_ms);
+    if (dinv) {
+      if (A.ptr64) hipLaunchKernelGGL((inv_diag_kernel<int64_t>), dim3(grid), dim3(256), 0, stream, n, (const int64_t *)A.rowptr, A.col, A.val, dinv, st.d_nzero);
+      else hipLaunchKernelGGL((inv_diag_kernel<int32_t>), dim3(grid), dim3(256), 0, stream, n, (const int32_t *)A.rowptr, A.col, A.val, dinv, st.d_nzero);
+      HIP_CHECK(hipGetLastError());
+    }
+  } else {
+    if ((size_t)nnz > st.cap || !st.d_val) {
+      if (st.d_val) { HIP_CHECK(hipStreamSynchronize(stream)); (void)hipFree(st.d_val); st.d_val = nullptr; }
+      HIP_CHECK(hipMalloc((void **)&st.d_val, sizeof(double) * (size_t)std::max<int64_t>(nnz, 1)));
+      st.cap = (size_t)nnz;
+      if (st.timed) t0 = std::chrono::steady_clock::now();
+    }
+    HIP_CHECK(hipMemcpyAsync(st.d_val, hval, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, stream));
+    lap(st.copy_ms);
+    if (A.ptr64) hipLaunchKernelGGL((sell_refill_kernel<int64_t>), dim3(grid), dim3(256), 0, stream, n, (const int64_t *)A.rowptr, A.soff, A.scol, st.d_val, A.sval, dinv, st.d_nzero);
+    else hipLaunchKernelGGL((sell_refill_kernel<int32_t>), dim3(grid), dim3(256), 0, stream, n, (const int32_t *)A.rowptr, A.soff, A.scol, st.d_val, A.sval, dinv, st.d_nzero);
+    HIP_CHECK(hipGetLastError());
+  }
+  lap(st.fill_ms);
+}
+
+void gmg_solver::refill_release(RefillStage &st)
+{
+  (void)hipStreamSynchronize(stream);
+  if (st.d_val) (void)hipFree(st.d_val);
+  if (st.d_nzero) (void)hipFree(st.d_nzero);
+  st.d_val = nullptr; st.d_nzero = nullptr; st.cap = 0;
 }
 
 void gmg_solver::refresh_values()
@@ -6158,41 +6221,17 @@ void gmg_solver::refresh_values()
   HIP_CHECK(hipSetDevice(device));
   const bool timing = opt_int("GMG_SETUP_TIMING", 0) != 0;
   const auto t_begin = std::chrono::steady_clock::now();
-  int *d_nzero = nullptr;
-  HIP_CHECK(hipMalloc((void **)&d_nzero, sizeof(int)));
-  double *d_val = nullptr;
-  size_t cap = 0;
+  RefillStage st;
   try {
     for (int l = 0; l < nlev; ++l) {
       Level &L = lev[l];
       if (!L.values_dirty) continue;
-      DevCSR &A = L.A;
-      const int64_t nnz = L.hA.nnz(), n = L.n;
-      HIP_CHECK(hipMemsetAsync(d_nzero, 0, sizeof(int), stream));
+      const int64_t n = L.n;
       const bool want_dinv = L.dinv != nullptr;
-      if (!A.sell) {
-        // CSR-stream layout: the value array itself is streamed
-        HIP_CHECK(hipMemcpyAsync(A.val, L.hA.val.data(), sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, stream));
-        if (want_dinv) {
-          const int grid = (int)std::max<int64_t>(1, (n + 255) / 256);
-          if (A.ptr64) hipLaunchKernelGGL((inv_diag_kernel<int64_t>), dim3(grid), dim3(256), 0, stream, n, (const int64_t *)A.rowptr, A.col, A.val, L.dinv, d_nzero);
-          else hipLaunchKernelGGL((inv_diag_kernel<int32_t>), dim3(grid), dim3(256), 0, stream, n, (const int32_t *)A.rowptr, A.col, A.val, L.dinv, d_nzero);
-          HIP_CHECK(hipGetLastError());
-        }
-      } else {
-        if ((size_t)nnz > cap) {
-          if (d_val) { HIP_CHECK(hipStreamSynchronize(stream)); (void)hipFree(d_val); d_val = nullptr; }
-          HIP_CHECK(hipMalloc((void **)&d_val, sizeof(double) * (size_t)std::max<int64_t>(nnz, 1)));
-          cap = (size_t)nnz;
-        }
-        HIP_CHECK(hipMemcpyAsync(d_val, L.hA.val.data(), sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, stream));
-        const int grid = (int)std::max<int64_t>(1, (n + 255) / 256);
-        if (A.ptr64) hipLaunchKernelGGL((sell_refill_kernel<int64_t>), dim3(grid), dim3(256), 0, stream, n, (const int64_t *)A.rowptr, A.soff, A.scol, d_val, A.sval, L.dinv, d_nzero);
-        else hipLaunchKernelGGL((sell_refill_kernel<int32_t>), dim3(grid), dim3(256), 0, stream, n, (const int32_t *)A.rowptr, A.soff, A.scol, d_val, A.sval, L.dinv, d_nzero);
-        HIP_CHECK(hipGetLastError());
-      }
+      if (st.d_nzero) HIP_CHECK(hipMemsetAsync(st.d_nzero, 0, sizeof(int), stream));
+      refill_values(L.A, L.hA.val.data(), L.dinv, st);
       int nzero = 0;
-      HIP_CHECK(hipMemcpyAsync(&nzero, d_nzero, sizeof(int), hipMemcpyDeviceToHost, stream));
+      HIP_CHECK(hipMemcpyAsync(&nzero, st.d_nzero, sizeof(int), hipMemcpyDeviceToHost, stream));
       HIP_CHECK(hipStreamSynchronize(stream));
       const bool need_diag = l < nlev - 1 ? (L.pre.kind == SM_JACOBI || L.post.kind == SM_JACOBI) : coarse_eff == GMG_COARSE_CG_JACOBI;
       REQUIRE(!(want_dinv && need_diag && nzero > 0), GMG_ERR_SINGULAR, "zero diagonal entry on level " + std::to_string(l));
@@ -6210,13 +6249,11 @@ void gmg_solver::refresh_values()
       L.values_dirty = false;
     }
   } catch (...) {
-    if (d_val) (void)hipFree(d_val);
-    (void)hipFree(d_nzero);
+    refill_release(st);
     throw;
   }
   HIP_CHECK(hipStreamSynchronize(stream));
-  if (d_val) (void)hipFree(d_val);
-  (void)hipFree(d_nzero);
+  refill_release(st);
   setup_done = true;
   if (timing) std::fprintf(stderr, "[gmg_setup] value refresh %8.1f ms\n",
                            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
@@ -6699,6 +6736,43 @@ static void update_values_impl(gmg_handle_t h, int lev, const double *val)
   }
 }
 
+// v = nzval of the caller's CSC order in the CSR order the handle holds (rp = its row pointer).  `perm` records, on first use, where the
+// counting-sort transposition of convert_input put every CSC entry; later calls may pass NULL for colptr / rowidx and cost one
+// parallel scatter.  Nothing is changed when a REQUIRE fails.  fn / what ("level", "block") go into the messages.
+static void csc_values_to_csr(std::vector<double> &v, const std::vector<int64_t> &rp, int64_t nrows, int64_t ncols,
+                              std::vector<uint32_t> &perm_store, const void *colptr, const void *rowidx, const double *val,
+                              int index_base, int index_bytes, const char *fn, const char *what)
+{
+  const std::string f = std::string(fn) + ": ", w = what;
+  const int64_t nnz = rp.empty() ? 0 : rp.back();
+  if (perm_store.size() != (size_t)nnz) {
+    REQUIRE(colptr && rowidx, GMG_ERR_INVALID, f + "the first call on a " + w + " needs colptr and rowidx");
+    REQUIRE(nnz < (int64_t)UINT32_MAX, GMG_ERR_UNSUPPORTED, "more than 2^32-1 stored entries on one " + w);
+    REQUIRE(read_index(colptr, 0, index_bytes) == index_base && read_index(colptr, ncols, index_bytes) - index_base == nnz, GMG_ERR_INVALID,
+            f + "the column pointers do not describe the pattern this " + w + " was set with");
+    std::vector<uint32_t> perm((size_t)nnz);
+    std::vector<int64_t> fill(rp.begin(), rp.end() - 1);
+    for (int64_t c = 0; c < ncols; ++c) {
+      const int64_t k0 = read_index(colptr, c, index_bytes) - index_base, k1 = read_index(colptr, c + 1, index_bytes) - index_base;
+      REQUIRE(k0 <= k1 && k1 <= nnz, GMG_ERR_INVALID, "column pointers not monotone");
+      for (int64_t k = k0; k < k1; ++k) {
+        const int64_t r = read_index(rowidx, k, index_bytes) - index_base;
+        REQUIRE(r >= 0 && r < nrows, GMG_ERR_INVALID, "row index out of range");
+        REQUIRE(fill[(size_t)r] < rp[(size_t)r + 1], GMG_ERR_INVALID, f + "the pattern differs from the one this " + w + " was set with");
+        perm[(size_t)k] = (uint32_t)fill[(size_t)r]++;
+      }
+    }
+    perm_store.swap(perm);
+  }
+  v.assign((size_t)nnz, 0.0);
+  const uint32_t *pm = perm_store.data();
+  const int64_t nchunk = (nnz + (1 << 20) - 1) >> 20;
+  parallel_chunks(nchunk, [&](int64_t t) {
+    const int64_t k0 = t << 20, k1 = std::min(nnz, k0 + (1 << 20));
+    for (int64_t k = k0; k < k1; ++k) v[pm[k]] = val[k];
+  });
+}
+
 int gmg_update_values(gmg_handle_t h, int lev, const double *val)
 {
   return guarded(h, [&] {
@@ -6726,34 +6800,8 @@ int gmg_update_values_csc(gmg_handle_t h, int lev, const void *colptr, const voi
       rp.assign((size_t)nrows + 1, 0);
       for (int64_t i = 0; i < nrows; ++i) rp[(size_t)i + 1] = rp[(size_t)i] + L.sA->len[L.sA->rowpid[(size_t)i]];
     } else rp = L.hA.ptr;
-    const int64_t nnz = rp.back();
-    if (L.csc_perm.size() != (size_t)nnz) {
-      // first refresh: where the counting-sort transposition of gmg_set_matrix (convert_input) put every CSC entry
-      REQUIRE(colptr && rowidx, GMG_ERR_INVALID, "gmg_update_values_csc: the first call on a level needs colptr and rowidx");
-      REQUIRE(nnz < (int64_t)UINT32_MAX, GMG_ERR_UNSUPPORTED, "more than 2^32-1 stored entries on one level");
-      REQUIRE(read_index(colptr, 0, index_bytes) == index_base && read_index(colptr, ncols, index_bytes) - index_base == nnz, GMG_ERR_INVALID,
-              "gmg_update_values_csc: the column pointers do not describe the pattern this level was set with");
-      std::vector<uint32_t> perm((size_t)nnz);
-      std::vector<int64_t> fill(rp.begin(), rp.end() - 1);
-      for (int64_t c = 0; c < ncols; ++c) {
-        const int64_t k0 = read_index(colptr, c, index_bytes) - index_base, k1 = read_index(colptr, c + 1, index_bytes) - index_base;
-        REQUIRE(k0 <= k1 && k1 <= nnz, GMG_ERR_INVALID, "column pointers not monotone");
-        for (int64_t k = k0; k < k1; ++k) {
-          const int64_t r = read_index(rowidx, k, index_bytes) - index_base;
-          REQUIRE(r >= 0 && r < nrows, GMG_ERR_INVALID, "row index out of range");
-          REQUIRE(fill[(size_t)r] < rp[(size_t)r + 1], GMG_ERR_INVALID, "gmg_update_values_csc: the pattern differs from the one this level was set with");
-          perm[(size_t)k] = (uint32_t)fill[(size_t)r]++;
-        }
-      }
-      L.csc_perm.swap(perm);
-    }
-    std::vector<double> v((size_t)nnz);
-    const uint32_t *pm = L.csc_perm.data();
-    const int64_t nchunk = (nnz + (1 << 20) - 1) >> 20;
-    parallel_chunks(nchunk, [&](int64_t t) {
-      const int64_t k0 = t << 20, k1 = std::min(nnz, k0 + (1 << 20));
-      for (int64_t k = k0; k < k1; ++k) v[pm[k]] = val[k];
-    });
+    std::vector<double> v;
+    csc_values_to_csr(v, rp, nrows, ncols, L.csc_perm, colptr, rowidx, val, index_base, index_bytes, "gmg_update_values_csc", "level");
     std::vector<uint32_t> keep;
     keep.swap(L.csc_perm);                                   // (update_values_impl may re-hash the level; the pattern, hence the permutation, stays)
     update_values_impl(h, lev, v.data());

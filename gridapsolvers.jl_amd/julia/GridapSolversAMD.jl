@@ -27,7 +27,7 @@ module GridapSolversAMD
 
 using LinearAlgebra
 using SparseArrays
-using BlockArrays: blocks
+using BlockArrays: blocks, AbstractBlockMatrix
 using Gridap
 using Gridap.Algebra
 using GridapSolvers
@@ -38,7 +38,7 @@ export HipGMGLinearSolver, HipCGSolver, HipFGMRESSolver, HipMINRESSolver, PatchT
 export HipRichardsonLinearSolver, HipBlockTriangularSolver, HipBlockDiagonalSolver, HipBlockFGMRESSolver, block_mul!, block_cg_solve!
 export block_minres_solve!
 export HipGMRESSolver, HipBlockGMRESSolver
-export HipSchurComplementSolver
+export HipSchurComplementSolver, block_setup_info
 export HipNullspaceSolver, device_project!, device_make_orthogonal!, device_reconstruct!, device_is_orthonormal
 
 const libgmgamd = get(ENV, "LIBGMGAMD", joinpath(@__DIR__, "..", "libgmgamd.so"))
@@ -735,15 +735,17 @@ struct HipBlockTriangularSolver <: Gridap.Algebra.LinearSolver
   mats    :: Dict{Tuple{Int,Int},Any}
   coeffs  :: Matrix{Float64}
   half    :: Symbol                      # :upper | :lower | :diagonal (BlockDiagonalSolver) | :schur (HipSchurComplementSolver)
+  nonlinear :: Vector{Int}               # diagonal blocks that are NonlinearSystemBlocks (BlockSolverInterfaces.jl:206-214): set up again by numerical_setup!
 end
 function HipBlockTriangularSolver(solvers::AbstractVector; mats=Dict{Tuple{Int,Int},Any}(),
-                                  coeffs=fill(1.0,length(solvers),length(solvers)), half=:upper)
+                                  coeffs=fill(1.0,length(solvers),length(solvers)), half=:upper, nonlinear=Int[])
   @assert half in (:upper,:lower,:diagonal)                                   # BlockTriangularSolvers.jl:65
   @assert size(coeffs) == (length(solvers),length(solvers))
-  HipBlockTriangularSolver(collect(Any,solvers), Dict{Tuple{Int,Int},Any}(mats), Matrix{Float64}(coeffs), half)
+  @assert all(i -> 1 <= i <= length(solvers) && !haskey(mats,(i,i)), nonlinear)   # a NonlinearSystemBlock is the system's block, not a MatrixBlock
+  HipBlockTriangularSolver(collect(Any,solvers), Dict{Tuple{Int,Int},Any}(mats), Matrix{Float64}(coeffs), half, collect(Int,nonlinear))
 end
-HipBlockDiagonalSolver(solvers::AbstractVector; mats=Dict{Tuple{Int,Int},Any}()) =
-  HipBlockTriangularSolver(solvers; mats=mats, half=:diagonal)
+HipBlockDiagonalSolver(solvers::AbstractVector; mats=Dict{Tuple{Int,Int},Any}(), nonlinear=Int[]) =
+  HipBlockTriangularSolver(solvers; mats=mats, half=:diagonal, nonlinear=nonlinear)
 
 # SchurComplementSolver(A,B,C,S) (LinearSolvers/SchurComplementSolvers.jl:11-26; solve!: :55-74) on the block handle, kind
 # GMG_BLOCK_SCHUR.  A and S are, as in the reference, numerical setups where the device has them: a HipGMGNumericalSetup is
@@ -768,7 +770,7 @@ function HipSchurComplementSolver(A, B::SparseMatrixCSC, C::SparseMatrixCSC, S)
   nS = solvers[2] isa HipGMGNumericalSetup ? solvers[2].n : size(mats[(2,2)],1)
   size(B) == (nA,nS) || error("HipSchurComplementSolver: B has size $(size(B)), expected $((nA,nS))")
   size(C) == (nS,nA) || error("HipSchurComplementSolver: C has size $(size(C)), expected $((nS,nA))")
-  return HipBlockTriangularSolver(solvers, mats, fill(1.0,2,2), :schur)
+  return HipBlockTriangularSolver(solvers, mats, fill(1.0,2,2), :schur, Int[])
 end
 
 struct HipBlockFGMRESSolver <: Gridap.Algebra.LinearSolver
@@ -875,6 +877,42 @@ end
 Gridap.Algebra.numerical_setup(ss::HipBlockSymbolicSetup{HipBlockTriangularSolver}, mat::AbstractMatrix) = _block_numerical_setup(ss.solver, mat, ss.solver)
 Gridap.Algebra.numerical_setup(ss::HipBlockSymbolicSetup{HipBlockFGMRESSolver}, mat::AbstractMatrix) = _block_numerical_setup(ss.solver.Pr, mat, ss.solver)
 Gridap.Algebra.numerical_setup(ss::HipBlockSymbolicSetup{HipBlockGMRESSolver}, mat::AbstractMatrix) = _block_numerical_setup(ss.solver.P, mat, ss.solver)
+
+# numerical_setup!(ns,A[,x]) (BlockTriangularSolvers.jl:156-186, BlockDiagonalSolvers.jl:153-163): new values on the same patterns.
+# Every stored system block goes over as CSC values (gmg_block_update_values_csc: the first call per block records the transposition);
+# the solver of a diagonal block listed in `nonlinear` (NonlinearSystemBlock, BlockSolverInterfaces.jl:232-236) is set up again -- a
+# GMG block first refreshes its own handle from blocks(A)[i,i] (`smatrices[i]`: the re-assembled matrices of all its levels) --
+# the others and the MatrixBlocks (`mats`) keep their first set-up (:104-109).  x, the linearisation point, is not needed: the
+# device takes assembled matrices (GridapExtras.jl:12-14).  gmg_block_setup then works in place where the layouts allow it.
+function _block_update_values(h, i, j, M::AbstractMatrix)
+  C = M isa SparseMatrixCSC{Float64} ? M : SparseMatrixCSC{Float64,Int64}(sparse(M))
+  GC.@preserve C check_block(h, ccall((:gmg_block_update_values_csc, libgmgamd), Cint,
+    (Ptr{Cvoid},Cint,Cint,Cint,Ptr{Cvoid},Ptr{Cvoid},Ptr{Float64},Cint,Cint),
+    h, 0, i, j, C.colptr, C.rowval, C.nzval, 1, Cint(sizeof(eltype(C.colptr)))))
+end
+function Gridap.Algebra.numerical_setup!(ns::HipBlockNumericalSetup, mat::AbstractBlockMatrix, x = nothing; smatrices = nothing)
+  P = ns.solver isa HipBlockTriangularSolver ? ns.solver : (ns.solver isa HipBlockFGMRESSolver ? ns.solver.Pr : ns.solver.P)
+  B = blocks(mat); NB = length(P.solvers); h = ns.handle
+  for i in 1:NB, j in 1:NB
+    iszero(nnz(sparse(B[i,j]))) || _block_update_values(h, i-1, j-1, B[i,j])
+  end
+  ig = 0                                                    # position in ns.block_ns: the GMG blocks in order
+  for (i,s) in enumerate(P.solvers)
+    isgmg = s isa HipGMGLinearSolver || s isa HipGMGNumericalSetup
+    isgmg && (ig += 1)
+    i in P.nonlinear || continue
+    isgmg && numerical_setup!(ns.block_ns[ig], B[i,i], isnothing(smatrices) ? nothing : smatrices[i])
+    check_block(h, ccall((:gmg_block_refresh_diag_solver, libgmgamd), Cint, (Ptr{Cvoid},Cint), h, i-1))
+  end
+  check_block(h, ccall((:gmg_block_setup, libgmgamd), Cint, (Ptr{Cvoid},), h))
+  return ns
+end
+# what the last gmg_block_setup did: (kind = 1 full | 2 in place, blocks_refreshed, value_bytes, device_bytes)
+function block_setup_info(ns::HipBlockNumericalSetup)
+  k = Ref{Cint}(0); nb = Ref{Int64}(0); vb = Ref{Int64}(0); db = Ref{Int64}(0)
+  check_block(ns.handle, ccall((:gmg_block_get_setup_info, libgmgamd), Cint, (Ptr{Cvoid},Ref{Cint},Ref{Int64},Ref{Int64},Ref{Int64}), ns.handle, k, nb, vb, db))
+  return (kind = Int(k[]), blocks_refreshed = nb[], value_bytes = vb[], device_bytes = db[])
+end
 
 # block vectors are passed as their contiguous parent (BlockArrays stores a BlockVector's blocks back to back)
 _flat(v::AbstractVector) = v isa Vector{Float64} ? v : parent(v)

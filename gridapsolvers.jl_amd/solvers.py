@@ -20,7 +20,7 @@ julia/GridapSolversAMD.jl.
     BlockTriangularSolver(blocks,solvers,coeffs,half)  BlockTriangularSolvers.jl:55-85    BlockTriangularSolver
     SchurComplementSolver(A,B,C,S)  SchurComplementSolvers.jl:11-26 SchurComplementSolver (A, S = (solver, matrix) pairs)
     NullSpace(V) / NullspaceSolver(solver,N;constrain_matrix)  SolverInterfaces/NullSpaces.jl, NullspaceSolvers.jl:30-43   same names (f! = f_)
-    LinearSystemBlock / MatrixBlock BlockSolvers/BlockSolverInterfaces.jl            same names
+    LinearSystemBlock / NonlinearSystemBlock / MatrixBlock BlockSolvers/BlockSolverInterfaces.jl   same names
     symbolic_setup / numerical_setup / numerical_setup! / solve!    same names (solve_ = solve!)
     ConvergenceLog                  SolverInterfaces/ConvergenceLogs.jl:42   ConvergenceLog
 
@@ -31,6 +31,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import time
 
 import numpy as np
 
@@ -39,7 +40,7 @@ from . import abi
 __all__ = [
     "JacobiLinearSolver", "RichardsonSmoother", "GaussSeidelSmoother", "SymGaussSeidelSmoother", "PatchSolver", "BlockJacobiSolver", "LUSolver",
     "GMGLinearSolver", "CGSolver", "FGMRESSolver", "MINRESSolver", "GMRESSolver", "ConvergenceLog", "PatchProlongationOperator",
-    "RichardsonLinearSolver", "BlockDiagonalSolver", "BlockTriangularSolver", "SchurComplementSolver", "LinearSystemBlock", "MatrixBlock", "LinearSolverFromSmoother",
+    "RichardsonLinearSolver", "BlockDiagonalSolver", "BlockTriangularSolver", "SchurComplementSolver", "LinearSystemBlock", "NonlinearSystemBlock", "MatrixBlock", "LinearSolverFromSmoother",
     "NullSpace", "NullspaceSolver", "is_orthonormal", "is_orthogonal", "make_orthonormal_", "gram_schmidt_", "modified_gram_schmidt_",
     "project", "project_", "make_orthogonal_", "reconstruct", "reconstruct_",
     "symbolic_setup", "numerical_setup", "numerical_setup_", "solve_", "mul_",
@@ -286,6 +287,15 @@ class GMRESSolver:
 
 class LinearSystemBlock:
     """LinearSystemBlock(): the block is taken from the system matrix (BlockSolverInterfaces.jl)."""
+
+
+class NonlinearSystemBlock(LinearSystemBlock):
+    """NonlinearSystemBlock(ids=()) -- BlockSolverInterfaces.jl:206-214: a block taken from the system matrix whose solver is set
+    up again by numerical_setup!(ns, A, x) (:232-236); a LinearSystemBlock keeps its first set-up (:104-109).  `ids` names the
+    blocks of x the block depends on (the reference's `I`); the device takes assembled matrices, so it is stored only."""
+
+    def __init__(self, ids=()):
+        self.ids = tuple(ids) if isinstance(ids, (tuple, list)) else (ids,)
 
 
 class MatrixBlock:
@@ -875,6 +885,47 @@ class BlockNumericalSetup:
             self.close()
             raise
 
+    # -- numerical_setup!(ns, A, x): BlockTriangularSolvers.jl:156-186, BlockDiagonalSolvers.jl:153-163
+    def update(self, mat, smatrices=None):
+        """numerical_setup!(ns, A): new values on the same patterns.  Every present system block is handed over again; the solver
+        of a NonlinearSystemBlock diagonal block is set up again (a GMGLinearSolver first refreshes its own handle from mat[i][i];
+        `smatrices[i]`, optional, = the re-assembled matrices of all its levels), LinearSystemBlock and MatrixBlock solvers keep
+        theirs (BlockSolverInterfaces.jl:104-118,232-236)."""
+        lib, h = self._lib, self.h
+        nb = len(self.solver.solvers)
+        if len(mat) != nb or any(len(r) != nb for r in mat):
+            raise ValueError("block matrix does not match the number of solvers")
+        t0 = time.perf_counter()
+        for i in range(nb):
+            for j in range(nb):
+                if mat[i][j] is None:
+                    continue
+                shape, ptr, idx, val, layout, base = _csr_fields(mat[i][j])
+                if layout == abi.CSC:
+                    st = lib.gmg_block_update_values_csc(h, abi.BLOCK_SLOT_SYSTEM, i, j, C.c_void_p(ptr.ctypes.data),
+                                                         C.c_void_p(idx.ctypes.data), C.c_void_p(val.ctypes.data), base, ptr.dtype.itemsize)
+                else:
+                    st = lib.gmg_block_update_values(h, abi.BLOCK_SLOT_SYSTEM, i, j, C.c_void_p(val.ctypes.data))
+                abi.check_block(h, st)
+        t1 = time.perf_counter()
+        for i, sv in enumerate(self.solver.solvers):
+            if not isinstance(self.solver.blocks[i][i], NonlinearSystemBlock):
+                continue
+            if isinstance(sv, GMGLinearSolver):
+                self.block_ns[i].update(mat[i][i], None if smatrices is None else smatrices[i])
+            abi.check_block(h, lib.gmg_block_refresh_diag_solver(h, i))
+        t2 = time.perf_counter()
+        abi.check_block(h, lib.gmg_block_setup(h))
+        # seconds of the last update: values recorded on the host copies / the GMG handles' own refresh / gmg_block_setup
+        self.update_seconds = dict(record=t1 - t0, gmg=t2 - t1, block_setup=time.perf_counter() - t2)
+        return self
+
+    def setup_info(self):
+        """what the last gmg_block_setup did: kind (1 full, 2 in place), blocks_refreshed, value_bytes, device_bytes"""
+        k, v = C.c_int(0), [C.c_int64(0) for _ in range(3)]
+        abi.check_block(self.h, self._lib.gmg_block_get_setup_info(self.h, C.byref(k), *[C.byref(q) for q in v]))
+        return dict(zip(("kind", "blocks_refreshed", "value_bytes", "device_bytes"), (k.value,) + tuple(q.value for q in v)))
+
     def _fill_logs(self):
         """copy the block solvers' ConvergenceLogs back (their last application)"""
         for i, sv in enumerate(self.solver.solvers):
@@ -1293,15 +1344,17 @@ def numerical_setup(ss, A=None, device_id=None):
     raise TypeError(f"no numerical_setup for {type(ss).__name__}")
 
 
-def numerical_setup_(ns, A, smatrices=None):
-    """Gridap.Algebra.numerical_setup!(ns, A) (smatrices: re-assembled matrices of all levels, optional)."""
-    if isinstance(ns, GMGNumericalSetup):
+def numerical_setup_(ns, A, smatrices=None, x=None):
+    """Gridap.Algebra.numerical_setup!(ns, A[, x]) (smatrices: re-assembled matrices of all levels, optional; for a block solver one
+    list per diagonal block).  `x`, the linearisation point, is accepted and unused: the device takes assembled matrices
+    (GridapExtras.jl:12-14 falls back to numerical_setup!(ns, A) in the same way)."""
+    if isinstance(ns, (GMGNumericalSetup, BlockNumericalSetup)):
         return ns.update(A, smatrices)
-    if isinstance(ns, _KrylovNumericalSetup):
+    if isinstance(ns, _KrylovNumericalSetup):                  # FGMRESSolvers.jl:112-128: forwarded to the preconditioner
         ns.P_ns.update(A, smatrices)
         return ns
     if isinstance(ns, NullspaceNumericalSetup):                # NullspaceSolvers.jl:77-90: forwarded; the null space stays on the handle
-        numerical_setup_(ns.ns, A, smatrices)
+        numerical_setup_(ns.ns, A, smatrices, x)
         return ns
     raise TypeError(f"no numerical_setup! for {type(ns).__name__}")
 

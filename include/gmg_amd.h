@@ -670,8 +670,45 @@ GMG_API int gmg_block_set_diag_solver(gmg_block_handle_t h, int i, int kind, int
  * pressure mass matrix, StokesGMG.jl:145) */
 GMG_API int gmg_block_set_diag_matrix(gmg_block_handle_t h, int i, int64_t n, int64_t nnz, const void *ptr,
                                       const void *idx, const double *val, int layout, int index_base, int index_bytes);
-/* numerical_setup */
+/* numerical_setup; after gmg_block_update_values* / gmg_block_refresh_diag_solver: numerical_setup! (see below) */
 GMG_API int gmg_block_setup(gmg_block_handle_t h);
+/* ---- numerical_setup!(ns,A,x) of a block solver: new values on the same patterns, once per Newton step
+ * (NonlinearSolvers/NewtonRaphsonSolver.jl:45,73 -> FGMRESSolvers.jl:112-128 -> BlockTriangularSolvers.jl:156-186 /
+ * BlockDiagonalSolvers.jl:153-163 -> BlockSolverInterfaces.jl:104-118,232-236 -> GMGLinearSolvers.jl:260-297).
+ * The update calls record the values on the handle's host copy of the block and mark it; gmg_block_setup must be called again.
+ * GMG_ERR_STATE before the first gmg_block_setup; GMG_ERR_INVALID, with nothing changed, for an absent block, a wrong slot or a CSC
+ * pattern whose size disagrees with the stored block.  When nothing but values changed since the last setup (no block set again, no
+ * solver, partition or communicator changed, no coefficient changed from or to zero), the communicator has one rank, GMG_REFRESH
+ * is not 0 and every changed block is stored with explicit values (CSR-stream or SELL-64: the rule of gmg_update_values), that
+ * gmg_block_setup works IN PLACE: nothing is freed or allocated -- work vectors, Krylov bases, attachments stay -- and each changed
+ * block costs one host-to-device copy of its values and a refill on the device.  Otherwise it is a full setup.  Both give the
+ * same bits and keep the same state: the internal solution vector (the initial guesses of CG-Jacobi block solvers, the Schur
+ * solver's du: the reference keeps its work caches across numerical_setup!) and a null space set on the handle survive either.
+ * Which solvers are set up again follows the reference:
+ *  - a diagonal block marked with gmg_block_refresh_diag_solver (NonlinearSystemBlock, BlockSolverInterfaces.jl:206-214,232-236):
+ *    Jacobi / CG-Jacobi recompute D^-1 from the current values of their matrix (a zero diagonal: GMG_ERR_SINGULAR naming the block), LU
+ *    rebuilds its dense inverse; for a GMG block the caller has refreshed the GMG handle itself (gmg_update_values* + gmg_setup on
+ *    it, which leave it attached and on the block handle's stream) and the block handle only checks that it is set up;
+ *  - a block that is not marked (LinearSystemBlock, MatrixBlock, :104-109) keeps its D^-1 / inverse EVEN WHEN system block (i,i) was
+ *    updated: a Jacobi / CG-Jacobi block that streams the system's own (i,i) block then iterates on the new operator with the
+ *    old D^-1 -- what the reference's aliasing gives when jacobian! updates A in place;
+ *  - an off-diagonal preconditioner block without a gmg_block_set_precond_block entry IS the system block's storage and follows it.
+ * Marks hold for one gmg_block_setup. */
+enum gmg_block_slot { GMG_BLOCK_SLOT_SYSTEM = 0, GMG_BLOCK_SLOT_PRECOND = 1, GMG_BLOCK_SLOT_DIAG_MATRIX = 2 };
+/* same pattern, new values, in the order of the arrays handed to gmg_block_set_system_block / _precond_block /
+ * _diag_matrix (slot DIAG_MATRIX: j is ignored).  CSR-set blocks: values in CSR order. */
+GMG_API int gmg_block_update_values(gmg_block_handle_t h, int slot, int i, int j, const double *val);
+/* blocks that were set in GMG_CSC layout (GMG_ERR_STATE otherwise): nzval in CSC order; the first call per block also takes the
+ * unchanged colptr / rowidx and records the transposition, later calls may pass NULL for both (as gmg_update_values_csc) */
+GMG_API int gmg_block_update_values_csc(gmg_block_handle_t h, int slot, int i, int j, const void *colptr, const void *rowidx,
+                                        const double *val, int index_base, int index_bytes);
+/* block_numerical_setup!(NonlinearSystemBlock, ...), BlockSolverInterfaces.jl:232-236: the solver of diagonal block i is set up
+ * again at the next gmg_block_setup from the current values of its matrix */
+GMG_API int gmg_block_refresh_diag_solver(gmg_block_handle_t h, int i);
+/* what the last gmg_block_setup did: kind 1 = full, 2 = in place; blocks whose values were (re)written; bytes of
+ * values sent to the device; device bytes the handle holds now.  NULL pointers are skipped. */
+GMG_API int gmg_block_get_setup_info(gmg_block_handle_t h, int *kind, int64_t *blocks_refreshed, int64_t *value_bytes,
+                                     int64_t *device_bytes);
 /* solve!(x,ns::BlockDiagonalSolverNS|BlockTriangularSolverNS,b) */
 GMG_API int gmg_block_precond_apply(gmg_block_handle_t h, const double *b, double *x, int memspace);
 /* mul!(y,A,x) on the block system */
