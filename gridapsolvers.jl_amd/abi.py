@@ -20,7 +20,8 @@ OP_A, OP_P, OP_R = 0, 1, 2
 LEVEL_KRYLOV = -1          # GMG_LEVEL_KRYLOV: the separate Krylov operator of a finest level in the overlapping layout
 COARSE_DENSE_INVERSE, COARSE_CG_JACOBI, COARSE_HOST_CALLBACK = 0, 1, 2
 BLOCK_DIAGONAL, BLOCK_LOWER, BLOCK_UPPER, BLOCK_SCHUR = 0, 1, 2, 3
-BLOCK_GMG, BLOCK_CG_JACOBI, BLOCK_LU, BLOCK_JACOBI = 1, 2, 3, 4
+BLOCK_GMG, BLOCK_CG_JACOBI, BLOCK_LU, BLOCK_JACOBI, BLOCK_KRYLOV_GMG = 1, 2, 3, 4, 5
+KRYLOV_CG, KRYLOV_FGMRES, KRYLOV_GMRES = 1, 2, 3
 BLOCK_SLOT_SYSTEM, BLOCK_SLOT_PRECOND, BLOCK_SLOT_DIAG_MATRIX = 0, 1, 2
 
 
@@ -161,6 +162,8 @@ SYMBOLS = {
                                     C.c_void_p, C.c_int, C.c_int, C.c_int],
     "gmg_block_set_coeff": [C.c_void_p, C.c_int, C.c_int, C.c_double],
     "gmg_block_set_diag_gmg": [C.c_void_p, C.c_int, C.c_void_p],
+    "gmg_block_set_diag_krylov_gmg": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_double, C.c_double],
     "gmg_block_set_diag_solver": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double],
     "gmg_block_set_diag_matrix": [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_int, C.c_int, C.c_int],
@@ -180,6 +183,7 @@ SYMBOLS = {
     "gmg_block_gmres_solve": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                               C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Result), C.c_void_p, C.c_int],
     "gmg_block_diag_log": [C.c_void_p, C.c_int, C.POINTER(Result)],
+    "gmg_block_diag_stats": [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
     "gmg_block_nullspace_set": [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int],
     "gmg_block_nullspace_get": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int],
     "gmg_block_nullspace_size": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64)],

@@ -7,11 +7,15 @@
 //   BlockTriangularSolver solve!: src/BlockSolvers/BlockTriangularSolvers.jl:186-242
 //   SchurComplementSolver solve!: src/LinearSolvers/SchurComplementSolvers.jl:55-74 (2 blocks: A = block 0, S = block 1)
 // Block vectors are contiguous on the device, block i at off[i]..off[i+1].  Diagonal-block solvers:
-// a set-up gmg handle, CGSolver(JacobiLinearSolver()), LUSolver() (small blocks) or JacobiLinearSolver().
+// a set-up gmg handle, CGSolver(JacobiLinearSolver()), LUSolver() (small blocks), JacobiLinearSolver(), or a Krylov solver around a
+// set-up gmg handle (GMG_BLOCK_KRYLOV_GMG: FGMRESSolver(m,gmg) / GMRESSolver(m;Pr|Pl=gmg) / CGSolver(gmg), NavierStokesGMG.jl:159-169).
 
 struct BlockDiag {
   int kind = 0;                 // gmg_block_diag_kind, 0 = not set
-  gmg_solver *g = nullptr;      // GMG_BLOCK_GMG (borrowed)
+  gmg_solver *g = nullptr;      // GMG_BLOCK_GMG, GMG_BLOCK_KRYLOV_GMG (borrowed)
+  int krylov = 0, m = 0, m_add = 1, side = 0;   // GMG_BLOCK_KRYLOV_GMG: gmg_krylov_kind and the solver's sizes (side: 0 = Pr, 1 = Pl)
+  bool restart = false, flexible = false;
+  int64_t napplies = 0, total_iters = 0;        // gmg_block_diag_stats: since the last gmg_block_setup
   HostCSR hM;                   // matrix of the block solver (MatrixBlock / BiformBlock); empty: system block (i,i)
   bool hasM = false;
   DevCSR M;
@@ -91,7 +95,7 @@ struct gmg_block_solver {
     for (auto &kv : msys) kv.second.dirty = false;
     for (auto &kv : mpre) kv.second.dirty = false;
     for (auto &m : mdiag) m.dirty = false;
-    for (auto &D : diag) D.refresh = false;
+    for (auto &D : diag) { D.refresh = false; D.napplies = 0; D.total_iters = 0; }
   }
 
   // the device form of a dirty block (nullptr: it has none, e.g. the matrix of an LU block)
@@ -158,7 +162,7 @@ struct gmg_block_solver {
       for (int i = 0; i < nb; ++i) {
         BlockDiag &D = diag[i];
         if (!D.refresh) continue;
-        if (D.kind == GMG_BLOCK_GMG)                         // the caller has refreshed the GMG handle itself (gmg_update_values* + gmg_setup)
+        if (D.kind == GMG_BLOCK_GMG || D.kind == GMG_BLOCK_KRYLOV_GMG)   // the caller has refreshed the GMG handle itself (gmg_update_values* + gmg_setup)
           REQUIRE(D.g && D.g->setup_done, GMG_ERR_STATE, "the GMG handle of block " + std::to_string(i) + " is not set up");
         else if (D.kind == GMG_BLOCK_LU) {
           HIP_CHECK(hipStreamSynchronize(eng.stream));
@@ -191,6 +195,11 @@ struct gmg_block_solver {
       REQUIRE(hpre.count({0, 1}) || hsys.count({0, 1}), GMG_ERR_STATE, "Schur complement solver: block (0,1) (B) is missing: no precond block and no system block");
       REQUIRE(hpre.count({1, 0}) || hsys.count({1, 0}), GMG_ERR_STATE, "Schur complement solver: block (1,0) (C) is missing: no precond block and no system block");
     }
+    // a Krylov solver around a GMG: the nested solve uses the GMG handle's scalar slots, mailbox and basis caches and reduces on its own rank only
+    for (int i = 0; i < nb; ++i)
+      if (diag[i].kind == GMG_BLOCK_KRYLOV_GMG)
+        REQUIRE(!distributed() && (!diag[i].g || diag[i].g->comm.nranks == 1), GMG_ERR_UNSUPPORTED,
+                "the Krylov solver around the GMG of block " + std::to_string(i) + " is single-GPU (no partitioned nested solve)");
     // State that numerical_setup! keeps (the reference's work caches): y -- the initial guesses of the CG block solvers and the
     // Schur solver's du -- on every later setup; and, when only values changed (the fallback of the in-place path), D^-1 / the
     // inverse of the diagonal solvers that are NOT marked, so that both paths of gmg_block_setup give the same bits.
@@ -241,8 +250,10 @@ struct gmg_block_solver {
       BlockDiag &D = diag[i];
       REQUIRE(D.kind != 0, GMG_ERR_STATE, "no solver set for diagonal block " + std::to_string(i));
       const int64_t n = bsize(i);
-      if (D.kind == GMG_BLOCK_GMG) {
+      if (D.kind == GMG_BLOCK_GMG || D.kind == GMG_BLOCK_KRYLOV_GMG) {
         gmg_solver *g = D.g;
+        if (D.kind == GMG_BLOCK_KRYLOV_GMG)
+          REQUIRE(!g || !g->has_outer(), GMG_ERR_UNSUPPORTED, "the GMG handle of block " + std::to_string(i) + " has its finest level in the overlapping layout");
         REQUIRE(g && g->setup_done, GMG_ERR_STATE, "the GMG handle of block " + std::to_string(i) + " is not set up");
         REQUIRE(g->device == eng.device, GMG_ERR_INVALID, "GMG handle lives on another device");
         REQUIRE(g->comm.nranks == eng.comm.nranks, GMG_ERR_INVALID, "the GMG handle of block " + std::to_string(i) + " and the block solver must span the same ranks");
@@ -359,7 +370,30 @@ struct gmg_block_solver {
         eng.copy(yi, D.g->cg_x, n);
       } else
       D.g->gmg_solve_dev(yi, wi, -1.0);
+      D.napplies += 1; D.total_iters += D.g->log.num_iters;
       break;
+    case GMG_BLOCK_KRYLOV_GMG: {
+      // solve!(yi,ns,wi) of FGMRESSolver(m,gmg) / GMRESSolver(m;Pr|Pl=gmg) / CGSolver(gmg) on the GMG handle's own finest matrix: the
+      // operator, caches (fg_V / fg_Z, gm_*, cg_*), scalar slots and mailbox of gmg_fgmres_solve / gmg_gmres_solve / gmg_cg_solve, on
+      // the block handle's stream.  The outer solve reduces on the block engine: the two never share a slot.  Slots on the GMG handle:
+      // FGMRES / GMRES 1..j+1, norm / dot 0, a nested cg_core kScalarSlots - 8*depth (the GMG's coarsest CG-Jacobi one depth further).
+      // yi keeps its previous content: the initial guess (FGMRESSolvers.jl:136, GMRESSolvers.jl:143, CGSolvers.jl:79).
+      gmg_solver &S = *D.g;
+      D.log.configure(D.maxiter, D.atol, D.rtol);
+      if (D.krylov == GMG_KRYLOV_CG) {
+        KrylovOps ops = S.level0_ops(1);
+        cg_core(S, n, wi, yi, S.cg_w, S.cg_p, S.cg_z, S.cg_r, ops, D.flexible, D.log);
+      } else if (D.krylov == GMG_KRYLOV_FGMRES) {
+        KrylovOps ops = S.level0_ops(1);
+        fgmres_core(S, n, S.lev[0].nvec, wi, yi, S.fg_V, S.fg_Z, ops, D.m, D.restart, D.m_add, D.log, true);
+      } else {
+        KrylovOps ops = S.level0_ops(D.side == 0 ? 1 : 0);
+        if (D.side == 1) ops.precond_left = [&S](double *z, const double *r) { S.krylov_precond(1, z, r, -1.0); };
+        gmres_core(S, n, S.lev[0].nvec, wi, yi, ops, D.m, D.restart, D.m_add, D.log);
+      }
+      D.napplies += 1; D.total_iters += D.log.num_iters;
+      break;
+    }
     case GMG_BLOCK_CG_JACOBI: {                           // yi keeps its previous content: CG's initial guess
       KrylovOps ops;
       ops.resid = [&, i](double *x, const double *b, double *r) { eng.spmv_resid(D.M, with_ghosts(i, x), b, r); };
@@ -370,6 +404,7 @@ struct gmg_block_solver {
       };
       D.log.configure(D.maxiter, D.atol, D.rtol);
       cg_core(eng, n, wi, yi, D.w, D.p, D.z, D.r, ops, false, D.log);
+      D.napplies += 1; D.total_iters += D.log.num_iters;
       break;
     }
     case GMG_BLOCK_LU:
@@ -648,6 +683,34 @@ int gmg_block_set_diag_gmg(gmg_block_handle_t h, int i, gmg_handle_t g)
   });
 }
 
+int gmg_block_set_diag_krylov_gmg(gmg_block_handle_t h, int i, gmg_handle_t g, int krylov, int m, int restart, int m_add, int flexible,
+                                  int side, int maxiter, double atol, double rtol)
+{
+  return guarded_b(h, [&] {
+    check_block(h, i);
+    REQUIRE(g, GMG_ERR_INVALID, "null GMG handle");
+    REQUIRE(krylov == GMG_KRYLOV_CG || krylov == GMG_KRYLOV_FGMRES || krylov == GMG_KRYLOV_GMRES, GMG_ERR_INVALID,
+            "krylov must be GMG_KRYLOV_CG, GMG_KRYLOV_FGMRES or GMG_KRYLOV_GMRES");
+    REQUIRE(side == 0 || side == 1, GMG_ERR_INVALID, "side must be 0 (Pr) or 1 (Pl)");
+    REQUIRE(krylov != GMG_KRYLOV_FGMRES || side == 0, GMG_ERR_INVALID, "FGMRES takes the GMG as Pr (side 0)");
+    REQUIRE(krylov != GMG_KRYLOV_CG || side == 1, GMG_ERR_INVALID, "CG takes the GMG as Pl (side 1)");
+    if (krylov != GMG_KRYLOV_CG) REQUIRE(m >= 1 && m_add >= 1, GMG_ERR_INVALID, "bad Krylov basis sizes (m < 1 or m_add < 1)");
+    REQUIRE(maxiter >= 0, GMG_ERR_INVALID, "maxiter < 0");
+    REQUIRE(g->setup_done, GMG_ERR_INVALID, "the GMG handle of block " + std::to_string(i) + " is not set up");
+    REQUIRE(g->lev[0].n == h->bsize(i), GMG_ERR_INVALID, "GMG handle size does not match block " + std::to_string(i));
+    BlockDiag &D = h->diag[i];
+    if (D.g && D.g != g) {
+      if (D.g->stream == h->eng.stream) D.g->stream = D.g->own_stream;
+      if (D.g->attached_to == h) D.g->attached_to = nullptr;
+    }
+    D = BlockDiag();
+    D.kind = GMG_BLOCK_KRYLOV_GMG; D.g = g;
+    D.krylov = krylov; D.m = m; D.restart = restart != 0; D.m_add = m_add; D.flexible = flexible != 0; D.side = side;
+    D.maxiter = maxiter; D.atol = atol; D.rtol = rtol;
+    h->touch();
+  });
+}
+
 int gmg_block_set_diag_solver(gmg_block_handle_t h, int i, int kind, int maxiter, double atol, double rtol)
 {
   return guarded_b(h, [&] {
@@ -656,6 +719,7 @@ int gmg_block_set_diag_solver(gmg_block_handle_t h, int i, int kind, int maxiter
     REQUIRE(maxiter >= 0, GMG_ERR_INVALID, "maxiter < 0");
     BlockDiag &D = h->diag[i];
     if (D.g && D.g->stream == h->eng.stream) D.g->stream = D.g->own_stream;
+    if (D.g && D.g->attached_to == h) D.g->attached_to = nullptr;   // (the GMG handle is free again: another block handle may take it)
     HostCSR keep;
     const bool had = D.hasM;
     if (had) keep = std::move(D.hM);
@@ -896,6 +960,19 @@ int gmg_block_diag_log(gmg_block_handle_t h, int i, gmg_result *res)
     REQUIRE(!L->residuals.empty(), GMG_ERR_STATE, "this block solver keeps no convergence log");
     const size_t k = std::min<size_t>((size_t)L->num_iters, L->residuals.size() - 1);
     L->export_to(res, nullptr, 0, L->residuals[k]);
+  });
+}
+
+int gmg_block_diag_stats(gmg_block_handle_t h, int i, int64_t *napplies, int64_t *total_iters)
+{
+  return guarded_b(h, [&] {
+    REQUIRE(h, GMG_ERR_INVALID, "null handle");
+    check_block(h, i);
+    const BlockDiag &D = h->diag[i];
+    REQUIRE(D.kind == GMG_BLOCK_GMG || D.kind == GMG_BLOCK_CG_JACOBI || D.kind == GMG_BLOCK_KRYLOV_GMG, GMG_ERR_STATE,
+            "this block solver is not iterative");
+    if (napplies) *napplies = D.napplies;
+    if (total_iters) *total_iters = D.total_iters;
   });
 }
 

@@ -737,6 +737,25 @@ struct gmg_solver {
     gm_tab_n = nvec;
     return gm_tab;
   }
+  // FGMRES (option fgmres_fused): the device table of the Z pointers gmres_combine_kernel loops over for x += sum g_i Z_i.  One table
+  // per engine (the caller's Z cache is the engine's own: fg_Z of a GMG handle, fg_Z of a block handle); fz_host = what it holds.
+  const double **fz_tab = nullptr;
+  int fz_tab_cap = 0;
+  std::vector<double *> fz_host;
+  const double *const *fgmres_table(const std::vector<double *> &Z, int j)
+  {
+    if ((int)fz_host.size() >= j && std::equal(Z.begin(), Z.begin() + j, fz_host.begin())) return fz_tab;
+    HIP_CHECK(hipStreamSynchronize(stream));                 // (no launch may still be reading the table that is replaced)
+    const int nvec = (int)Z.size();
+    if (nvec > fz_tab_cap) {
+      if (fz_tab) release(fz_tab, (size_t)fz_tab_cap);
+      fz_tab_cap = std::max(2 * fz_tab_cap, nvec + 7);
+      fz_tab = dalloc<const double *>((size_t)fz_tab_cap);
+    }
+    HIP_CHECK(hipMemcpy(fz_tab, Z.data(), sizeof(double *) * (size_t)nvec, hipMemcpyHostToDevice));
+    fz_host = Z;
+    return fz_tab;
+  }
   // staging buffers for host-memory callers
   double *st_b = nullptr, *st_x = nullptr;
   std::vector<double *> st_extra;
@@ -938,6 +957,7 @@ struct gmg_solver {
     fg_V.clear(); fg_Z.clear(); st_extra.clear();
     mr_vec.clear(); mr_parts = nullptr; mr_nv = 0;
     gm_V.clear(); gm_zl = gm_zr = nullptr; gm_tab = nullptr; gm_tab_cap = gm_tab_n = 0; gm_nv = 0;
+    fz_tab = nullptr; fz_tab_cap = 0; fz_host.clear();
     setup_done = false;
   }
 
@@ -4422,8 +4442,13 @@ static double cg_core(gmg_solver &S, int64_t n, const double *db, double *dx, do
 // solve!(x,ns::FGMRESNumericalSetup,b), Krylov/FGMRESSolvers.jl:130-199.  V/Z are the caller's basis
 // caches (:58-70); they grow by m_add when the basis outgrows them (:151-154).  nv = allocation length
 // of a basis vector (n plus ghost space in distributed runs).
+// Fused path (option fgmres_fused: -1 = in solves nested in a block preconditioner (`nested`) only, 0 = never, 1 = always; one rank or
+// rank-local reductions): the twin of gmres_core's -- column j is one dot_partial_kernel launch, j gmres_mgs_kernel launches on V and
+// gmres_normalize_kernel, which posts the column to the host; the solution update x += sum g_i Z_i is one gmres_combine_kernel over
+// the table of the Z pointers (x may be a sub-vector of a block vector, 8-byte aligned only: the kernel's scalar form then).  Both
+// paths perform the same floating-point operations in the same order.
 static double fgmres_core(gmg_solver &S, int64_t n, int64_t nv, const double *db, double *dx, std::vector<double *> &V,
-                   std::vector<double *> &Z, const KrylovOps &ops, int m0, bool restart, int m_add, ConvLog &log)
+                   std::vector<double *> &Z, const KrylovOps &ops, int m0, bool restart, int m_add, ConvLog &log, bool nested = false)
 {
   int m = std::max<int>(m0, (int)Z.size());
   while ((int)V.size() < m + 1) V.push_back(S.dvec(nv));
@@ -4445,6 +4470,10 @@ static double fgmres_core(gmg_solver &S, int64_t n, int64_t nv, const double *db
     hcap = newcap; ldh = nld;
   };
   const int grid = gmg_solver::grid_for(n);
+  const int fopt = S.opt_int("GMG_FGMRES_FUSED", -1);
+  const bool fuse = (fopt > 0 || (fopt < 0 && nested)) && S.fuse_reductions();
+  const bool post = fuse && S.opt_int("GMG_HOST_POLL", 1) != 0;
+  auto aligned16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
 
   // krylov_residual!(V[1],x,A,b,Pl,zl): KrylovUtils.jl:46-54 ; FGMRESSolvers.jl:136-140
   auto residual = [&](double *out) {
@@ -4473,17 +4502,45 @@ static double fgmres_core(gmg_solver &S, int64_t n, int64_t nv, const double *db
       else S.copy(Zj, V[j - 1], n);
       if (ops.precond_left) { ops.apply(Zj, ops.zl); ops.precond_left(Vn, ops.zl); }   // krylov_mul! with Pl, KrylovUtils.jl:14-18
       else ops.apply(Zj, Vn);                            // :159
-      for (int i = 1; i <= j; ++i) {                     // :160-163 modified Gram-Schmidt
-        S.dot_async(n, Vn, V[i - 1], i, false);
-        hipLaunchKernelGGL(axmy_dev_kernel, dim3(grid), dim3(256), 0, S.stream, n, S.d_scalars + i, V[i - 1], Vn);
+      // (the fused kernels take dot_partial_kernel's order for 16-byte aligned operands: the basis is dvec's, aligned by hipMalloc)
+      bool al = fuse && aligned16(Vn);
+      for (int i = 0; al && i < j; ++i) al = aligned16(V[i]);
+      if (al) {
+        double *pin = S.d_partials, *pout = S.d_partials2;
+        int np = S.dot_partials(n, Vn, V[0], pin);       // first stage of H[1,j] (:161)
+        const int nbd = gmg_solver::dot_grid(n);
+        for (int i = 1; i <= j; ++i) {                   // :160-163 ; the last launch leaves the partials of norm(V[j+1])^2 (:164)
+          hipLaunchKernelGGL(gmres_mgs_kernel, dim3(nbd), dim3(kBlock), 0, S.stream, n, Vn, V[i - 1],
+                             i < j ? (const double *)V[i] : (const double *)nullptr, i < j ? 0 : 1, pin, np, S.d_scalars + i, pout);
+          HIP_CHECK(hipGetLastError());
+          std::swap(pin, pout);
+          np = nbd;
+        }
+        unsigned long long want = 0;
+        if (post) { S.need_mail_col(); want = ++S.mail_seq; }
+        hipLaunchKernelGGL(gmres_normalize_kernel, dim3(grid), dim3(kBlock), 0, S.stream, n, Vn, pin, np, S.d_scalars + 1, j + 1,
+                           S.d_mail_col, post ? &S.d_mail->value : nullptr, post ? &S.d_mail->seq : nullptr, want);   // :164-165
+        HIP_CHECK(hipGetLastError());
+        if (post) {
+          S.posted = want;
+          (void)S.fetch_scalar(j + 1);                   // waits for the number: the column is in the mailbox
+          for (int i = 1; i <= j + 1; ++i) Hm(i, j) = S.h_mail_col[i - 1];
+        }
+      } else {
+        for (int i = 1; i <= j; ++i) {                   // :160-163 modified Gram-Schmidt
+          S.dot_async(n, Vn, V[i - 1], i, false);
+          hipLaunchKernelGGL(axmy_dev_kernel, dim3(grid), dim3(256), 0, S.stream, n, S.d_scalars + i, V[i - 1], Vn);
+          HIP_CHECK(hipGetLastError());
+        }
+        S.dot_async(n, Vn, Vn, j + 1, true);             // :164
+        hipLaunchKernelGGL(div_dev_kernel, dim3(grid), dim3(256), 0, S.stream, n, S.d_scalars + (j + 1), Vn); // :165
         HIP_CHECK(hipGetLastError());
       }
-      S.dot_async(n, Vn, Vn, j + 1, true);               // :164
-      hipLaunchKernelGGL(div_dev_kernel, dim3(grid), dim3(256), 0, S.stream, n, S.d_scalars + (j + 1), Vn); // :165
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipMemcpyAsync(S.h_scalars + 1, S.d_scalars + 1, sizeof(double) * (size_t)(j + 1), hipMemcpyDeviceToHost, S.stream));
-      HIP_CHECK(hipStreamSynchronize(S.stream));
-      for (int i = 1; i <= j + 1; ++i) Hm(i, j) = S.h_scalars[i];
+      if (!(al && post)) {
+        HIP_CHECK(hipMemcpyAsync(S.h_scalars + 1, S.d_scalars + 1, sizeof(double) * (size_t)(j + 1), hipMemcpyDeviceToHost, S.stream));
+        HIP_CHECK(hipStreamSynchronize(S.stream));
+        for (int i = 1; i <= j + 1; ++i) Hm(i, j) = S.h_scalars[i];
+      }
       for (int i = 1; i <= j - 1; ++i) {                 // :168-172
         const double gm = c[i - 1] * Hm(i, j) + s[i - 1] * Hm(i + 1, j);
         Hm(i + 1, j) = -s[i - 1] * Hm(i, j) + c[i - 1] * Hm(i + 1, j);
@@ -4517,6 +4574,16 @@ static double fgmres_core(gmg_solver &S, int64_t n, int64_t nv, const double *db
       for (int k = i + 1; k <= j; ++k) acc += Hm(i, k) * g[k - 1];
       g[i - 1] = (g[i - 1] - acc) / Hm(i, i);
     }
+    if (fuse && j > 0) {                                 // :191-193 in one pass over the table of Z
+      bool vec = aligned16(dx);
+      for (int i = 0; i < j; ++i) vec = vec && aligned16(Z[i]);
+      const double *const *tab = S.fgmres_table(Z, j);
+      for (int i = 1; i <= j; ++i) S.h_scalars[i] = g[i - 1];
+      HIP_CHECK(hipMemcpyAsync(S.d_scalars + 1, S.h_scalars + 1, sizeof(double) * (size_t)j, hipMemcpyHostToDevice, S.stream));
+      hipLaunchKernelGGL(gmres_combine_kernel, dim3(grid), dim3(kBlock), 0, S.stream, n, dx, (const double *)dx, tab, S.d_scalars + 1, j,
+                         vec ? 1 : 0);
+      HIP_CHECK(hipGetLastError());
+    } else
     for (int i = 1; i <= j; ++i) {                       // :191-193
       hipLaunchKernelGGL(axpy_kernel, dim3(grid), dim3(256), 0, S.stream, n, g[i - 1], Z[i - 1], dx);
       HIP_CHECK(hipGetLastError());
@@ -7007,7 +7074,7 @@ const OptionKey kOptionKeys[] = {
   {"GMG_PAT_WIDE_ROUNDS", false}, {"GMG_PERSIST", false}, {"GMG_PERSIST_FENCED", false}, {"GMG_PERSIST_FOLD", false}, {"GMG_PERSIST_MAX_SLICES", false}, {"GMG_PERSIST_REGS", false},
   {"GMG_PERSIST_SHARED", false}, {"GMG_PROF_STRIDE", true}, {"GMG_REFRESH", true}, {"GMG_SELL", false}, {"GMG_SELL_BLOCK", false},
   {"GMG_SELL_DEFER", false}, {"GMG_SELL_MAXPAD", false}, {"GMG_SELL_UN", false}, {"GMG_SETUP_TIMING", true}, {"GMG_VDICT", false},
-  {"GMG_XCD_REMAP", false}, {"GMG_XCD_REMAP_BIG", false}, {"GMG_X0_ZERO", true}, {"GMG_HOST_POLL", true}, {"GMG_HOST_CHUNK_BYTES", true}, {"GMG_PAT_FMA", false}, {"GMG_PAT_R2", false}, {"GMG_RED_FUSED", false}, {"GMG_GMRES_FUSED", true}, {"GMG_NULLSPACE_FUSED", true}, {"GMG_PAT_R2MV", false}, {"GMG_PAT_R2_OCC", false}, {"GMG_PAT_PAIR_P", false}, {"GMG_PAT_R2MV_DOT", false}, {"GMG_PERSIST_WPB", false}, {"GMG_HOST_TIMELINE", true}, {"GMG_PAT_R2MV_MIN", false}, {"GMG_PAT_BCAST", false}, {"GMG_PAT_R2_WGS", false}, {"GMG_PAT_ZWALK", false}, {"GMG_PAT_ZWALK_T", false}, {"GMG_PAT_ZWALK_ROWS", false}, {"GMG_PAT_ZWALK_MV", false}, {"GMG_PAT_ZWALK_WIDE", false}, {"GMG_PAT_ZWALK_WIDE_ROWS", false}, {"GMG_PAT_FUSE2", false}, {"GMG_PAT_FUSE2_W", false}, {"GMG_PAT_FUSE2_T", false}, {"GMG_PAT_FUSE2_ROWS", false}, {"GMG_PAT_FUSE2_BOX", false}, {"GMG_PAT_BOX", false}, {"GMG_PAT_WIDE_GRID", false}, {"GMG_PAT_BOX_T", false}, {"GMG_PAT_BOX_MIN_ROWS", false}, {"GMG_PAT_BOX_MAX_ROWS", false},
+  {"GMG_XCD_REMAP", false}, {"GMG_XCD_REMAP_BIG", false}, {"GMG_X0_ZERO", true}, {"GMG_HOST_POLL", true}, {"GMG_HOST_CHUNK_BYTES", true}, {"GMG_PAT_FMA", false}, {"GMG_PAT_R2", false}, {"GMG_RED_FUSED", false}, {"GMG_GMRES_FUSED", true}, {"GMG_FGMRES_FUSED", true}, {"GMG_NULLSPACE_FUSED", true}, {"GMG_PAT_R2MV", false}, {"GMG_PAT_R2_OCC", false}, {"GMG_PAT_PAIR_P", false}, {"GMG_PAT_R2MV_DOT", false}, {"GMG_PERSIST_WPB", false}, {"GMG_HOST_TIMELINE", true}, {"GMG_PAT_R2MV_MIN", false}, {"GMG_PAT_BCAST", false}, {"GMG_PAT_R2_WGS", false}, {"GMG_PAT_ZWALK", false}, {"GMG_PAT_ZWALK_T", false}, {"GMG_PAT_ZWALK_ROWS", false}, {"GMG_PAT_ZWALK_MV", false}, {"GMG_PAT_ZWALK_WIDE", false}, {"GMG_PAT_ZWALK_WIDE_ROWS", false}, {"GMG_PAT_FUSE2", false}, {"GMG_PAT_FUSE2_W", false}, {"GMG_PAT_FUSE2_T", false}, {"GMG_PAT_FUSE2_ROWS", false}, {"GMG_PAT_FUSE2_BOX", false}, {"GMG_PAT_BOX", false}, {"GMG_PAT_WIDE_GRID", false}, {"GMG_PAT_BOX_T", false}, {"GMG_PAT_BOX_MIN_ROWS", false}, {"GMG_PAT_BOX_MAX_ROWS", false},
   {"GMG_PERSIST_FORCE_TIMEOUT", true}, {"GMG_PAT_XNEXT", false}, {"GMG_PAT_CLOSE", false}, {"GMG_CG_SPLIT", true},
 };
 // "pat_tile", "PAT_TILE" and "GMG_PAT_TILE" name the same option

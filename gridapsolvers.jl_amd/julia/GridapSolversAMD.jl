@@ -715,12 +715,39 @@ end
 #     solver = HipBlockFGMRESSolver(20, P; atol=1e-10, rtol=1e-12)
 #     ns = numerical_setup(symbolic_setup(solver,A),A); solve!(x,ns,b)       # A::BlockMatrix, x,b::BlockVector
 #
-# solvers[i]: HipGMGLinearSolver | CGSolver(JacobiLinearSolver()) | LUSolver() | JacobiLinearSolver().
+# solvers[i]: HipGMGLinearSolver | CGSolver(JacobiLinearSolver()) | LUSolver() | JacobiLinearSolver() | a Krylov solver around a
+# HipGMGLinearSolver `gmg` -- FGMRESSolver(m,gmg) | GMRESSolver(m;Pr=gmg) | GMRESSolver(m;Pl=gmg) | CGSolver(gmg;flexible) -- the
+# solver_u of test/Applications/NavierStokesGMG.jl:159-169 (gmg_block_set_diag_krylov_gmg; single GPU).
 # `mats[(i,j)]` replaces the system block in the preconditioner (MatrixBlock / an assembled BiformBlock).
 # ------------------------------------------------------------------------------------------------
 const GMG_BLOCK_DIAGONAL, GMG_BLOCK_LOWER, GMG_BLOCK_UPPER = Cint(0), Cint(1), Cint(2)
 const GMG_BLOCK_SCHUR = Cint(3)
 const GMG_BLOCK_GMG, GMG_BLOCK_CG_JACOBI, GMG_BLOCK_LU, GMG_BLOCK_JACOBI = Cint(1), Cint(2), Cint(3), Cint(4)
+const GMG_BLOCK_KRYLOV_GMG = Cint(5)
+const GMG_KRYLOV_CG, GMG_KRYLOV_FGMRES, GMG_KRYLOV_GMRES = Cint(1), Cint(2), Cint(3)
+
+# A Krylov solver around a GMG as the solver of a diagonal block -> (gmg, krylov, m, restart, m_add, flexible, side) for
+# gmg_block_set_diag_krylov_gmg; `nothing` for anything else.  An FGMRES with a Pl, both sides of GMRES, or a preconditioner that
+# is not a HipGMGLinearSolver has no device path.
+const _KRYLOV_GMG_FORMS = "a Krylov solver on a diagonal block wraps a HipGMGLinearSolver: FGMRESSolver(m,gmg) (Pl = nothing), " *
+                          "GMRESSolver(m;Pr=gmg) or GMRESSolver(m;Pl=gmg) (one side), CGSolver(gmg;flexible); or CGSolver(JacobiLinearSolver())"
+function _krylov_gmg_spec(s)
+  LS = GridapSolvers.LinearSolvers
+  if s isa LS.FGMRESSolver
+    (isnothing(s.Pl) && s.Pr isa HipGMGLinearSolver) || error(_KRYLOV_GMG_FORMS)
+    return (s.Pr, GMG_KRYLOV_FGMRES, s.m, s.restart, s.m_add, false, 0)
+  elseif s isa LS.GMRESSolver
+    (isnothing(s.Pr) != isnothing(s.Pl)) || error(_KRYLOV_GMG_FORMS)
+    P, side = isnothing(s.Pl) ? (s.Pr, 0) : (s.Pl, 1)
+    P isa HipGMGLinearSolver || error(_KRYLOV_GMG_FORMS)
+    return (P, GMG_KRYLOV_GMRES, s.m, s.restart, s.m_add, false, side)
+  elseif s isa LS.CGSolver && !(s.Pl isa JacobiLinearSolver)
+    s.Pl isa HipGMGLinearSolver || error(_KRYLOV_GMG_FORMS)
+    return (s.Pl, GMG_KRYLOV_CG, 1, false, 1, s.flexible, 1)
+  end
+  return nothing
+end
+_is_gmg_block(s) = s isa HipGMGLinearSolver || s isa HipGMGNumericalSetup || !isnothing(_krylov_gmg_spec(s))
 
 function check_block(h::Ptr{Cvoid}, status::Cint)
   if status != 0
@@ -859,6 +886,15 @@ function _block_numerical_setup(P::HipBlockTriangularSolver, mat, owner)
       check_block(h, ccall((:gmg_block_set_diag_gmg, libgmgamd), Cint, (Ptr{Cvoid},Cint,Ptr{Cvoid}), h, i-1, g.handle))
       continue
     end
+    spec = _krylov_gmg_spec(s)
+    if !isnothing(spec)                            # FGMRESSolver(m,gmg) & co.: the GMG is set up on the block's matrix as a bare one
+      gmg, krylov, m, restart, m_add, flexible, side = spec
+      g = numerical_setup(symbolic_setup(gmg,Mi),Mi); push!(ns.block_ns, g)
+      check_block(h, ccall((:gmg_block_set_diag_krylov_gmg, libgmgamd), Cint,
+        (Ptr{Cvoid},Cint,Ptr{Cvoid},Cint,Cint,Cint,Cint,Cint,Cint,Cint,Float64,Float64),
+        h, i-1, g.handle, krylov, m, restart ? 1 : 0, m_add, flexible ? 1 : 0, side, s.log.tols.maxiter, s.log.tols.atol, s.log.tols.rtol))
+      continue
+    end
     kind_i, maxiter, atol, rtol = if s isa GridapSolvers.LinearSolvers.CGSolver
       @assert s.Pl isa JacobiLinearSolver && !s.flexible
       GMG_BLOCK_CG_JACOBI, s.log.tols.maxiter, s.log.tols.atol, s.log.tols.rtol
@@ -898,7 +934,7 @@ function Gridap.Algebra.numerical_setup!(ns::HipBlockNumericalSetup, mat::Abstra
   end
   ig = 0                                                    # position in ns.block_ns: the GMG blocks in order
   for (i,s) in enumerate(P.solvers)
-    isgmg = s isa HipGMGLinearSolver || s isa HipGMGNumericalSetup
+    isgmg = _is_gmg_block(s)                                # (a Krylov wrapper brings a GMG setup of its own, refreshed like a bare one)
     isgmg && (ig += 1)
     i in P.nonlinear || continue
     isgmg && numerical_setup!(ns.block_ns[ig], B[i,i], isnothing(smatrices) ? nothing : smatrices[i])
@@ -919,7 +955,7 @@ _flat(v::AbstractVector) = v isa Vector{Float64} ? v : parent(v)
 
 function _fill_block_logs!(ns::HipBlockNumericalSetup, P::HipBlockTriangularSolver)
   for (i,s) in enumerate(P.solvers)
-    (s isa HipGMGLinearSolver || s isa HipGMGNumericalSetup || s isa GridapSolvers.LinearSolvers.CGSolver) || continue
+    (_is_gmg_block(s) || s isa GridapSolvers.LinearSolvers.CGSolver) || continue   # a Krylov wrapper: its own log, not the GMG's
     res = Ref(GmgResult(0,0,0.0,0.0))
     check_block(ns.handle, ccall((:gmg_block_diag_log, libgmgamd), Cint, (Ptr{Cvoid},Cint,Ref{GmgResult}), ns.handle, i-1, res))
     (s isa HipGMGNumericalSetup ? s.solver.log : s.log).num_iters = res[].niters

@@ -307,7 +307,8 @@ class MatrixBlock:
 
 class BlockDiagonalSolver:
     """BlockDiagonalSolver(blocks, solvers) / BlockDiagonalSolver(solvers) -- BlockDiagonalSolvers.jl:20-45.
-    solvers[i]: GMGLinearSolver | CGSolver(JacobiLinearSolver()) | LUSolver() | JacobiLinearSolver()."""
+    solvers[i]: GMGLinearSolver | CGSolver(JacobiLinearSolver()) | LUSolver() | JacobiLinearSolver() | a Krylov solver around a
+    GMGLinearSolver: FGMRESSolver(m, gmg) | GMRESSolver(m, Pr=gmg) | GMRESSolver(m, Pl=gmg) | CGSolver(gmg, flexible=...)."""
 
     half = "diagonal"
 
@@ -315,6 +316,8 @@ class BlockDiagonalSolver:
         if solvers is None:
             blocks, solvers = None, blocks
         self.solvers = list(solvers)
+        for sv in self.solvers:
+            _krylov_gmg_spec(sv)               # NotImplementedError: a Krylov solver around something that is not a GMG
         nb = len(self.solvers)
         diag = [LinearSystemBlock() for _ in range(nb)] if blocks is None else list(blocks)
         if len(diag) != nb:
@@ -331,6 +334,8 @@ class BlockTriangularSolver:
         if solvers is None:
             blocks, solvers = None, blocks
         self.solvers = list(solvers)
+        for sv in self.solvers:
+            _krylov_gmg_spec(sv)               # NotImplementedError: a Krylov solver around something that is not a GMG
         nb = len(self.solvers)
         if blocks is None:
             blocks = [[LinearSystemBlock() for _ in range(nb)] for _ in range(nb)]
@@ -345,18 +350,54 @@ class BlockTriangularSolver:
         self.half = half
 
 
+_KRYLOV_GMG_FORMS = ("a Krylov solver on a diagonal block wraps a GMGLinearSolver: FGMRESSolver(m, gmg) (Pl=None), "
+                     "GMRESSolver(m, Pr=gmg) or GMRESSolver(m, Pl=gmg) (one side), CGSolver(gmg, flexible=...); "
+                     "or CGSolver(JacobiLinearSolver())")
+
+
+def _krylov_gmg_spec(sv):
+    """FGMRESSolver(m, gmg) | GMRESSolver(m, Pr=gmg) | GMRESSolver(m, Pl=gmg) | CGSolver(gmg) as a diagonal-block solver
+    (test/Applications/NavierStokesGMG.jl:159-169) -> (gmg, krylov, m, restart, m_add, flexible, side) for
+    gmg_block_set_diag_krylov_gmg.  None: not one of these solvers, or one without any preconditioner (never a block solver);
+    NotImplementedError: a Krylov solver around something the device cannot nest."""
+    if isinstance(sv, FGMRESSolver):
+        if sv.Pr is None and sv.Pl is None:
+            return None
+        if sv.Pl is not None or not isinstance(sv.Pr, GMGLinearSolver):
+            raise NotImplementedError(_KRYLOV_GMG_FORMS)
+        return sv.Pr, abi.KRYLOV_FGMRES, sv.m, sv.restart, sv.m_add, False, 0
+    if isinstance(sv, GMRESSolver):
+        if sv.Pr is None and sv.Pl is None:
+            return None
+        if sv.Pr is not None and sv.Pl is not None:
+            raise NotImplementedError(_KRYLOV_GMG_FORMS)
+        P, side = (sv.Pr, 0) if sv.Pr is not None else (sv.Pl, 1)
+        if not isinstance(P, GMGLinearSolver):
+            raise NotImplementedError(_KRYLOV_GMG_FORMS)
+        return P, abi.KRYLOV_GMRES, sv.m, sv.restart, sv.m_add, False, side
+    if isinstance(sv, CGSolver):
+        if sv.Pl is None or isinstance(sv.Pl, JacobiLinearSolver):
+            return None
+        if not isinstance(sv.Pl, GMGLinearSolver):
+            raise NotImplementedError(_KRYLOV_GMG_FORMS)
+        return sv.Pl, abi.KRYLOV_CG, 1, False, 1, sv.flexible, 1
+    return None
+
+
 def _is_block_diag_solver(sv):
     """what BlockNumericalSetup can put on a diagonal block"""
     return isinstance(sv, (GMGLinearSolver, LUSolver, JacobiLinearSolver)) or \
-        (isinstance(sv, CGSolver) and isinstance(sv.Pl, JacobiLinearSolver) and not sv.flexible)
+        (isinstance(sv, CGSolver) and isinstance(sv.Pl, JacobiLinearSolver) and not sv.flexible) or \
+        _krylov_gmg_spec(sv) is not None
 
 
 class SchurComplementSolver:
     """SchurComplementSolver(A, B, C, S) -- SchurComplementSolvers.jl:11-26: the block factorisation of [A B; C D] with
     S ~ D - C A^-1 B (solve!: :55-74).  The reference receives A and S as numerical setups; here each is the pair
     (solver, matrix) that stands for numerical_setup(symbolic_setup(solver, matrix), matrix), with solver one of
-    GMGLinearSolver | CGSolver(JacobiLinearSolver()) | LUSolver() | JacobiLinearSolver(); matrix may be None for a
-    GMGLinearSolver (its own smatrices[0]).  B and C are CSR-like matrices of shape (n_A, n_S) and (n_S, n_A).
+    GMGLinearSolver | CGSolver(JacobiLinearSolver()) | LUSolver() | JacobiLinearSolver() | FGMRESSolver(m, gmg) |
+    GMRESSolver(m, Pr=gmg) | GMRESSolver(m, Pl=gmg) | CGSolver(gmg); matrix may be None for a GMGLinearSolver or a Krylov
+    solver around one (the GMG's own smatrices[0]).  B and C are CSR-like matrices of shape (n_A, n_S) and (n_S, n_A).
     The matrix given to numerical_setup (2 x 2 nested) serves mul! and the outer Krylov residual only, as in the reference."""
 
     half = "schur"
@@ -371,9 +412,10 @@ class SchurComplementSolver:
                 raise TypeError(f"SchurComplementSolver: the solver of {name} must be a GMGLinearSolver, CGSolver(JacobiLinearSolver()), "
                                 "LUSolver() or JacobiLinearSolver()")
             if M is None:
-                if not isinstance(sv, GMGLinearSolver):
+                spec = _krylov_gmg_spec(sv)
+                if not isinstance(sv, GMGLinearSolver) and spec is None:
                     raise ValueError(f"SchurComplementSolver: {name} needs a matrix (only a GMGLinearSolver brings its own)")
-                M = sv.smatrices[0]
+                M = (sv if spec is None else spec[0]).smatrices[0]
             if M.shape[0] != M.shape[1]:
                 raise ValueError(f"SchurComplementSolver: the matrix of {name} must be square")
             sizes.append((sv, M))
@@ -863,6 +905,14 @@ class BlockNumericalSetup:
                     self.block_ns[i] = g
                     abi.check_block(h, lib.gmg_block_set_diag_gmg(h, i, g.h))
                     continue
+                spec = _krylov_gmg_spec(sv)
+                if spec is not None:               # FGMRESSolver(m, gmg) & co.: the GMG is set up on the block's matrix as a bare one
+                    gmg, krylov, m, restart, m_add, flexible, side = spec
+                    g = GMGNumericalSetup(gmg, Mi, device_id)
+                    self.block_ns[i] = g
+                    abi.check_block(h, lib.gmg_block_set_diag_krylov_gmg(h, i, g.h, krylov, m, int(restart), m_add, int(flexible), side,
+                                                                         sv.log.maxiter, sv.log.atol, sv.log.rtol))
+                    continue
                 if isinstance(sv, CGSolver) and isinstance(sv.Pl, JacobiLinearSolver) and not sv.flexible:
                     kind, (mi, at, rt) = abi.BLOCK_CG_JACOBI, (sv.log.maxiter, sv.log.atol, sv.log.rtol)
                 elif isinstance(sv, LUSolver):
@@ -871,7 +921,7 @@ class BlockNumericalSetup:
                     kind, (mi, at, rt) = abi.BLOCK_JACOBI, (0, 0.0, 0.0)
                 else:
                     raise NotImplementedError("block solvers on the device: GMGLinearSolver, CGSolver(JacobiLinearSolver()), "
-                                              "LUSolver(), JacobiLinearSolver()")
+                                              "LUSolver(), JacobiLinearSolver(); " + _KRYLOV_GMG_FORMS)
                 abi.check_block(h, lib.gmg_block_set_diag_solver(h, i, kind, mi, at, rt))
                 if isinstance(blk, MatrixBlock):
                     shape, ptr, idx, val, layout, base = _csr_fields(blk.mat)
@@ -911,7 +961,7 @@ class BlockNumericalSetup:
         for i, sv in enumerate(self.solver.solvers):
             if not isinstance(self.solver.blocks[i][i], NonlinearSystemBlock):
                 continue
-            if isinstance(sv, GMGLinearSolver):
+            if isinstance(sv, GMGLinearSolver) or _krylov_gmg_spec(sv) is not None:
                 self.block_ns[i].update(mat[i][i], None if smatrices is None else smatrices[i])
             abi.check_block(h, lib.gmg_block_refresh_diag_solver(h, i))
         t2 = time.perf_counter()
@@ -929,10 +979,17 @@ class BlockNumericalSetup:
     def _fill_logs(self):
         """copy the block solvers' ConvergenceLogs back (their last application)"""
         for i, sv in enumerate(self.solver.solvers):
-            if isinstance(sv, (GMGLinearSolver, CGSolver)):
+            # (a Krylov solver around a GMG: the wrapper's own log; the GMG's stays as the GMG leaves it)
+            if isinstance(sv, (GMGLinearSolver, CGSolver)) or _krylov_gmg_spec(sv) is not None:
                 res = abi.Result()
                 abi.check_block(self.h, self._lib.gmg_block_diag_log(self.h, i, C.byref(res)))
                 sv.log.num_iters, sv.log.flag = int(res.niters), int(res.flag)
+
+    def diag_stats(self, i):
+        """gmg_block_diag_stats: (applications, iterations in all) of the iterative solver of block i since the last setup"""
+        a, t = C.c_int64(0), C.c_int64(0)
+        abi.check_block(self.h, self._lib.gmg_block_diag_stats(self.h, i, C.byref(a), C.byref(t)))
+        return int(a.value), int(t.value)
 
     def mul(self, y, x):
         """mul!(y, A, x) on the block system"""

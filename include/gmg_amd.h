@@ -271,6 +271,10 @@ GMG_API int gmg_set_options(gmg_handle_t h, int mode, int cycle, int maxiter, do
  *                    previous dot's partials, subtracts the projection and accumulates the next dot's partials in one pass -- and
  *                    gmres_normalize_kernel, the solution update as one gmres_combine_kernel; 0: a dot, a reduce and an axmy launch
  *                    per coefficient and an axpy per basis vector.  Same bits either way)
+ *                    fgmres_fused* (-1: an FGMRES nested in a block preconditioner (gmg_block_set_diag_krylov_gmg) runs its Arnoldi
+ *                    column with the kernels of gmres_fused on V and x += sum g_i Z_i as one gmres_combine_kernel over the table of
+ *                    Z, the entry points gmg_fgmres_solve[_pl] / gmg_block_fgmres_solve keep a dot, a reduce and an axmy launch per
+ *                    coefficient; 1: all of them fused; 0: none.  Where red_fused applies.  Same bits either way)
  *                    nullspace_fused* (1: where red_fused applies, the dots of a null-space projection are one pass over v for up to
  *                    8 basis vectors, nullspace_dots_kernel, the combination and the subtraction from x another,
  *                    nullspace_project_kernel, and make_orthogonal! / Gram-Schmidt chain nullspace_mgs_kernel; 0: a dot per
@@ -623,8 +627,10 @@ enum gmg_block_diag_kind {
   GMG_BLOCK_GMG = 1,        /* a GMGLinearSolver numerical setup (gmg handle) */
   GMG_BLOCK_CG_JACOBI = 2,  /* CGSolver(JacobiLinearSolver();maxiter,atol,rtol), CGSolvers.jl:73-120 */
   GMG_BLOCK_LU = 3,         /* LUSolver() on a small block: dense inverse on the device */
-  GMG_BLOCK_JACOBI = 4      /* JacobiLinearSolver(), JacobiLinearSolvers.jl:43-47 */
+  GMG_BLOCK_JACOBI = 4,     /* JacobiLinearSolver(), JacobiLinearSolvers.jl:43-47 */
+  GMG_BLOCK_KRYLOV_GMG = 5  /* FGMRESSolver(m,gmg) / GMRESSolver(m;Pr|Pl=gmg) / CGSolver(gmg): gmg_block_set_diag_krylov_gmg */
 };
+enum gmg_krylov_kind { GMG_KRYLOV_CG = 1, GMG_KRYLOV_FGMRES = 2, GMG_KRYLOV_GMRES = 3 };
 /* BlockDiagonalSolver(solvers) / BlockTriangularSolver(blocks,solvers,coeffs,half): BlockTriangularSolvers.jl:55-85.
  * kind = GMG_BLOCK_SCHUR (exactly 2 blocks, GMG_ERR_INVALID otherwise): the block factorisation of [A B; C D] with S ~ D - C A^-1 B,
  *   solve!(x_u,A,y_u); bp = y_p - C x_u; solve!(x_p,S,bp); bu = B x_p; solve!(du,A,bu); x_u .-= du     (SchurComplementSolvers.jl:65-71)
@@ -665,6 +671,23 @@ GMG_API int gmg_block_set_precond_block(gmg_block_handle_t h, int i, int j, int6
 GMG_API int gmg_block_set_coeff(gmg_block_handle_t h, int i, int j, double c);
 /* solvers[i] */
 GMG_API int gmg_block_set_diag_gmg(gmg_block_handle_t h, int i, gmg_handle_t g);
+/* solvers[i] = a Krylov solver around a GMG (test/Applications/NavierStokesGMG.jl:159-169: solver_u = FGMRESSolver(20,gmg;...)):
+ * solve A y_i = w_i with A the GMG handle's own finest matrix -- the operator of gmg_fgmres_solve -- by FGMRES (FGMRESSolvers.jl:130-199,
+ * the GMG as Pr), GMRES (GMRESSolvers.jl:132-210, side 0 = Pr, 1 = Pl) or CG (CGSolvers.jl:73-120, the GMG as Pl; flexible as there),
+ * preconditioned by that GMG.  m, restart, m_add: FGMRES / GMRES; flexible: CG.  The content of y_i on entry is the initial guess: for
+ * the diagonal and triangular kinds y_i is the handle's internal vector, which persists between applications (the reference's
+ * ns.work_caches; zero after the first setup); for GMG_BLOCK_SCHUR it is the caller's x, then du (SchurComplementSolvers.jl:65-70).
+ * The nested solve runs on the GMG handle's scalar slots, host mailbox, basis caches (allocated at the first application, kept across
+ * gmg_setup refreshes of the GMG handle and counted by its gmg_device_bytes) on the block handle's stream, so it never collides with
+ * the outer solve on the block handle.  numerical_setup!: as for a GMG block -- the caller refreshes the GMG handle,
+ * gmg_block_refresh_diag_solver only checks it; an in-place gmg_block_setup stays in place.  The wrapper keeps a ConvergenceLog of
+ * its own (gmg_block_diag_log: the last nested solve, not the GMG's).  Option fgmres_fused of the GMG handle chooses the kernels of
+ * a nested FGMRES column (default: fused), same bits.
+ * GMG_ERR_INVALID: bad krylov / side (FGMRES: 0, CG: 1), m < 1 or m_add < 1 (FGMRES / GMRES), a GMG handle that is not set up or whose
+ * finest size is not bsize(i).  GMG_ERR_UNSUPPORTED at gmg_block_setup, naming the block, when the block handle or the GMG handle has
+ * a communicator of more than one rank. */
+GMG_API int gmg_block_set_diag_krylov_gmg(gmg_block_handle_t h, int i, gmg_handle_t g, int krylov, int m, int restart, int m_add,
+                                          int flexible, int side, int maxiter, double atol, double rtol);
 GMG_API int gmg_block_set_diag_solver(gmg_block_handle_t h, int i, int kind, int maxiter, double atol, double rtol);
 /* matrix the solver of block i is set up on when it is not the system block (i,i) (e.g. the -1/alpha
  * pressure mass matrix, StokesGMG.jl:145) */
@@ -730,8 +753,11 @@ GMG_API int gmg_block_minres_solve(gmg_block_handle_t h, const double *b, double
 GMG_API int gmg_block_gmres_solve(gmg_block_handle_t h, const double *b, double *x, int memspace, int m, int restart, int m_add,
                                   int maxiter, double atol, double rtol, int use_precond_right, int use_precond_left,
                                   gmg_result *res, double *hist, int hist_cap);
-/* ConvergenceLog of the last solve of diagonal block i (GMG / CG blocks) */
+/* ConvergenceLog of the last solve of diagonal block i (GMG / CG blocks; GMG_BLOCK_KRYLOV_GMG: the wrapper's own log) */
 GMG_API int gmg_block_diag_log(gmg_block_handle_t h, int i, gmg_result *res);
+/* applications of the solver of diagonal block i and the iterations they took in all, since the last gmg_block_setup (GMG, CG-Jacobi
+ * and GMG_BLOCK_KRYLOV_GMG blocks; GMG_ERR_STATE for a direct one).  NULL pointers are skipped. */
+GMG_API int gmg_block_diag_stats(gmg_block_handle_t h, int i, int64_t *napplies, int64_t *total_iters);
 /* The null space of the block system (vectors of the total length, blocks concatenated): the twins of gmg_nullspace_* above, same
  * arguments and status codes; _project_guess covers gmg_block_cg_solve, _fgmres_solve, _minres_solve and _gmres_solve; _image_norms
  * applies the system blocks.  The handle must be set up; the null space stays across later gmg_block_setup calls. */
