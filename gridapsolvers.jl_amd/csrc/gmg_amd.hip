@@ -461,6 +461,8 @@ struct Level {
   double *ptmp = nullptr, *pcor = nullptr;
   bool post_shares_pre = true;
   std::shared_ptr<GsLevel> gs;    // level-set schedule + triangle tables of the level's Gauss-Seidel smoother(s), one copy for pre and post
+  int gs_order_kind = 0;          // gmg_set_gs_ordering: the visiting order the next gmg_setup builds (GMG_GS_ORDER_NATURAL)
+  std::vector<int32_t> gs_order;  // GMG_GS_ORDER_GIVEN: the caller's permutation
   int64_t n = 0;                  // owned rows
   int64_t nvec = 0;               // vector length = owned + ghost
   HaloPlan halo;                  // neighbour exchange plan (multi-GPU)
@@ -3160,7 +3162,7 @@ struct gmg_solver {
   void patch_precond(Level &L, Smoother &S, const double *r, double omega, bool relax, double *dx, double *x);
   // Gauss-Seidel smoother (gs.inc.hpp)
   void build_gs(int l, bool values_only = false);
-  void gs_solve(Level &L, int dir, const double *r, double *dx);
+  void gs_solve(Level &L, int dir, const double *r, double *dx, int xmode = 0, double *x = nullptr);
   void gs_pass(int l, Smoother &S, double *x, double *r, bool x_zero);
 
   // May the transfer T in front of the pass S of level l run as that pass's head?  One rank, a Jacobi pass that runs as one launch
@@ -7075,7 +7077,7 @@ const OptionKey kOptionKeys[] = {
   {"GMG_PERSIST_SHARED", false}, {"GMG_PROF_STRIDE", true}, {"GMG_REFRESH", true}, {"GMG_SELL", false}, {"GMG_SELL_BLOCK", false},
   {"GMG_SELL_DEFER", false}, {"GMG_SELL_MAXPAD", false}, {"GMG_SELL_UN", false}, {"GMG_SETUP_TIMING", true}, {"GMG_VDICT", false},
   {"GMG_XCD_REMAP", false}, {"GMG_XCD_REMAP_BIG", false}, {"GMG_X0_ZERO", true}, {"GMG_HOST_POLL", true}, {"GMG_HOST_CHUNK_BYTES", true}, {"GMG_PAT_FMA", false}, {"GMG_PAT_R2", false}, {"GMG_RED_FUSED", false}, {"GMG_GMRES_FUSED", true}, {"GMG_FGMRES_FUSED", true}, {"GMG_NULLSPACE_FUSED", true}, {"GMG_PAT_R2MV", false}, {"GMG_PAT_R2_OCC", false}, {"GMG_PAT_PAIR_P", false}, {"GMG_PAT_R2MV_DOT", false}, {"GMG_PERSIST_WPB", false}, {"GMG_HOST_TIMELINE", true}, {"GMG_PAT_R2MV_MIN", false}, {"GMG_PAT_BCAST", false}, {"GMG_PAT_R2_WGS", false}, {"GMG_PAT_ZWALK", false}, {"GMG_PAT_ZWALK_T", false}, {"GMG_PAT_ZWALK_ROWS", false}, {"GMG_PAT_ZWALK_MV", false}, {"GMG_PAT_ZWALK_WIDE", false}, {"GMG_PAT_ZWALK_WIDE_ROWS", false}, {"GMG_PAT_FUSE2", false}, {"GMG_PAT_FUSE2_W", false}, {"GMG_PAT_FUSE2_T", false}, {"GMG_PAT_FUSE2_ROWS", false}, {"GMG_PAT_FUSE2_BOX", false}, {"GMG_PAT_BOX", false}, {"GMG_PAT_WIDE_GRID", false}, {"GMG_PAT_BOX_T", false}, {"GMG_PAT_BOX_MIN_ROWS", false}, {"GMG_PAT_BOX_MAX_ROWS", false},
-  {"GMG_PERSIST_FORCE_TIMEOUT", true}, {"GMG_PAT_XNEXT", false}, {"GMG_PAT_CLOSE", false}, {"GMG_CG_SPLIT", true},
+  {"GMG_PERSIST_FORCE_TIMEOUT", true}, {"GMG_PAT_XNEXT", false}, {"GMG_PAT_CLOSE", false}, {"GMG_CG_SPLIT", true}, {"GMG_GS_WIDE", true},
 };
 // "pat_tile", "PAT_TILE" and "GMG_PAT_TILE" name the same option
 const OptionKey *find_option(const char *key)
@@ -7968,7 +7970,7 @@ int gmg_get_kernel_stats(gmg_handle_t h, gmg_kernel_stats *out)
       HIP_CHECK(hipEventElapsedTime(&ms, h->prof_ev[i], h->prof_ev[i + 1]));
       h->prof_ms += ms;
       h->prof_launches += h->prof_w[i / 2];
-      if (h->prof_w[i / 2] > 2) h->prof_fused += 1;          // (a weight of 2 is a fused PAIR of sweeps, sells_z2sweep_kernel: not a one-launch pass)
+      if (h->prof_w[i / 2] > 2 && h->prof_xm[i / 2] >= 0) h->prof_fused += 1;   // (a weight of 2 is a fused PAIR of sweeps, sells_z2sweep_kernel: not a one-launch pass; -1: the launches of a Gauss-Seidel direction)
       const int v = std::min(2, std::max(0, (int)h->prof_xm[i / 2]));
       h->prof_ms_v[v] += ms; h->prof_n_v[v] += h->prof_w[i / 2];
     }

@@ -49,6 +49,7 @@ const GMG_MEM_HOST, GMG_MEM_DEVICE = Cint(0), Cint(1)
 const GMG_PRE, GMG_POST, GMG_PRE_AND_POST = Cint(0), Cint(1), Cint(2)
 const GMG_PATCH_LU, GMG_PATCH_NOPIVOT = Cint(0), Cint(1)
 const GMG_GS_SYMMETRIC, GMG_GS_FORWARD, GMG_GS_BACKWARD = Cint(0), Cint(1), Cint(2)
+const GMG_GS_ORDER_NATURAL, GMG_GS_ORDER_MULTICOLOR, GMG_GS_ORDER_GIVEN = Cint(0), Cint(1), Cint(2)
 
 struct GmgResult
   niters::Int32
@@ -98,6 +99,7 @@ struct HipGMGLinearSolver{A,B,C,D,E,F} <: Gridap.Algebra.LinearSolver
   device         :: Int
   options        :: Dict{String,Float64}   # device-side policy handed to gmg_set_option before the operators are set (keys: include/gmg_amd.h)
   pin_vectors    :: Bool                   # page-lock the Vector{Float64}s solve! is called with, once (PETScCaches.jl:23-36 pins its x / b the same way)
+  gs_ordering    :: Vector{Any}            # per smoothed level: :natural, :multicolor or a 1-based permutation (gmg_set_gs_ordering)
 end
 
 # Same keyword surface as GMGLinearSolver(smatrices,interp,restrict;...) GMGLinearSolvers.jl:48-69, plus three keywords the
@@ -112,7 +114,7 @@ function HipGMGLinearSolver(
   coarsest_solver = Gridap.Algebra.LUSolver(),
   mode = :preconditioner, cycle_type = :v_cycle,
   maxiter = 100, atol = 1.0e-14, rtol = 1.0e-08, verbose = false, device = 0,
-  options = Dict{String,Float64}(), pin_vectors = false,
+  options = Dict{String,Float64}(), pin_vectors = false, gs_ordering = :natural,
 )
   nlev = length(smatrices)
   @assert nlev-1 == length(interp) == length(pre_smoothers) == length(post_smoothers)
@@ -122,7 +124,12 @@ function HipGMGLinearSolver(
   tols = SolverTolerances{Float64}(;maxiter=maxiter,atol=atol,rtol=rtol)
   log  = ConvergenceLog("GMG-MI355X",tols;verbose=verbose)
   opts = Dict{String,Float64}(string(k) => Float64(v) for (k,v) in pairs(options))
-  return HipGMGLinearSolver(smatrices,interp,restrict,pre_smoothers,post_smoothers,coarsest_solver,mode,cycle_type,log,device,opts,pin_vectors)
+  # the visiting order of the levels' Gauss-Seidel sweeps (the reference's GaussSeidelSmoother has no field for it): one entry for
+  # every smoothed level, or one entry per level -- :natural, :multicolor or a 1-based permutation of the level's rows
+  gso = (gs_ordering isa Symbol || gs_ordering isa AbstractVector{<:Integer}) ? Any[gs_ordering for _ in 1:nlev-1] : Any[gs_ordering...]
+  @assert length(gso) == nlev-1
+  @assert all(o -> o ∈ (:natural,:multicolor) || o isa AbstractVector{<:Integer}, gso)
+  return HipGMGLinearSolver(smatrices,interp,restrict,pre_smoothers,post_smoothers,coarsest_solver,mode,cycle_type,log,device,opts,pin_vectors,gso)
 end
 
 struct HipGMGSymbolicSetup{A} <: Gridap.Algebra.SymbolicSetup
@@ -288,6 +295,20 @@ function _set_smoother(h, lev, which, sm::GaussSeidelSmoother)
                  h, lev, which, sm.niter, sm.ω, t))
 end
 
+# the visiting order of a level's Gauss-Seidel sweeps (inert on a level without such a smoother); takes effect at gmg_setup
+function _set_gs_ordering(h, lev, o)
+  if o isa Symbol
+    check(h, ccall((:gmg_set_gs_ordering, libgmgamd), Cint, (Ptr{Cvoid},Cint,Cint,Ptr{Int32},Int64),
+                   h, lev, o === :multicolor ? GMG_GS_ORDER_MULTICOLOR : GMG_GS_ORDER_NATURAL, C_NULL, 0))
+  else
+    order = Int32.(o .- 1)
+    GC.@preserve order begin
+      check(h, ccall((:gmg_set_gs_ordering, libgmgamd), Cint, (Ptr{Cvoid},Cint,Cint,Ptr{Int32},Int64),
+                     h, lev, GMG_GS_ORDER_GIVEN, order, length(order)))
+    end
+  end
+end
+
 # numerical_setup(ss,A): GMGLinearSolvers.jl:183-210
 function Gridap.Algebra.numerical_setup(ss::HipGMGSymbolicSetup, mat::AbstractMatrix)
   s = ss.solver
@@ -323,6 +344,7 @@ function Gridap.Algebra.numerical_setup(ss::HipGMGSymbolicSetup, mat::AbstractMa
       _set_smoother(h, l-1, GMG_PRE,  s.pre_smoothers[l])
       _set_smoother(h, l-1, GMG_POST, s.post_smoothers[l])
     end
+    s.gs_ordering[l] === :natural || _set_gs_ordering(h, l-1, s.gs_ordering[l])
   end
   tols = s.log.tols
   mode  = s.mode == :preconditioner ? 0 : 1

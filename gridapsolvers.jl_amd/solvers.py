@@ -38,7 +38,7 @@ import numpy as np
 from . import abi
 
 __all__ = [
-    "JacobiLinearSolver", "RichardsonSmoother", "GaussSeidelSmoother", "SymGaussSeidelSmoother", "PatchSolver", "BlockJacobiSolver", "LUSolver",
+    "JacobiLinearSolver", "RichardsonSmoother", "GaussSeidelSmoother", "SymGaussSeidelSmoother", "multicolor_order", "PatchSolver", "BlockJacobiSolver", "LUSolver",
     "GMGLinearSolver", "CGSolver", "FGMRESSolver", "MINRESSolver", "GMRESSolver", "ConvergenceLog", "PatchProlongationOperator",
     "RichardsonLinearSolver", "BlockDiagonalSolver", "BlockTriangularSolver", "SchurComplementSolver", "LinearSystemBlock", "NonlinearSystemBlock", "MatrixBlock", "LinearSolverFromSmoother",
     "NullSpace", "NullspaceSolver", "is_orthonormal", "is_orthogonal", "make_orthonormal_", "gram_schmidt_", "modified_gram_schmidt_",
@@ -118,10 +118,15 @@ class RichardsonSmoother:
 
 
 class GaussSeidelSmoother:
-    """GaussSeidelSmoother(niter=1, omega=1.0, type=:symmetric) -- SymGaussSeidelSmoothers.jl:105-118."""
-    _TYPES = {"symmetric": abi.GS_SYMMETRIC, "forward": abi.GS_FORWARD, "backward": abi.GS_BACKWARD}
+    """GaussSeidelSmoother(niter=1, omega=1.0, type=:symmetric) -- SymGaussSeidelSmoothers.jl:105-118.
 
-    def __init__(self, niter=1, omega=1.0, type="symmetric"):
+    ordering: the visiting order of the sweeps on the smoother's level (gmg_set_gs_ordering) -- "natural" (the reference's), "multicolor"
+    (greedy first-fit colouring of the symmetrised stored pattern, rows sorted stably by colour) or a 1-D integer array: order[k] is the
+    row the forward sweep visits k-th.  One order per level: pre- and post-smoother of a level must name the same."""
+    _TYPES = {"symmetric": abi.GS_SYMMETRIC, "forward": abi.GS_FORWARD, "backward": abi.GS_BACKWARD}
+    _ORDERINGS = {"natural": abi.GS_ORDER_NATURAL, "multicolor": abi.GS_ORDER_MULTICOLOR}
+
+    def __init__(self, niter=1, omega=1.0, type="symmetric", ordering="natural"):
         if type not in self._TYPES:
             raise ValueError("The type must be :symmetric, :forward or :backward.")
         if not int(niter) > 0:
@@ -129,11 +134,47 @@ class GaussSeidelSmoother:
         if not float(omega) > 0.0:
             raise ValueError("The relaxation parameter must be a positive real number.")
         self.niter, self.omega, self.type = int(niter), float(omega), type
+        self.ordering = self._check_ordering(ordering)
+
+    @classmethod
+    def _check_ordering(cls, ordering):
+        if isinstance(ordering, str):
+            if ordering not in cls._ORDERINGS:
+                raise ValueError('The ordering must be "natural", "multicolor" or a 1-D integer array.')
+            return ordering
+        if isinstance(ordering, (bytes, dict, set)) or ordering is None:
+            raise ValueError('The ordering must be "natural", "multicolor" or a 1-D integer array.')
+        a = np.asarray(ordering)
+        if a.ndim != 1 or a.dtype.kind not in "iu" or (a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31)):
+            raise ValueError('The ordering must be "natural", "multicolor" or a 1-D integer array.')
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def _same_ordering(self, other):
+        a, b = self.ordering, other.ordering
+        if isinstance(a, str) or isinstance(b, str):
+            return isinstance(a, str) and isinstance(b, str) and a == b
+        return np.array_equal(a, b)
 
 
-def SymGaussSeidelSmoother(niter=1, omega=1.0):
+def SymGaussSeidelSmoother(niter=1, omega=1.0, ordering="natural"):
     """SymGaussSeidelSmoother(niter, omega) = GaussSeidelSmoother(niter, omega, :symmetric) -- SymGaussSeidelSmoothers.jl:121."""
-    return GaussSeidelSmoother(niter, omega, "symmetric")
+    return GaussSeidelSmoother(niter, omega, "symmetric", ordering)
+
+
+def multicolor_order(A):
+    """gmg_gs_multicolor_order on the stored pattern of a square matrix (poisson.CSR, scipy CSR, ...; explicit zeros count) ->
+    (order, color): the visiting order ordering="multicolor" uses and the colour of every row.  Host only: no handle, no GPU."""
+    shape, ptr, idx, _val, layout, base = _csr_fields(A)
+    if shape[0] != shape[1]:
+        raise ValueError("multicolor_order: the matrix must be square")
+    # (the colouring symmetrises the pattern, so a CSC pattern gives the same answer as its CSR form)
+    ptr = np.ascontiguousarray(ptr, dtype=np.int64) - base
+    idx = np.ascontiguousarray(idx, dtype=np.int32) - np.int32(base)
+    n = int(shape[0])
+    order, color, nc = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32), C.c_int64(0)
+    abi.check(None, abi.load().gmg_gs_multicolor_order(n, C.c_void_p(ptr.ctypes.data), C.c_void_p(idx.ctypes.data),
+                                                       C.c_void_p(order.ctypes.data), C.c_void_p(color.ctypes.data), C.byref(nc)))
+    return order, color
 
 
 class LinearSolverFromSmoother:
@@ -638,6 +679,7 @@ class GMGNumericalSetup:
             if s.restrict[l] is not None:
                 _set_op(lib.gmg_set_restriction, h, l, s.restrict[l])
             pre, post = s.pre_smoothers[l], s.post_smoothers[l]
+            self._set_gs_ordering(l, pre, post)
             if post is pre:
                 self._set_smoother(l, abi.PRE_AND_POST, pre)
             else:
@@ -664,6 +706,19 @@ class GMGNumericalSetup:
         abi.check(h, lib.gmg_setup(h))
         self.n = int(mats[0].shape[0])
         self.sizes = [int(A.shape[0]) for A in mats]
+
+    def _set_gs_ordering(self, l, pre, post):
+        """one visiting order per level (gmg_set_gs_ordering): the one its Gauss-Seidel smoother(s) name"""
+        gs = [sm for sm in (pre, post) if isinstance(sm, GaussSeidelSmoother)]
+        if not gs:
+            return
+        if len(gs) == 2 and not gs[0]._same_ordering(gs[1]):
+            raise ValueError(f"level {l}: the pre- and the post-smoother name different orderings (one order per level)")
+        o = gs[0].ordering
+        if isinstance(o, str):
+            abi.check(self.h, self._lib.gmg_set_gs_ordering(self.h, l, GaussSeidelSmoother._ORDERINGS[o], None, 0))
+        else:
+            abi.check(self.h, self._lib.gmg_set_gs_ordering(self.h, l, abi.GS_ORDER_GIVEN, C.c_void_p(o.ctypes.data), o.size))
 
     def _set_smoother(self, l, which, sm):
         lib, h = self._lib, self.h
@@ -838,6 +893,15 @@ class GMGNumericalSetup:
         v = [C.c_int64(0) for _ in range(4)]
         abi.check(self.h, self._lib.gmg_get_gs_schedule(self.h, lev, 0 if forward else 1, *[C.byref(q) for q in v]))
         return dict(zip(("nsets", "max_set_rows", "nlaunches", "nwide"), (q.value for q in v)))
+
+
+    def gs_ordering(self, lev=0):
+        """gmg_get_gs_ordering: the visiting order the setup of the level's Gauss-Seidel smoother used ->
+        dict(kind ("natural" / "multicolor" / "given"), ncolors (0 unless multicolor), order)"""
+        kind, nc = C.c_int(0), C.c_int64(0)
+        order = np.empty(self.sizes[lev], dtype=np.int32)
+        abi.check(self.h, self._lib.gmg_get_gs_ordering(self.h, lev, C.byref(kind), C.byref(nc), C.c_void_p(order.ctypes.data), order.size))
+        return dict(kind=("natural", "multicolor", "given")[kind.value], ncolors=nc.value, order=order)
 
 
 def _set_block(fn, h, i, j, M):

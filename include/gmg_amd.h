@@ -190,6 +190,39 @@ GMG_API int gmg_set_smoother_gauss_seidel(gmg_handle_t h, int lev, int which, in
 GMG_API int gmg_get_gs_schedule(gmg_handle_t h, int lev, int dir, int64_t *nsets, int64_t *max_set_rows,
                                 int64_t *nlaunches, int64_t *nwide);
 
+/* The visiting order of a level's Gauss-Seidel sweeps.  order[k] is the row the forward sweep visits k-th, pos its inverse.
+ * Forward: for k = 0 .. n-1, i = order[k]: dx_i = (r_i - sum a_ij dx_j) / a_ii over the stored j with pos(j) < k in ascending pos(j),
+ * one rounded product and one rounded subtraction per term, the division last; backward: k = n-1 .. 0 over pos(j) > k in descending
+ * pos(j).  That is forward_sub! / backward_sub! on B = A[order, order] applied to r[order] and scattered back; the rest of a pass
+ * (dx = omega dx, x += dx, r -= A dx in the level's own numbering) is unchanged.
+ *   GMG_GS_ORDER_NATURAL     (default) order[k] = k.
+ *   GMG_GS_ORDER_MULTICOLOR  greedy first-fit colouring of the symmetrised STORED pattern (explicit zeros count, the diagonal does
+ *                            not): rows in natural order, each takes the smallest colour no already-coloured neighbour holds; the
+ *                            order is the rows sorted stably by colour.  Rows of one colour share no stored entry, so the solve has
+ *                            at most as many level sets as colours (exactly as many on a structurally symmetric pattern).
+ *                            Deterministic, built on the host at gmg_setup from the pattern only: a value refresh keeps it.
+ *                            Greedy, not optimal.
+ *   GMG_GS_ORDER_GIVEN       the caller's permutation (copied): n entries, every row exactly once.
+ * gmg_set_gs_ordering takes effect at the next gmg_setup, which then rebuilds everything; one order per level, shared by its pre- and
+ * post-smoother.  Legal on any smoothed level and inert where no smoother of the level is Gauss-Seidel.  An unknown kind, `order`
+ * given with another kind than GIVEN, n different from the level's rows or a bad permutation: GMG_ERR_INVALID, the message names the
+ * level and the first offending position.  gmg_get_gs_schedule reports the sets and launches of the order in use.  On a level with an
+ * order of its own the one-set launches run gs_wide_kernel (one wave per slice of 64 permuted rows); where omega == 1 and every
+ * launch of the direction's plan is a one-set launch, that kernel also updates x and the update launch is not made (same rounding).
+ * With profiling enabled on the level (gmg_profile_enable), gmg_kernel_stats.launches counts the launches of the triangular solves
+ * and of the x updates of its Gauss-Seidel passes (r -= A dx is not counted).
+ * gmg_get_gs_ordering returns what the last gmg_setup used: kind, the number of colours (0 unless MULTICOLOR) and, if `order` is not
+ * NULL, the n entries of the order (the identity for NATURAL); cap < n: GMG_ERR_INVALID.  GMG_ERR_STATE if no smoother of the level
+ * is Gauss-Seidel.  Any of the outputs may be NULL. */
+enum gmg_gs_order { GMG_GS_ORDER_NATURAL = 0, GMG_GS_ORDER_MULTICOLOR = 1, GMG_GS_ORDER_GIVEN = 2 };
+GMG_API int gmg_set_gs_ordering(gmg_handle_t h, int lev, int kind, const int32_t *order, int64_t n);
+GMG_API int gmg_get_gs_ordering(gmg_handle_t h, int lev, int *kind, int64_t *ncolors, int32_t *order, int64_t cap);
+/* The colouring itself, without a handle and without a GPU: 0-based CSR pattern of a square matrix (ptr[nrows + 1], col[ptr[nrows]];
+ * columns in any order, duplicates allowed) -> order[nrows], color[nrows] (either may be NULL), *ncolors.  gmg_setup calls this
+ * function.  A column outside [0, nrows) or a non-monotone ptr: GMG_ERR_INVALID. */
+GMG_API int gmg_gs_multicolor_order(int64_t nrows, const int64_t *ptr, const int32_t *col, int32_t *order, int32_t *color,
+                                    int64_t *ncolors);
+
 /* Patch-corrected prolongation  y = P x - sum_p R_p^T A_pp^-1 R_p (A P x)  over the given patches
  * (PatchProlongationOperator, PatchBasedSmoothers/PatchTransferOperators.jl:153-172 with rhs = lhs = the
  * level operator; used by the reference for grad-div problems, test/Applications/StokesGMG.jl:125-133).
@@ -289,6 +322,9 @@ GMG_API int gmg_set_options(gmg_handle_t h, int mode, int cycle, int maxiter, do
  *                    r -= A dx in front of a post-smoothing pass, 4 bit 1 also where the finer level is no one-launch level; one
  *                    rank, transfer tables in the LDS form that fit next to the pass's own; 0 = separate launches.  Same bits
  *                    either way; gmg_sweep_signature ends in folds=R+P / R / P / none for a level with a one-launch pass)
+ *   Gauss-Seidel     gs_wide* (1: on a level with a visiting order of its own (gmg_set_gs_ordering) the one-set launches run
+ *                    gs_wide_kernel and fold the x update where they may; 0: they run gs_sets_kernel with the update launch, as the
+ *                    natural order does.  Same bits either way: the A/B switch of tools/gs_timing.py)
  *   coarsest level   coarse_host_max (1500) coarse_host_fallback_max (6000) coarse_auto_cg_min (20000: a dense-inverse request on a
  *                    coarsest level of at least this many dofs is served by the device CG-Jacobi solver instead) gj_mfma (1) gj_wide_min (4096)
  *   patch smoother   patch_dedup (1) patch_source_dedup (1) patch_operator (1)

@@ -11,9 +11,15 @@ levels (default 4), everything in one process, b and x resident in HBM.
   vcycle / cg  median ms of one V-cycle (the GMG as a preconditioner, maxiter = 1) and of one CG solve (rtol 1e-6, maxiter 20, rhs
                of u = x1 + x2), with iteration counts, for both smoother choices
 
+  --ordering   the visiting order of every Gauss-Seidel smoother above: natural (default) or multicolor (gmg_set_gs_ordering)
+  --ab         (with --ordering multicolor) the kernel A/B on level 0: one forward triangular solve + x update through gs_wide_kernel
+               (option gs_wide = 1) and through gs_sets_kernel (gs_wide = 0) on the same tables, alternating, timed by the library's
+               HIP events around exactly those launches (gmg_profile_enable / gmg_get_kernel_stats) and by the host clock around
+               the whole pass; at omega = 0.9 both forms make the update launch (the kernels alone), at omega = 1 the new one folds it
+
 Every figure: one warm-up call, then --reps calls each between two device synchronisations; median, minimum and maximum are kept.
 
-    python tools/gs_timing.py [--cells 128] [--levels 4] [--reps 10] [--out profiles/gs_timing.json]
+    python tools/gs_timing.py [--cells 128] [--levels 4] [--reps 10] [--ordering natural] [--ab] [--out profiles/gs_timing.json]
 Prints one JSON object."""
 import argparse
 import json
@@ -36,6 +42,8 @@ def main():
     ap.add_argument("--cells", type=int, default=128)
     ap.add_argument("--levels", type=int, default=4)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--ordering", choices=("natural", "multicolor"), default="natural")
+    ap.add_argument("--ab", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -66,8 +74,8 @@ def main():
                                  post_smoothers=[sm] * (nlev - 1), maxiter=1, mode="preconditioner", **kw)
 
     smoothers = dict(jacobi_10_10=lambda: S.RichardsonSmoother(S.JacobiLinearSolver(), 10, 2.0 / 3.0),
-                     sym_gauss_seidel_1=lambda: S.SymGaussSeidelSmoother(1))
-    out = dict(cells=a.cells, levels=nlev, dofs=[int(M.shape[0]) for M in H["mats"]], reps=a.reps, setup_s={}, vcycle_ms={}, cg={})
+                     sym_gauss_seidel_1=lambda: S.SymGaussSeidelSmoother(1, 1.0, a.ordering))
+    out = dict(ordering=a.ordering, cells=a.cells, levels=nlev, dofs=[int(M.shape[0]) for M in H["mats"]], reps=a.reps, setup_s={}, vcycle_ms={}, cg={})
     for name, make in smoothers.items():
         g = gmg(make())
         t0 = time.perf_counter()
@@ -76,7 +84,8 @@ def main():
         out["setup_s"][name] = time.perf_counter() - t0
         out.setdefault("device_bytes", {})[name] = ns.device_bytes()
         if name == "sym_gauss_seidel_1":
-            out["schedule"] = [dict(level=l, forward=ns.gs_schedule(l, True), backward=ns.gs_schedule(l, False)) for l in range(nlev - 1)]
+            out["schedule"] = [dict(level=l, forward=ns.gs_schedule(l, True), backward=ns.gs_schedule(l, False),
+                                    ncolors=ns.gs_ordering(l)["ncolors"]) for l in range(nlev - 1)]
 
         def vcycle():
             S.solve_(xd, ns, bd)
@@ -93,7 +102,7 @@ def main():
         out["cg"][name] = dict(ms=runs(cg), iters=int(solver.log.num_iters), flag=int(solver.log.flag))
         ks.P_ns.close()
     # one forward pass per level, next to one mat-vec of the level
-    ns = S.numerical_setup(S.symbolic_setup(gmg(S.GaussSeidelSmoother(1, 1.0, "forward")), A), A)
+    ns = S.numerical_setup(S.symbolic_setup(gmg(S.GaussSeidelSmoother(1, 1.0, "forward", a.ordering)), A), A)
     out["forward"] = []
     for l in range(nlev - 1):
         n = ns.sizes[l]
@@ -104,6 +113,28 @@ def main():
         out["forward"].append(dict(level=l, rows=n, pass_ms=p, matvec_ms=m, triangular_solve_ms_estimate=p["median"] - m["median"],
                                    launches=ns.gs_schedule(l, True)["nlaunches"]))
     ns.close()
+    if a.ab:
+        out["ab_level0"] = {}
+        for omega in (0.9, 1.0):
+            ns = S.numerical_setup(S.symbolic_setup(gmg(S.GaussSeidelSmoother(1, omega, "forward", a.ordering)), A), A)
+            n = ns.sizes[0]
+            r = torch.from_numpy(np.random.default_rng(0).uniform(-1.0, 1.0, n)).cuda()
+            dx = torch.zeros_like(r)
+            ev, wall, launches = {1: [], 0: []}, {1: [], 0: []}, {}
+            for rep in range(a.reps + 1):                     # (the first round is the warm-up)
+                for wide in (1, 0):
+                    ns.set_option("gs_wide", wide)
+                    ns.profile(0)
+                    w = timed(lambda: ns.precond(0, r, dx))
+                    st = ns.kernel_stats()
+                    ns.profile(0, False)
+                    launches[wide] = st["launches"]
+                    if rep:
+                        ev[wide].append(st["total_ms"]); wall[wide].append(w)
+            out["ab_level0"]["omega_%g" % omega] = {name: dict(solve_and_update_event_ms=_stats(ev[wide]), pass_wall_ms=_stats(wall[wide]),
+                                                               launches=launches[wide])
+                                                    for name, wide in (("gs_wide_kernel", 1), ("gs_sets_kernel", 0))}
+            ns.close()
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
