@@ -20,6 +20,7 @@ GS_ORDER_NATURAL, GS_ORDER_MULTICOLOR, GS_ORDER_GIVEN = 0, 1, 2
 OP_A, OP_P, OP_R = 0, 1, 2
 LEVEL_KRYLOV = -1          # GMG_LEVEL_KRYLOV: the separate Krylov operator of a finest level in the overlapping layout
 COARSE_DENSE_INVERSE, COARSE_CG_JACOBI, COARSE_HOST_CALLBACK = 0, 1, 2
+COARSE_BUILT_NONE, COARSE_BUILT_HOST_LU, COARSE_BUILT_DEVICE_GJ, COARSE_BUILT_HOST_CONSTRAINED = 0, 1, 2, 3   # gmg_get_coarse_info
 BLOCK_DIAGONAL, BLOCK_LOWER, BLOCK_UPPER, BLOCK_SCHUR = 0, 1, 2, 3
 BLOCK_GMG, BLOCK_CG_JACOBI, BLOCK_LU, BLOCK_JACOBI, BLOCK_KRYLOV_GMG = 1, 2, 3, 4, 5
 KRYLOV_CG, KRYLOV_FGMRES, KRYLOV_GMRES = 1, 2, 3
@@ -85,6 +86,7 @@ SYMBOLS = {
                                                   C.c_int, C.c_int, C.c_int],
     "gmg_set_coarse_solver": [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p],
     "gmg_get_coarse_log": [C.c_void_p, C.POINTER(Result)],
+    "gmg_get_coarse_info": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "gmg_set_options": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double],
     "gmg_set_option": [C.c_void_p, C.c_char_p, C.c_double],
     "gmg_get_option": [C.c_void_p, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)],

@@ -641,6 +641,9 @@ struct gmg_solver {
   // setup and gigabytes (29 791 dofs, BASELINE config 3: 1.9 s, 7.1 GB) for a solve the outer Krylov method only needs to ~1e-7
   int coarse_eff = GMG_COARSE_DENSE_INVERSE;
   bool coarse_auto = false;
+  // gmg_get_coarse_info: how the last dense inverse of this engine was built (a record of what build_dense_inverse /
+  // build_coarse_device / build_constrained_inverse decided; nothing reads it back)
+  struct CoarseInfo { int built_by = 0, panel = 0, mfma = 0, device_rejected = 0; } coarse_info;
   void resolve_coarse_kind()
   {
     coarse_eff = coarse_kind; coarse_auto = false;
@@ -5715,6 +5718,7 @@ void gmg_solver::build_coarse()
           "the dense-inverse coarse solver needs the coarsest matrix whole (gmg_set_matrix), not streamed");
   REQUIRE(coarse_k == 0 || coarse_eff == GMG_COARSE_DENSE_INVERSE, GMG_ERR_UNSUPPORTED,
           "gmg_set_coarse_nullspace: the constrained coarsest solve exists for the dense-inverse coarse solver (LUSolver()) only");
+  coarse_info = CoarseInfo();
   if (coarse_eff == GMG_COARSE_DENSE_INVERSE && coarse_k > 0) d_Ainv = build_constrained_inverse(lev[nlev - 1].hA, "coarsest-level matrix");
   else if (coarse_eff == GMG_COARSE_DENSE_INVERSE) d_Ainv = build_dense_inverse(lev[nlev - 1].hA, "coarsest-level matrix");
   else if (coarse_eff == GMG_COARSE_CG_JACOBI) { cc_w = dvec(n); cc_p = dvec(n); cc_z = dvec(n); cc_r = dvec(n); }
@@ -5730,6 +5734,7 @@ void gmg_solver::build_coarse()
 double *gmg_solver::build_dense_inverse(const HostCSR &A, const std::string &what)
 {
   const int n = (int)A.nrows;
+  coarse_info = CoarseInfo();
   // Small matrices: exact banded LU with partial pivoting on the host (O(n^2 * bandwidth)).
   // Large ones: blocked Gauss-Jordan on the device (no pivoting; result verified below).
   if (n > opt_int("GMG_COARSE_HOST_MAX", 1500)) {
@@ -5748,6 +5753,8 @@ double *gmg_solver::build_dense_inverse(const HostCSR &A, const std::string &wha
       while (allocs.size() > mark) { (void)hipFree(allocs.back()); allocs.pop_back(); }
       dev_bytes = bytes0;
       if (e.code != GMG_ERR_SINGULAR) throw;
+      coarse_info = CoarseInfo();
+      coarse_info.device_rejected = 1;
     }
   }
   BandLU lu;
@@ -5766,6 +5773,7 @@ double *gmg_solver::build_dense_inverse(const HostCSR &A, const std::string &wha
   run_threads(nthreads, work);
   double *d = upload(inv);
   HIP_CHECK(hipStreamSynchronize(stream));
+  coarse_info.built_by = GMG_COARSE_BUILT_HOST_LU;
   return d;
 }
 
@@ -5807,6 +5815,8 @@ double *gmg_solver::build_constrained_inverse(const HostCSR &A, const std::strin
   run_threads(nthreads, work);
   double *d = upload(inv);
   HIP_CHECK(hipStreamSynchronize(stream));
+  coarse_info = CoarseInfo();
+  coarse_info.built_by = GMG_COARSE_BUILT_HOST_CONSTRAINED;
   return d;
 }
 
@@ -5883,6 +5893,9 @@ double *gmg_solver::build_coarse_device(const HostCSR &A, const std::string &wha
   for (size_t i = allocs.size(); i-- > mark;)
     if (allocs[i] != (void *)D) { (void)hipFree(allocs[i]); allocs.erase(allocs.begin() + (long)i); }
   dev_bytes = bytes0 + bytesD;
+  coarse_info.built_by = GMG_COARSE_BUILT_DEVICE_GJ;
+  coarse_info.panel = wide ? GJ_W : GJ_B;
+  coarse_info.mfma = gj_mfma ? 1 : 0;
   return D;
 }
 
@@ -7091,6 +7104,17 @@ const OptionKey *find_option(const char *key)
   return nullptr;
 }
 } // namespace
+
+int gmg_get_coarse_info(gmg_handle_t h, int *built_by, int *panel, int *mfma, int *device_rejected)
+{
+  return guarded(h, [&] {
+    check_ready(h);
+    if (built_by) *built_by = h->coarse_info.built_by;
+    if (panel) *panel = h->coarse_info.panel;
+    if (mfma) *mfma = h->coarse_info.mfma;
+    if (device_rejected) *device_rejected = h->coarse_info.device_rejected;
+  });
+}
 
 int gmg_set_option(gmg_handle_t h, const char *key, double value)
 {

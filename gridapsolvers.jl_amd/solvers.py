@@ -819,6 +819,14 @@ class GMGNumericalSetup:
         abi.check(self.h, self._lib.gmg_coarse_solve(self.h, pr, px, ms))
         return x
 
+    def coarse_info(self):
+        """gmg_get_coarse_info: how the setup built the dense inverse of LUSolver() on the coarsest level ->
+        dict(built_by ("none" / "host_lu" / "device_gj" / "host_constrained"), panel (0, 32 or 64), mfma, device_rejected)"""
+        v = [C.c_int(0) for _ in range(4)]
+        abi.check(self.h, self._lib.gmg_get_coarse_info(self.h, *[C.byref(q) for q in v]))
+        return dict(built_by=("none", "host_lu", "device_gj", "host_constrained")[v[0].value], panel=v[1].value,
+                    mfma=bool(v[2].value), device_rejected=bool(v[3].value))
+
     def dot(self, a, b):
         pa, ms, _k1 = _vec(a)
         pb, ms2, _k2 = _vec(b)

@@ -255,6 +255,18 @@ GMG_API int gmg_set_coarse_solver(gmg_handle_t h, int kind, int maxiter, double 
                                   gmg_coarse_solve_fn fn, void *ctx);
 /* ConvergenceLog summary of the last iterative coarse solve (GMG_COARSE_CG_JACOBI). */
 GMG_API int gmg_get_coarse_log(gmg_handle_t h, gmg_result *res);
+/* How the last gmg_setup built the dense inverse of GMG_COARSE_DENSE_INVERSE (read-only; no reference counterpart: LUSolver() has
+ * one path).  built_by: see below.  panel: width of the device Gauss-Jordan panels, 32 or 64 (gj_wide_min), 0 on the host.
+ * mfma: 1 when the device trailing update ran on the FP64 matrix cores (gj_mfma), else 0.  device_rejected: 1 when the device
+ * inversion was tried, refused the matrix with GMG_ERR_SINGULAR (zero pivot, or its own A*(Ainv*v) == v check) and the host's
+ * pivoted banded LU took over (n <= coarse_host_fallback_max).  Any output may be NULL.  GMG_ERR_STATE before a setup. */
+enum gmg_coarse_built_by {
+  GMG_COARSE_BUILT_NONE = 0,            /* the coarsest solver is not a dense inverse (CG_JACOBI, HOST_CALLBACK, or chosen by coarse_auto_cg_min) */
+  GMG_COARSE_BUILT_HOST_LU = 1,         /* banded LU with partial pivoting on the host (n <= coarse_host_max, or the fallback) */
+  GMG_COARSE_BUILT_DEVICE_GJ = 2,       /* blocked Gauss-Jordan without pivoting on the device, result verified */
+  GMG_COARSE_BUILT_HOST_CONSTRAINED = 3 /* inv([A K; K' 0]) on the host (gmg_set_coarse_nullspace) */
+};
+GMG_API int gmg_get_coarse_info(gmg_handle_t h, int *built_by, int *panel, int *mfma, int *device_rejected);
 
 /* ---- solver options --------------------------------------------------------- */
 /* kwargs of GMGLinearSolver: mode, cycle_type, maxiter, atol, rtol (GMGLinearSolvers.jl:56-58). */
