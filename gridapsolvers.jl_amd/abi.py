@@ -21,6 +21,7 @@ OP_A, OP_P, OP_R = 0, 1, 2
 LEVEL_KRYLOV = -1          # GMG_LEVEL_KRYLOV: the separate Krylov operator of a finest level in the overlapping layout
 COARSE_DENSE_INVERSE, COARSE_CG_JACOBI, COARSE_HOST_CALLBACK = 0, 1, 2
 COARSE_BUILT_NONE, COARSE_BUILT_HOST_LU, COARSE_BUILT_DEVICE_GJ, COARSE_BUILT_HOST_CONSTRAINED = 0, 1, 2, 3   # gmg_get_coarse_info
+HALO_FIX_NONE, HALO_FIX_CSR, HALO_FIX_SLICED, HALO_FIX_SLICED_DICT = 0, 1, 2, 3   # gmg_get_halo_info
 BLOCK_DIAGONAL, BLOCK_LOWER, BLOCK_UPPER, BLOCK_SCHUR = 0, 1, 2, 3
 BLOCK_GMG, BLOCK_CG_JACOBI, BLOCK_LU, BLOCK_JACOBI, BLOCK_KRYLOV_GMG = 1, 2, 3, 4, 5
 KRYLOV_CG, KRYLOV_FGMRES, KRYLOV_GMRES = 1, 2, 3
@@ -140,6 +141,9 @@ SYMBOLS = {
                                   C.c_void_p, C.c_void_p],
     "gmg_get_comm_stats": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
     "gmg_get_comm_info": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "gmg_get_halo_info": [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int),
+                          C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                          C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "gmg_set_replication": [C.c_void_p, C.c_int, C.c_void_p, C.c_int64],
     "gmg_set_krylov_map": [C.c_void_p, C.c_void_p, C.c_int64],
     "gmg_comm_set_loopback": [C.c_void_p, C.c_int],

@@ -415,6 +415,8 @@ struct GhostFix {
   int64_t *soff = nullptr;
   double *sval = nullptr, *dict = nullptr;
   uint8_t *scode = nullptr;
+  int64_t nent = 0;                 // ghost entries of these rows (gmg_get_halo_info)
+  int ndict = 0;                    // distinct doubles among the slots when they fit a dictionary, the padding zero included; else 0
 };
 
 struct GsLevel;                    // gs.inc.hpp
@@ -480,6 +482,8 @@ struct Level {
   double *gh_sval = nullptr;
   uint8_t *gh_scode = nullptr;      // one byte per entry into gh_dict (<= 256 distinct values) instead of gh_sval
   double *gh_dict = nullptr;
+  int64_t gh_nent = 0;              // ghost entries of the boundary rows; gh_ndict: GhostFix::ndict of the sliced form (gmg_get_halo_info)
+  int gh_ndict = 0;
   // the restriction of an own | ghost level split the same way (round 5): R keeps the own columns -- and with them a row-pattern
   // layout -- and runs while consistent!(r) is in flight, the ghost columns of the coarse rows next to the box faces are added afterwards
   bool r_split = false;
@@ -3029,6 +3033,7 @@ struct gmg_solver {
       code[q] = (uint8_t)it->second;
     }
     G.nb = (int64_t)nbr; G.rows = upload(brows); G.len = upload(glen); G.soff = upload(soff); G.scol = upload(scol);
+    G.nent = (int64_t)bcol.size(); G.ndict = small ? (int)dict.size() : 0;
     if (small) { dict.resize(256, 0.0); G.scode = upload(code); G.dict = upload(dict); }
     else G.sval = upload(sval);
   }
@@ -6062,12 +6067,14 @@ void gmg_solver::setup()
       L.split = true;
       L.nbnd = (int64_t)brows.size();
       L.gh_rows = upload(brows); L.gh_ptr = upload(bptr); L.gh_col = upload(bcol); L.gh_val = upload(bval);
+      L.gh_nent = (int64_t)bcol.size(); L.gh_ndict = 0;
       if (opt_int("GMG_HALO_FIX_SELL", 1) && !brows.empty()) {
         // slices of 64 boundary rows, column-major, one byte per entry into a dictionary when the values allow: ONE builder for this
         // level's fix-up and the split restriction's (build_ghost_fix) -- ghost_fix_sell_kernel reads both
         GhostFix gf;
         build_ghost_fix(gf, brows, bptr, bcol, bval);
         L.gh_len = gf.len; L.gh_soff = gf.soff; L.gh_scol = gf.scol; L.gh_scode = gf.scode; L.gh_dict = gf.dict; L.gh_sval = gf.sval;
+        L.gh_ndict = gf.ndict;
       }
       {   // send slots of every boundary row (fused pack): valid when every sent row is a boundary row
         HaloPlan &Hp = L.halo;
@@ -7892,6 +7899,33 @@ int gmg_get_comm_info(gmg_handle_t h, int *transport, int *rank, int *nranks, in
     }
     if (comm_count) *comm_count = cnt;                       // what ncclCommCount says (-1: not an RCCL communicator)
     if (comm_device) *comm_device = dev >= 0 ? dev : h->device;
+  });
+}
+
+int gmg_get_halo_info(gmg_handle_t h, int lev, int64_t *boundary_rows, int64_t *send_slots, int64_t *ghost_entries, int *fix_form,
+                      int *dict_values, int *pack_fused, int *r_split, int64_t *r_boundary_rows, int64_t *r_ghost_entries, int *r_form,
+                      int *r_dict_values)
+{
+  return guarded(h, [&] {
+    check_ready(h);
+    check_level(h, lev, false);
+    const Level &L = h->lev[lev];
+    REQUIRE(h->comm.nranks > 1 && L.halo.present && !L.halo.ovl, GMG_ERR_STATE,
+            "gmg_get_halo_info: not a partitioned level in the own | ghost layout");
+    auto form = [](int64_t nb, const void *code, const void *sval) {
+      return nb <= 0 ? GMG_HALO_FIX_NONE : code ? GMG_HALO_FIX_SLICED_DICT : sval ? GMG_HALO_FIX_SLICED : GMG_HALO_FIX_CSR;
+    };
+    if (boundary_rows) *boundary_rows = L.nbnd;
+    if (send_slots) *send_slots = L.halo.nsend();
+    if (ghost_entries) *ghost_entries = L.gh_nent;
+    if (fix_form) *fix_form = form(L.nbnd, L.gh_scode, L.gh_sval);
+    if (dict_values) *dict_values = L.gh_scode ? L.gh_ndict : 0;
+    if (pack_fused) *pack_fused = h->can_fuse_pack(lev) ? 1 : 0;
+    if (r_split) *r_split = L.r_split ? 1 : 0;
+    if (r_boundary_rows) *r_boundary_rows = L.r_split ? L.rfix.nb : 0;
+    if (r_ghost_entries) *r_ghost_entries = L.r_split ? L.rfix.nent : 0;
+    if (r_form) *r_form = L.r_split ? form(L.rfix.nb, L.rfix.scode, L.rfix.sval) : GMG_HALO_FIX_NONE;
+    if (r_dict_values) *r_dict_values = L.r_split && L.rfix.scode ? L.rfix.ndict : 0;
   });
 }
 

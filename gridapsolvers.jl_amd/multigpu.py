@@ -463,6 +463,21 @@ class DistributedGMG:
         return dict(transport=("none", "rccl", "host")[v[0].value], rank=v[1].value, nranks=v[2].value, rccl_comm_count=v[3].value,
                     device=v[4].value)
 
+    def halo_info(self, lev=0):
+        """what the setup decided for the own | ghost split of partitioned level `lev` (gmg_get_halo_info): boundary rows, send slots,
+        ghost entries, the fix-up's form ("none" / "csr" / "sliced" / "sliced+dict") and its dictionary's distinct-value count, whether
+        the pack is fused into the fix-up, whether R is split and the same figures for its ghost part"""
+        i64 = [C.c_int64(0) for _ in range(5)]
+        i32 = [C.c_int(0) for _ in range(6)]
+        abi.check(self.h, self._lib.gmg_get_halo_info(self.h, lev, C.byref(i64[0]), C.byref(i64[1]), C.byref(i64[2]), C.byref(i32[0]),
+                                                      C.byref(i32[1]), C.byref(i32[2]), C.byref(i32[3]), C.byref(i64[3]), C.byref(i64[4]),
+                                                      C.byref(i32[4]), C.byref(i32[5])))
+        forms = ("none", "csr", "sliced", "sliced+dict")
+        return dict(boundary_rows=int(i64[0].value), send_slots=int(i64[1].value), ghost_entries=int(i64[2].value),
+                    fix_form=forms[i32[0].value], dict_values=i32[1].value, pack_fused=bool(i32[2].value), r_split=bool(i32[3].value),
+                    r_boundary_rows=int(i64[3].value), r_ghost_entries=int(i64[4].value), r_form=forms[i32[4].value],
+                    r_dict_values=i32[5].value)
+
     def close(self):
         if getattr(self, "h", None):
             self._lib.gmg_destroy(self.h)

@@ -595,6 +595,25 @@ GMG_API int gmg_get_comm_stats(gmg_handle_t h, int64_t *n_exchanges, int64_t *n_
  * reports for the communicator (ncclCommCount; -1 when not RCCL) and the HIP device it sits on (ncclCommCuDevice / the handle's
  * device).  Any pointer may be NULL.  bench.py prints these so that a multi-GPU line shows how many ranks RCCL really saw. */
 GMG_API int gmg_get_comm_info(gmg_handle_t h, int *transport, int *rank, int *nranks, int *comm_count, int *comm_device);
+/* What the last gmg_setup decided for the own | ghost split of partitioned level `lev` (read-only: it records decisions and changes
+ * none; no reference counterpart -- PartitionedArrays has one form).  boundary_rows: owned rows with at least one ghost column, the rows
+ * the fix-up after the exchange finishes; send_slots: entries of the level's send lists; ghost_entries: stored entries in ghost
+ * columns.  fix_form: how the fix-up holds them, see below (halo_fix_sell, halo_fix_dict); dict_values: distinct doubles among the
+ * slots of the sliced form when it carries a dictionary -- the 0.0 of padded slots counts as one, so at most 256 -- else 0.
+ * pack_fused: 1 when every sent row is a boundary row and the fix-up of a sweep writes the next sweep's send buffer (halo_fuse_pack),
+ * 0 when a pack kernel runs before every exchange.  r_split: 1 when the level's restriction is split the same way (halo_split_r);
+ * r_boundary_rows / r_ghost_entries / r_form / r_dict_values: the same for the coarse rows of R that read ghost columns (zeros, and
+ * GMG_HALO_FIX_NONE, without the split).  Any output may be NULL.  GMG_ERR_STATE before a setup, and on a level that is not
+ * partitioned in the own | ghost layout (single rank, replicated, overlapping layout). */
+enum gmg_halo_fix_form {
+  GMG_HALO_FIX_NONE = 0,                /* no row reads a ghost column: no fix-up runs */
+  GMG_HALO_FIX_CSR = 1,                 /* one thread walks each boundary row (ghost_fix_kernel) */
+  GMG_HALO_FIX_SLICED = 2,              /* slices of 64 boundary rows, column-major, values as doubles (ghost_fix_sell_kernel) */
+  GMG_HALO_FIX_SLICED_DICT = 3          /* the same with one-byte codes into a dictionary of <= 256 doubles */
+};
+GMG_API int gmg_get_halo_info(gmg_handle_t h, int lev, int64_t *boundary_rows, int64_t *send_slots, int64_t *ghost_entries,
+                              int *fix_form, int *dict_values, int *pack_fused, int *r_split, int64_t *r_boundary_rows,
+                              int64_t *r_ghost_entries, int *r_form, int *r_dict_values);
 /* Levels >= lev are REPLICATED: every rank passes the GLOBAL operators of those levels
  * (gmg_set_matrix / _prolongation / _restriction, no gmg_set_partition) and computes them
  * redundantly -- no halo traffic where the level is tiny.  Across the boundary, P_{lev-1} has
