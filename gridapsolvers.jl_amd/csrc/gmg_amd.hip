@@ -957,7 +957,7 @@ struct gmg_solver {
     d_Ainv = d_partials = d_scalars = nullptr;
     d_partials2 = nullptr;
     cc_w = cc_p = cc_z = cc_r = nullptr;
-    d_rep_gid = nullptr; d_rep_tmp = nullptr; cg_x = nullptr; d_own2loc = nullptr;
+    d_rep_gid = nullptr; d_rep_tmp = nullptr; cg_x = nullptr; d_own2loc = nullptr; d_vr = nullptr;
     redist.glue_r = redist.glue_x = nullptr;
     for (auto &q : redist.d_self) q = nullptr;
     for (HaloPlan *H : {&redist.to_sub, &redist.from_sub}) { H->d_snd_idx = nullptr; H->d_sendbuf = nullptr; H->d_recvbuf = nullptr; H->d_pk_ptr = nullptr; H->d_pk_slot = nullptr; }
@@ -2774,8 +2774,40 @@ struct gmg_solver {
     HIP_CHECK(hipGetLastError());
     return nb;
   }
+  // Loopback communicator with gmg_comm_set_loopback_rows: a vector of the Krylov level is reduced as the W ranks of the folded
+  // partition would reduce it -- every virtual rank's rows by themselves (the same kernels on the same row counts), the W sums added
+  // in rank order (the all-reduce), the square root last -- so that a folded run reproduces the scalars of the W-rank run bit for bit.
+  std::vector<int64_t> vr_off;         // row offsets of the virtual ranks' owned rows (W + 1 entries); empty: one reduction over all rows
+  double *d_vr = nullptr;              // W local sums
+  bool vr_split(int64_t n) const { return comm.loopback && !reduce_local && vr_off.size() > 1 && n == vr_off.back(); }
+  int vr_count() const { return (int)vr_off.size() - 1; }
+  double *vr_sums()
+  {
+    if (!d_vr) d_vr = dvec(vr_count());
+    return d_vr;
+  }
+  // the W local sums -> d_scalars[slot], then what finish_reduction does after its local sum
+  void vr_finish(int slot, bool take_sqrt)
+  {
+    hipLaunchKernelGGL(sum_in_order_kernel, dim3(1), dim3(1), 0, stream, vr_count(), d_vr, d_scalars + slot);
+    HIP_CHECK(hipGetLastError());
+    posted = 0;
+    allreduce_slot(slot, take_sqrt);
+  }
   void dot_async(int64_t n, const double *a, const double *b, int slot, bool take_sqrt, bool post = false)
   {
+    if (vr_split(n)) {
+      double *sums = vr_sums();
+      for (int q = 0; q < vr_count(); ++q) {
+        const int64_t o = vr_off[(size_t)q], nq = vr_off[(size_t)q + 1] - o;
+        // (offsets are even, gmg_comm_set_loopback_rows: a + o is aligned as the rank's own vector is, so dot_partial_kernel takes the same form)
+        const int nbq = dot_partials(nq, a + o, b + o, d_partials);
+        hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kBlock), 0, stream, nbq, d_partials, sums + q, 0);
+        HIP_CHECK(hipGetLastError());
+      }
+      vr_finish(slot, take_sqrt);
+      return;
+    }
     const int nb = dot_partials(n, a, b, d_partials);
     finish_reduction(nb, slot, take_sqrt, d_partials, post);
   }
@@ -2805,6 +2837,11 @@ struct gmg_solver {
                        (take_sqrt && !dist) ? 1 : 0);
     HIP_CHECK(hipGetLastError());
     if (!dist) return;
+    allreduce_slot(slot, take_sqrt);
+  }
+  // d_scalars[slot] holds this rank's sum: all-reduce over the parts, then the square root
+  void allreduce_slot(int slot, bool take_sqrt)
+  {
     ++n_allreduces;
     if (comm.kind == COMM_RCCL) {
       const int rc = comm.api.AllReduce(d_scalars + slot, d_scalars + slot, 1, kNcclDouble, kNcclSum, comm.comm, stream);
@@ -3067,9 +3104,10 @@ struct gmg_solver {
     spmv_set(lev[l].A, x, y);
     finish_ghost<0>(l, x, y);
   }
-  void apply_A_sub(int l, double *x, double *y, const Smoother *next = nullptr)
+  // prepacked: the send buffer already holds x's send entries (gs_update_pack_kernel)
+  void apply_A_sub(int l, double *x, double *y, const Smoother *next = nullptr, bool prepacked = false)
   {
-    begin_exchange(l, x);
+    begin_exchange(l, x, prepacked);
     Level &L = lev[l];
     // the smoothing pass that follows starts from s = omega*(Dinv*y): let this kernel write it
     if (next && emits_s0(L, *next, L.A)) {
@@ -4432,6 +4470,18 @@ static double cg_core(gmg_solver &S, int64_t n, const double *db, double *dx, do
       S.finish_reduction(nb, 0, true, nparts, true);
       hipLaunchKernelGGL(cg_update_x_kernel, dim3(nb), dim3(kBlock), 0, S.stream, n, S.d_scalars + g_new, S.d_scalars + kPW, p, dx);   // :108
       HIP_CHECK(hipGetLastError());
+    } else if (S.vr_split(n)) {
+      // (gmg_comm_set_loopback_rows: the update and its partial ||r||^2 per virtual rank, as the W ranks launch them)
+      double *sums = S.vr_sums();
+      for (int q = 0; q < S.vr_count(); ++q) {
+        const int64_t o = S.vr_off[(size_t)q], nq = S.vr_off[(size_t)q + 1] - o;
+        const int nbq = (int)std::max<int64_t>(1, std::min<int64_t>(kRedBlocks, (nq + kBlock - 1) / kBlock));
+        hipLaunchKernelGGL(cg_update_kernel, dim3(nbq), dim3(kBlock), 0, S.stream, nq, S.d_scalars + g_new, S.d_scalars + kPW, p + o, w + o,
+                           dx + o, r + o, nparts, (const double *)nullptr, 0);
+        hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kBlock), 0, S.stream, nbq, nparts, sums + q, 0);
+        HIP_CHECK(hipGetLastError());
+      }
+      S.vr_finish(0, true);
     } else {
     hipLaunchKernelGGL(cg_update_kernel, dim3(nb), dim3(kBlock), 0, S.stream, n, S.d_scalars + g_new, S.d_scalars + kPW, p, w, dx, r,
                        nparts, npw ? S.d_partials : nullptr, npw); // :108-109
@@ -5921,9 +5971,12 @@ void gmg_solver::setup()
     std::fprintf(stderr, "[gmg_setup] level %d %-28s %8.1f ms\n", l, what, std::chrono::duration<double, std::milli>(now - t_last).count());
     t_last = now;
   };
+  // Gauss-Seidel on several ranks is rank-block Gauss-Seidel (gs.inc.hpp): own | ghost and replicated levels.  Sweeping the extended
+  // box of the overlapping layout is another method, without a counterpart in the reference
   for (int l = 0; l < nlev - 1; ++l)
-    REQUIRE(comm.nranks == 1 || (lev[l].pre.kind != SM_GAUSS_SEIDEL && lev[l].post.kind != SM_GAUSS_SEIDEL), GMG_ERR_UNSUPPORTED,
-            "Gauss-Seidel smoothers are single-GPU: this handle's communicator has more than one rank (real or loopback)");
+    REQUIRE(!(comm.nranks > 1 && lev[l].halo.present && lev[l].halo.ovl) || (lev[l].pre.kind != SM_GAUSS_SEIDEL && lev[l].post.kind != SM_GAUSS_SEIDEL),
+            GMG_ERR_UNSUPPORTED, "Gauss-Seidel smoother on level " + std::to_string(l) + ": the overlapping layout (gmg_set_partition_overlap) is not "
+            "supported, rank-block sweeps need the own | ghost layout (gmg_set_partition)");
   // patch smoothers / patch corrections with patches of more than 64 dofs take their blocks from the level's CSR (one thread block
   // per patch): a level kept in row-pattern form only gets its rows back
   for (int l = 0; l < nlev - 1; ++l) {
@@ -5943,7 +5996,9 @@ void gmg_solver::setup()
     for (int l = 0; l < nlev; ++l) {
       Level &L = lev[l];
       const bool own_ghost = L.halo.present && !L.halo.ovl;
-      if (own_ghost && L.sA && L.sA->complete() && !L.sA_split) rows_from_stream(L);
+      // (a Gauss-Seidel level builds its tables from the rows of the own x own block: a split stream gives its rows back as well)
+      const bool gs = l < nlev - 1 && (L.pre.kind == SM_GAUSS_SEIDEL || L.post.kind == SM_GAUSS_SEIDEL);
+      if (own_ghost && L.sA && L.sA->complete() && (!L.sA_split || gs)) rows_from_stream(L);
     }
   }
   if (redist.present) {
@@ -6023,7 +6078,7 @@ void gmg_solver::setup()
     }
     if (comm.nranks > 1 && L.halo.present && !L.halo.ovl)
       for (const Smoother *sp : {&L.pre, &L.post})
-        REQUIRE(sp->kind == SM_JACOBI || (sp->tab && sp->tab->has_blocks), GMG_ERR_UNSUPPORTED,
+        REQUIRE(sp->kind == SM_JACOBI || sp->kind == SM_GAUSS_SEIDEL || (sp->tab && sp->tab->has_blocks), GMG_ERR_UNSUPPORTED,
                 "distributed patch smoothers need the caller's patch matrices (gmg_set_smoother_patch_matrices): a rank's local matrix "
                 "holds the owned rows only, the blocks of patches reaching into ghost dofs cannot be gathered from it");
   }
@@ -6151,7 +6206,7 @@ void gmg_solver::setup()
       // :189-190 smoother caches: inv_diag = 1 ./ diag(A) (JacobiLinearSolvers.jl:20-23)
       int nzero = 0;
       L.dinv = build_inv_diag(L.A, nzero);
-      const bool need_diag = (L.pre.kind == SM_JACOBI) || (L.post.kind == SM_JACOBI);
+      const bool need_diag = (L.pre.kind == SM_JACOBI) || ((L.post_shares_pre ? L.pre : L.post).kind == SM_JACOBI);   // (a shared post is copied from pre below)
       REQUIRE(!(need_diag && nzero > 0), GMG_ERR_SINGULAR, "zero diagonal entry on level " + std::to_string(l));
       if (L.has_pcorr) {
         if (comm.nranks > 1 && L.halo.present && !L.halo.ovl) {
@@ -7097,7 +7152,7 @@ const OptionKey kOptionKeys[] = {
   {"GMG_PERSIST_SHARED", false}, {"GMG_PROF_STRIDE", true}, {"GMG_REFRESH", true}, {"GMG_SELL", false}, {"GMG_SELL_BLOCK", false},
   {"GMG_SELL_DEFER", false}, {"GMG_SELL_MAXPAD", false}, {"GMG_SELL_UN", false}, {"GMG_SETUP_TIMING", true}, {"GMG_VDICT", false},
   {"GMG_XCD_REMAP", false}, {"GMG_XCD_REMAP_BIG", false}, {"GMG_X0_ZERO", true}, {"GMG_HOST_POLL", true}, {"GMG_HOST_CHUNK_BYTES", true}, {"GMG_PAT_FMA", false}, {"GMG_PAT_R2", false}, {"GMG_RED_FUSED", false}, {"GMG_GMRES_FUSED", true}, {"GMG_FGMRES_FUSED", true}, {"GMG_NULLSPACE_FUSED", true}, {"GMG_PAT_R2MV", false}, {"GMG_PAT_R2_OCC", false}, {"GMG_PAT_PAIR_P", false}, {"GMG_PAT_R2MV_DOT", false}, {"GMG_PERSIST_WPB", false}, {"GMG_HOST_TIMELINE", true}, {"GMG_PAT_R2MV_MIN", false}, {"GMG_PAT_BCAST", false}, {"GMG_PAT_R2_WGS", false}, {"GMG_PAT_ZWALK", false}, {"GMG_PAT_ZWALK_T", false}, {"GMG_PAT_ZWALK_ROWS", false}, {"GMG_PAT_ZWALK_MV", false}, {"GMG_PAT_ZWALK_WIDE", false}, {"GMG_PAT_ZWALK_WIDE_ROWS", false}, {"GMG_PAT_FUSE2", false}, {"GMG_PAT_FUSE2_W", false}, {"GMG_PAT_FUSE2_T", false}, {"GMG_PAT_FUSE2_ROWS", false}, {"GMG_PAT_FUSE2_BOX", false}, {"GMG_PAT_BOX", false}, {"GMG_PAT_WIDE_GRID", false}, {"GMG_PAT_BOX_T", false}, {"GMG_PAT_BOX_MIN_ROWS", false}, {"GMG_PAT_BOX_MAX_ROWS", false},
-  {"GMG_PERSIST_FORCE_TIMEOUT", true}, {"GMG_PAT_XNEXT", false}, {"GMG_PAT_CLOSE", false}, {"GMG_CG_SPLIT", true}, {"GMG_GS_WIDE", true},
+  {"GMG_PERSIST_FORCE_TIMEOUT", true}, {"GMG_PAT_XNEXT", false}, {"GMG_PAT_CLOSE", false}, {"GMG_CG_SPLIT", true}, {"GMG_GS_WIDE", true}, {"GMG_GS_PACK_FUSED", true},
 };
 // "pat_tile", "PAT_TILE" and "GMG_PAT_TILE" name the same option
 const OptionKey *find_option(const char *key)
@@ -7830,6 +7885,26 @@ int gmg_comm_set_loopback(gmg_handle_t h, int virtual_nranks)
     REQUIRE(virtual_nranks >= 2, GMG_ERR_INVALID, "virtual_nranks must be >= 2");
     h->comm.loopback = true; h->comm.rank = 0; h->comm.nranks = virtual_nranks;
     h->touch();
+  });
+}
+
+int gmg_comm_set_loopback_rows(gmg_handle_t h, const int64_t *own_rows, int virtual_nranks)
+{
+  return guarded(h, [&] {
+    REQUIRE(h, GMG_ERR_INVALID, "null handle");
+    REQUIRE(h->comm.loopback, GMG_ERR_STATE, "gmg_comm_set_loopback first");
+    if (!own_rows) { h->vr_off.clear(); return; }
+    REQUIRE(virtual_nranks == h->comm.nranks, GMG_ERR_INVALID, "gmg_comm_set_loopback_rows: one row count per virtual rank (" +
+            std::to_string(h->comm.nranks) + ")");
+    std::vector<int64_t> off(1, 0);
+    for (int q = 0; q < virtual_nranks; ++q) {
+      REQUIRE(own_rows[q] >= 0, GMG_ERR_INVALID, "gmg_comm_set_loopback_rows: negative row count of virtual rank " + std::to_string(q));
+      // a rank's own vectors begin 16-byte aligned, which selects the two-rows-per-load form of the dot kernel: so must its part here
+      REQUIRE(q + 1 == virtual_nranks || own_rows[q] % 2 == 0, GMG_ERR_UNSUPPORTED, "gmg_comm_set_loopback_rows: virtual rank " +
+              std::to_string(q) + " owns an odd number of rows; the next rank's part of a folded vector would not be 16-byte aligned");
+      off.push_back(off.back() + own_rows[q]);
+    }
+    h->vr_off = std::move(off);
   });
 }
 

@@ -32,6 +32,20 @@
 //                   Same subtractions in the same order as gs_sets_kernel: the same bits.  Where w == 1 and EVERY launch of the
 //                   direction's plan is wide, each lane also updates x and the gs_update_kernel launch of that direction is dropped.
 // The natural order keeps gs_sets_kernel for both shapes.
+//
+// SEVERAL RANKS (the reference's distributed form, :155-165 with :71-75 / :93-97): every rank builds DiagonalIndices of its local matrix
+// over own_to_local(indices) and runs forward_sub! / backward_sub! on own_values(x), so the triangles are those of the OWN x OWN BLOCK
+// of each rank -- rank-block Gauss-Seidel, no communication inside a triangular solve -- and mul!(Adx, A, dx) is the distributed
+// product with its halo exchange.  On an own | ghost level (gmg_set_partition) schedule, colouring, given order and tables are those
+// of rows [0, n_own) and the stored columns < n_own of the level matrix; ghost columns enter nothing here, they are applied by
+// r -= A dx (apply_A_sub: begin_exchange(dx), own columns, boundary fix-up).  A replicated level sweeps its global matrix (the
+// reference with one part at that level); the overlapping layout is refused at gmg_setup.
+//   gs_update_pack_kernel  dx .= w dx ; x .+= dx AND the pack of dx's send entries in one launch (option gs_pack_fused, default 1), on
+//                   levels whose pack can fuse (can_fuse_pack: every sent row is a boundary row).  THE CHOICE: a row -> boundary-row
+//                   index table of the level (GsLevel::bidx, -1 off the boundary) leads the lane that updates row i to the row's
+//                   send slots (the level's d_pk_ptr / d_pk_slot), and that lane stores the value it has just written to dx[i]:
+//                   nobody reads dx[i] while another lane scales it.  Same roundings as gs_update_kernel.  Where the x update folds
+//                   into gs_wide_kernel there is no update launch and the pack stays halo_pack_kernel.
 
 namespace {
 
@@ -60,6 +74,7 @@ struct GsLevel {
   int order_kind = GMG_GS_ORDER_NATURAL;
   int64_t ncolors = 0;
   std::vector<int32_t> order;
+  int32_t *bidx = nullptr;   // own | ghost level: index of row i among the boundary rows (rows with a ghost column), -1 for the others
 };
 
 // rows of sets [s0, s1): dx[i] = (r[i] - sum_j a_ij dx[j]) / a_ii over the strict triangle in table order
@@ -153,6 +168,40 @@ __global__ void gs_update_kernel(int64_t n, double omega, int scale, int x_zero,
     if (scale) { d = __dmul_rn(omega, d); dx[i] = d; }
     x[i] = x_zero ? d : __dadd_rn(x[i], d);
   }
+}
+
+// gs_update_kernel on an own | ghost level + the pack of dx's send entries: the lane of row i stores the value it wrote to dx[i] into
+// the row's send slots pk_slot[pk_ptr[q] .. pk_ptr[q + 1]), q = bidx[i] (every slot is below the length of sendbuf: gmg_setup)
+__global__ void gs_update_pack_kernel(int64_t n, double omega, int scale, int x_zero, double *__restrict__ dx, double *__restrict__ x,
+                                      const int32_t *__restrict__ bidx, const int64_t *__restrict__ pk_ptr, const int32_t *__restrict__ pk_slot,
+                                      double *__restrict__ sendbuf)
+{
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {   // (grid_for caps the grid)
+    const int32_t q = bidx[i];
+    double d = dx[i];
+    if (scale) { d = __dmul_rn(omega, d); dx[i] = d; }
+    x[i] = x_zero ? d : __dadd_rn(x[i], d);
+    if (q >= 0)
+      for (int64_t k = pk_ptr[q]; k < pk_ptr[q + 1]; ++k) sendbuf[pk_slot[k]] = d;
+  }
+}
+
+// the own x own block of an own | ghost level matrix: rows as they are, the stored columns below n_own in storage order
+void gs_own_block(const HostCSR &A, int64_t n_own, HostCSR &B)
+{
+  B.nrows = B.ncols = n_own;
+  B.ptr.assign((size_t)n_own + 1, 0);
+  for (int64_t i = 0; i < n_own; ++i) {
+    int64_t cnt = 0;
+    for (int64_t k = A.ptr[(size_t)i]; k < A.ptr[(size_t)i + 1]; ++k) cnt += A.col[(size_t)k] < n_own ? 1 : 0;
+    B.ptr[(size_t)i + 1] = B.ptr[(size_t)i] + cnt;
+  }
+  B.col.resize((size_t)B.ptr[(size_t)n_own]); B.val.resize((size_t)B.ptr[(size_t)n_own]);
+  parallel_for(n_own, [&](int64_t i) {
+    int64_t at = B.ptr[(size_t)i];
+    for (int64_t k = A.ptr[(size_t)i]; k < A.ptr[(size_t)i + 1]; ++k)
+      if (A.col[(size_t)k] < n_own) { B.col[(size_t)at] = A.col[(size_t)k]; B.val[(size_t)at] = A.val[(size_t)k]; ++at; }
+  });
 }
 
 // columns ascending inside every row: A itself when they are, a sorted copy in `tmp` otherwise
@@ -327,6 +376,14 @@ void gmg_solver::build_gs(int l, bool values_only)
   HostCSR expanded, sorted;
   const HostCSR *A0 = &L.hA;
   if (L.sA) { expanded = expand_stream(*L.sA); A0 = &expanded; }
+  // own | ghost level (several ranks): the rank's block of rank-block Gauss-Seidel, rows [0, n_own) x stored columns < n_own
+  const bool own_ghost = comm.nranks > 1 && L.halo.present && !L.halo.ovl;
+  HostCSR block;
+  if (own_ghost) {
+    REQUIRE(A0->nrows == L.n && A0->ncols == L.nvec, GMG_ERR_INVALID, "Gauss-Seidel smoother: the local matrix must be n_own x (n_own + n_ghost) on level " + std::to_string(l));
+    gs_own_block(*A0, L.n, block);
+    A0 = &block;
+  }
   REQUIRE(A0->nrows == A0->ncols && A0->nrows == L.n, GMG_ERR_INVALID, "Gauss-Seidel smoother: the level matrix must be square");
   const HostCSR &An = gs_sorted_rows(*A0, sorted);
   std::vector<int64_t> dpos = gs_diag_positions(An);
@@ -347,6 +404,18 @@ void gmg_solver::build_gs(int l, bool values_only)
               std::to_string(L.gs_order.size()) + " entries, the level has " + std::to_string(An.nrows) + " rows (position " +
               std::to_string(std::min<int64_t>((int64_t)L.gs_order.size(), An.nrows)) + ")");
       G.order = L.gs_order;
+    }
+    if (own_ghost && L.halo.d_pk_ptr) {                       // row -> boundary-row index, in the order gmg_setup numbers the boundary rows
+      const HostCSR &W = L.sA ? expanded : L.hA;
+      std::vector<int32_t> bidx((size_t)L.n, -1);
+      int32_t q = 0;
+      for (int64_t i = 0; i < L.n; ++i) {
+        bool any = false;
+        for (int64_t k = W.ptr[(size_t)i]; k < W.ptr[(size_t)i + 1] && !any; ++k) any = W.col[(size_t)k] >= L.n;
+        if (any) bidx[(size_t)i] = q++;
+      }
+      REQUIRE((int64_t)q == L.nbnd, GMG_ERR_STATE, "Gauss-Seidel smoother: boundary rows of level " + std::to_string(l) + " do not match the halo split");
+      G.bidx = upload(bidx);
     }
   }
   REQUIRE(L.gs != nullptr, GMG_ERR_STATE, "Gauss-Seidel smoother: value refresh without a schedule");
@@ -422,8 +491,14 @@ void gmg_solver::gs_pass(int l, Smoother &S, double *x, double *r, bool x_zero)
       // profiled level: HIP events around the solve and the update of every direction, weighted with their launches
       const bool prof = (l == prof_level) && prof_used + 2 <= prof_ev.size();
       if (prof) HIP_CHECK(hipEventRecord(prof_ev[prof_used], stream));
+      // own | ghost level whose pack can fuse: the update launch also fills the send buffer of dx's exchange (gs_update_pack_kernel)
+      const bool pack = !fold && can_fuse_pack(l) && L.gs->bidx != nullptr && opt_int("GMG_GS_PACK_FUSED", 1) != 0;
       gs_solve(L, dir, r, L.dx, fold ? (xz ? 2 : 1) : 0, x);   // :187-188 / :196-197
-      if (!fold) {
+      if (pack) {
+        hipLaunchKernelGGL(gs_update_pack_kernel, dim3(grid_for(n)), dim3(256), 0, stream, n, S.omega, S.omega != 1.0 ? 1 : 0, xz ? 1 : 0, L.dx, x,
+                           L.gs->bidx, L.halo.d_pk_ptr, L.halo.d_pk_slot, L.halo.d_sendbuf);
+        HIP_CHECK(hipGetLastError());
+      } else if (!fold) {
         hipLaunchKernelGGL(gs_update_kernel, dim3(grid_for(n)), dim3(256), 0, stream, n, S.omega, S.omega != 1.0 ? 1 : 0, xz ? 1 : 0, L.dx, x);   // :189-190
         HIP_CHECK(hipGetLastError());
       }
@@ -434,7 +509,7 @@ void gmg_solver::gs_pass(int l, Smoother &S, double *x, double *r, bool x_zero)
         prof_used += 2;
       }
       xz = false;
-      apply_A_sub(l, L.dx, r);                              // :191-192
+      apply_A_sub(l, L.dx, r, nullptr, pack);               // :191-192 (the distributed product: exchanges dx)
     }
 }
 

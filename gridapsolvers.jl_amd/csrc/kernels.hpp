@@ -3849,6 +3849,14 @@ __global__ __launch_bounds__(kBlock) void reduce_final_kernel(int nparts, const 
   if (threadIdx.x == 0) out[0] = take_sqrt ? sqrt(t) : t;
 }
 
+// out[0] = ((v[0] + v[1]) + v[2]) + ... : the sums of the ranks of a folded partition added in rank order (one lane)
+__global__ void sum_in_order_kernel(int n, const double *__restrict__ v, double *__restrict__ out)
+{
+  double s = v[0];
+  for (int i = 1; i < n; ++i) s = __dadd_rn(s, v[i]);
+  out[0] = s;
+}
+
 // reduce_final_kernel + post_scalar_kernel in one launch: the scalar is also posted into host-mapped memory (fetch_scalar polls the number)
 __global__ __launch_bounds__(kBlock) void reduce_post_kernel(int nparts, const double *__restrict__ partials, double *__restrict__ out,
                                                              int take_sqrt, double *value, unsigned long long *seq, unsigned long long want)

@@ -1247,6 +1247,7 @@ Distributed counterpart of `numerical_setup(ss, A::AbstractMatrix)`: `s.smatrice
 PSparseMatrix of every level (explicit R is required: a local Pᵀ misses off-rank rows).  Levels `replicate_from:nlev`
 are gathered (`PA.to_trivial_partition`-style, here `_gather_global`) and computed redundantly on every rank -- the
 analogue of coarse levels living on fewer ranks (ModelHierarchies.jl:80-148) without the redistribution traffic.
+Gauss-Seidel smoothers pass through like the others: rank-block sweeps on the partitioned levels, global sweeps on the replicated ones.
 """
 function Gridap.Algebra.numerical_setup(ss::HipGMGSymbolicSetup, A::PA.PSparseMatrix;
                                         comm::MPI.Comm = MPI.COMM_WORLD, transport::Symbol = :rccl,
@@ -1303,6 +1304,10 @@ function Gridap.Algebra.numerical_setup(ss::HipGMGSymbolicSetup, A::PA.PSparseMa
     end
     s.post_smoothers[l] === s.pre_smoothers[l] ? _set_smoother(h, l-1, GMG_PRE_AND_POST, s.pre_smoothers[l]) :
       (_set_smoother(h, l-1, GMG_PRE, s.pre_smoothers[l]); _set_smoother(h, l-1, GMG_POST, s.post_smoothers[l]))
+    # GaussSeidelSmoother on a partitioned level: rank-block sweeps (every rank the own x own block of its local matrix,
+    # SymGaussSeidelSmoothers.jl:155-165).  The ordering is PER RANK: :multicolor colours the rank's own block, a permutation is one of
+    # the rank's own_length owned rows (1-based, as on one rank); on a replicated level it is one of the global rows.
+    s.gs_ordering[l] === :natural || _set_gs_ordering(h, l-1, s.gs_ordering[l])
   end
   tols = s.log.tols
   check(h, ccall((:gmg_set_options, libgmgamd), Cint, (Ptr{Cvoid},Cint,Cint,Cint,Float64,Float64), h,

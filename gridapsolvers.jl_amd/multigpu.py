@@ -20,7 +20,7 @@ import time
 import numpy as np
 
 from . import abi, partition as pa, poisson as po
-from .solvers import ConvergenceLog, _vec
+from .solvers import ConvergenceLog, GaussSeidelSmoother, _vec
 
 
 def rccl_path():
@@ -119,12 +119,19 @@ class DistributedGMG:
                  order=1, niter=10, omega=2.0 / 3.0, mode="preconditioner", cycle_type="v_cycle",
                  gmg_maxiter=1, gmg_atol=1e-14, gmg_rtol=1e-8, local_hierarchy=None, lengths=None, rep_from=None,
                  smoother="jacobi", depth=None, patch_tables=None, pcorr_tables=None, cells_global=None, options=None,
-                 stream_rows=0, finest_depth=0, sub_from=None, sub_ranks=None):
+                 stream_rows=0, finest_depth=0, sub_from=None, sub_ranks=None, gs_orders=None, loopback_rows=None):
         """smoother = "jacobi": Richardson(Jacobi, niter, omega); "patch": Richardson(PatchSolver, niter, omega) with the
         vertex-star patches OWNED by this rank (partition.local_vertex_star_patches) and caller-assembled patch matrices --
         a rank's local matrix has the owned rows only, so the blocks of patches reaching into ghost dofs come from the
         driver, as the reference assembles them from the solver's weak form on the local (ghosted) mesh
         (PatchSolvers.jl:137-150).
+        smoother = a solvers.GaussSeidelSmoother / SymGaussSeidelSmoother(...) object: that smoother (its niter, omega, type and ordering;
+        the arguments niter / omega are not used) pre and post on every smoothed level, as rank-block Gauss-Seidel on the partitioned
+        levels -- every rank sweeps the own x own block of its local matrix, r -= A dx is the distributed product -- and as global
+        sweeps on the replicated ones.  "natural" and "multicolor" hold per rank block; a given order is per level and per rank: a
+        list indexed by level, gs_orders, whose entry l is this rank's permutation of the level's owned rows (None: the smoother's
+        ordering; a folded partition takes the permutation of the folded own block; a replicated level one of its global rows).  Needs the own | ghost layout: depth / finest_depth other than None / 0 raise
+        ValueError.
         local_hierarchy: ready-made local operators (dict like partition.build_local_hierarchy's: levels = objects with A, P, R, n_own,
         n_ghost, nbr_rank, snd_ptr, snd_idx, rcv_ptr, replicated; rep_from; rep_gid) -- e.g. from dpartition for the vector-valued
         Stokes velocity hierarchy; then patch_tables[l] = (patch_ptr, dofs, blocks) supplies the smoother's patches per level
@@ -139,10 +146,26 @@ class DistributedGMG:
         sub_from / sub_ranks: the partitioned levels sub_from .. rep_from-1 on the first `sub_ranks` ranks only (np_per_level /
         redistribute! of the reference; gmg_set_redistribution: glued partition on all ranks + the subset's, two p2p plans) -- a
         capability: the communication model never prefers it on this hardware.
+        loopback_rows (loopback transports): the owned rows of every folded rank on level 0 (gmg_comm_set_loopback_rows) -- the dot
+        products and norms of CG are then reduced rank by rank and added in rank order, the scalars of the true W-rank run.
         stream_rows > 0: the operators of the levels that are laid out like a single-GPU level -- overlapping layout, replicated levels
         -- are handed over in blocks of that many rows (gmg_set_operator_rows): the library keeps their row-pattern form only, never
         a CSR copy (what a per-rank assembler that produces its rows plane by plane would do)."""
         import torch.distributed as dist
+        gs = smoother if isinstance(smoother, GaussSeidelSmoother) else None
+        if gs is not None:
+            if (depth is not None and np.any(np.asarray(depth) != 0)) or finest_depth:
+                raise ValueError("a Gauss-Seidel smoother needs the own | ghost layout on every partitioned level: depth / finest_depth must be None / 0")
+            if not isinstance(gs.ordering, str):
+                raise ValueError("a given ordering is per level and per rank: pass gs_orders=[order of level 0, order of level 1, ...]")
+            if gs_orders is not None:
+                if len(gs_orders) > nlevels - 1:
+                    raise ValueError("gs_orders: one entry per smoothed level at the most")
+                gs_orders = [None if o is None else GaussSeidelSmoother._check_ordering(o) for o in gs_orders]
+                if any(isinstance(o, str) for o in gs_orders):
+                    raise ValueError("gs_orders: every entry is None or a 1-D integer array")
+        elif gs_orders is not None or not isinstance(smoother, str):
+            raise ValueError('smoother must be "jacobi", "patch" or a GaussSeidelSmoother (gs_orders goes with the latter)')
         lib = abi.load()
         self._lib, self.rank, self.world = lib, rank, world
         d = len(cells_per_rank)
@@ -154,7 +177,7 @@ class DistributedGMG:
         # (an anisotropic mesh would change the iteration count with the rank grid)
         self.lengths = lengths
         self.local = local_hierarchy or pa.build_local_hierarchy(self.cells_global, nlevels, self.grid, rank, order, lengths, rep_from,
-                                                                  depth, smoother, finest_depth=finest_depth, sub_from=sub_from,
+                                                                  depth, "jacobi" if gs is not None else smoother, finest_depth=finest_depth, sub_from=sub_from,
                                                                   sub_ranks=sub_ranks)
         self.t_assembly = time.perf_counter() - t0
         self.order = order
@@ -192,6 +215,11 @@ class DistributedGMG:
                                                     C.cast(self._host.allreduce_cb, C.c_void_p), None))
             else:
                 raise ValueError("transport must be 'rccl', 'host', 'alone', 'rccl_loopback' or 'host_loopback'")
+        if loopback_rows is not None:
+            if transport not in ("rccl_loopback", "host_loopback"):
+                raise ValueError("loopback_rows goes with the loopback transports")
+            rows = np.ascontiguousarray(loopback_rows, dtype=np.int64)
+            abi.check(h, lib.gmg_comm_set_loopback_rows(h, C.c_void_p(rows.ctypes.data), rows.size))
         levels = self.local["levels"]
         for l, L in enumerate(levels):
             if L is None:                                     # a level of a rank subset this rank is not part of
@@ -232,7 +260,15 @@ class DistributedGMG:
                 else:
                     self._set(lib.gmg_set_prolongation, l, L.P)
                     self._set(lib.gmg_set_restriction, l, L.R)
-                if smoother == "patch":
+                if gs is not None:
+                    abi.check(h, lib.gmg_set_smoother_gauss_seidel(h, l, abi.PRE_AND_POST, gs.niter, gs.omega, GaussSeidelSmoother._TYPES[gs.type]))
+                    o = gs_orders[l] if gs_orders is not None and l < len(gs_orders) and gs_orders[l] is not None else gs.ordering
+                    if isinstance(o, str):
+                        if o != "natural":
+                            abi.check(h, lib.gmg_set_gs_ordering(h, l, GaussSeidelSmoother._ORDERINGS[o], None, 0))
+                    else:
+                        abi.check(h, lib.gmg_set_gs_ordering(h, l, abi.GS_ORDER_GIVEN, C.c_void_p(o.ctypes.data), o.size))
+                elif smoother == "patch":
                     self._set_patch_smoother(l, L, niter, omega)
                 else:
                     abi.check(h, lib.gmg_set_smoother_jacobi(h, l, abi.PRE_AND_POST, niter, omega))
@@ -250,8 +286,9 @@ class DistributedGMG:
             # transfer exchanges the halo geometry makes unnecessary (consistent!(r) before the restriction, consistent!(dxh) before r -= A dxh)
             # (the library is told the geometry -- layers, layers per sweep, reach of R -- and derives the first skip per pass itself;
             # overlap_hints() is the same rule evaluated here for this niter: what the bench line reports)
-            self.overlap_hints = pa.overlap_hints(self.local, niter, smoother)
-            for l, (lay, per, rr, sd) in enumerate(pa.overlap_geometry(self.local, smoother)):
+            geom_smoother = "jacobi" if gs is not None else smoother   # (a Gauss-Seidel hierarchy has no overlapping level: no hints)
+            self.overlap_hints = pa.overlap_hints(self.local, niter, geom_smoother)
+            for l, (lay, per, rr, sd) in enumerate(pa.overlap_geometry(self.local, geom_smoother)):
                 if lay > 0 and not int(os.environ.get("GMG_NO_OVERLAP_HINTS", "0")):
                     abi.check(h, lib.gmg_set_partition_overlap_hints(h, l, lay, per, rr, int(sd)))
         sub = self.local.get("sub") if world > 1 else None
@@ -455,6 +492,21 @@ class DistributedGMG:
         buf = C.create_string_buffer(256)
         abi.check(self.h, self._lib.gmg_sweep_signature(self.h, lev, buf, 256))
         return buf.value.decode()
+
+    def gs_schedule(self, level=0, forward=True):
+        """gmg_get_gs_schedule: what the setup of the level's Gauss-Seidel smoother built for one direction, on a partitioned level the
+        schedule of this rank's own x own block -> dict(nsets, max_set_rows, nlaunches, nwide)"""
+        v = [C.c_int64(0) for _ in range(4)]
+        abi.check(self.h, self._lib.gmg_get_gs_schedule(self.h, level, 0 if forward else 1, *[C.byref(q) for q in v]))
+        return dict(zip(("nsets", "max_set_rows", "nlaunches", "nwide"), (q.value for q in v)))
+
+    def gs_ordering(self, level=0):
+        """gmg_get_gs_ordering -> dict(kind, ncolors, order): the visiting order of this rank's own block of the level"""
+        L = self.local["levels"][level]
+        kind, nc = C.c_int(0), C.c_int64(0)
+        order = np.empty(L.n_own, dtype=np.int32)
+        abi.check(self.h, self._lib.gmg_get_gs_ordering(self.h, level, C.byref(kind), C.byref(nc), C.c_void_p(order.ctypes.data), order.size))
+        return dict(kind=("natural", "multicolor", "given")[kind.value], ncolors=nc.value, order=order)
 
     def comm_info(self):
         """what the handle communicates through (gmg_get_comm_info): transport, rank, ranks, ncclCommCount, HIP device"""

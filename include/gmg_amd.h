@@ -180,8 +180,19 @@ GMG_API int gmg_set_smoother_patch_matrices(gmg_handle_t h, int lev, int which, 
  * workgroup.  A missing or zero diagonal entry: GMG_ERR_SINGULAR at gmg_setup (SingularException, :31-33).  gmg_update_values +
  * gmg_setup keep the schedule and refill the values where the level's layout refreshes in place (any other path is a full setup
  * that rebuilds them; the results are the same bits).  gmg_smooth is solve!; gmg_precond_apply is ldiv!, :210-214 (x = 0, a copy
- * of r, all niter iterations).  Single GPU: GMG_ERR_UNSUPPORTED at gmg_setup on a communicator of more than one rank (real or
- * loopback).  gmg_model_bytes is not extended: on a handle with such a smoother its byte model still counts Jacobi sweeps.
+ * of r, all niter iterations).
+ * Several ranks (a communicator of more than one rank, real or loopback): RANK-BLOCK Gauss-Seidel, the reference's distributed form
+ * (:155-165, :71-75, :93-97: DiagonalIndices of the local matrix over the owned indices, forward_sub! / backward_sub! on
+ * own_values(x), mul!(Adx, A, dx) the distributed product).  On an own | ghost level (gmg_set_partition; also the levels of a
+ * redistributed subset on its member ranks) level sets, colouring, given order and tables are those of the rank's OWN x OWN BLOCK --
+ * rows [0, n_own), stored columns < n_own -- the triangular solves need no communication, and r -= A dx exchanges dx and applies
+ * the ghost columns; the diagonal test applies to the owned rows, a given order has n_own entries, gmg_get_gs_schedule /
+ * gmg_get_gs_ordering report the own-block schedule.  With one rank per block the sweep is the one-rank sweep; with more it is
+ * another (weaker) smoother, by construction.  A replicated level (gmg_set_replication) sweeps its global matrix on every rank.
+ * The overlapping layout (gmg_set_partition_overlap) is refused: GMG_ERR_UNSUPPORTED at gmg_setup, naming level and layout.
+ * On an own | ghost level whose pack can fuse (every sent row is a boundary row: pack_fused of gmg_get_halo_info) the update launch
+ * dx = omega dx ; x += dx also fills the send buffer of dx's exchange (gs_update_pack_kernel; option gs_pack_fused, same bits).
+ * gmg_model_bytes is not extended: on a handle with such a smoother its byte model still counts Jacobi sweeps.
  * gmg_sweep_signature of a level with such a smoother ends in " gs=F+B", " gs=F" or " gs=B" (the directions that have tables). */
 enum gmg_gs_type { GMG_GS_SYMMETRIC = 0, GMG_GS_FORWARD = 1, GMG_GS_BACKWARD = 2 };
 GMG_API int gmg_set_smoother_gauss_seidel(gmg_handle_t h, int lev, int which, int niter, double omega, int type);
@@ -337,6 +348,10 @@ GMG_API int gmg_set_options(gmg_handle_t h, int mode, int cycle, int maxiter, do
  *   Gauss-Seidel     gs_wide* (1: on a level with a visiting order of its own (gmg_set_gs_ordering) the one-set launches run
  *                    gs_wide_kernel and fold the x update where they may; 0: they run gs_sets_kernel with the update launch, as the
  *                    natural order does.  Same bits either way: the A/B switch of tools/gs_timing.py)
+ *                    gs_pack_fused* (1: on an own | ghost level whose pack can fuse, the x update of a Gauss-Seidel direction and the
+ *                    pack of dx's send entries are one launch, gs_update_pack_kernel; 0: gs_update_kernel, then halo_pack_kernel.
+ *                    Inert where the update folds into gs_wide_kernel or the pack cannot fuse.  Same bits either way: the A/B
+ *                    switch of tools/gs_dist_timing.py)
  *   coarsest level   coarse_host_max (1500) coarse_host_fallback_max (6000) coarse_auto_cg_min (20000: a dense-inverse request on a
  *                    coarsest level of at least this many dofs is served by the device CG-Jacobi solver instead) gj_mfma (1) gj_wide_min (4096)
  *   patch smoother   patch_dedup (1) patch_source_dedup (1) patch_operator (1)
@@ -531,6 +546,16 @@ GMG_API int gmg_comm_latency_probe(gmg_handle_t h, int nmsg, int64_t count, int 
  * receive), so pack -> ncclGroupStart/Send/Recv/GroupEnd on the communication stream -> event -> boundary fix-up -> ncclAllReduce
  * run exactly as on `virtual_nranks` GPUs, on the one that exists.  partition.fold_ranks() builds such a partition. */
 GMG_API int gmg_comm_set_loopback(gmg_handle_t h, int virtual_nranks);
+/* Optional, after gmg_comm_set_loopback: own_rows[q] = owned rows of virtual rank q on the Krylov level (their sum = the folded
+ * level's owned rows).  Without it a dot product or norm of the folded handle is ONE reduction over the stacked rows, which differs
+ * in the last bits from the sum of the ranks' reductions that `virtual_nranks` true ranks all-reduce.  With it the reductions of
+ * gmg_dot / gmg_norm, of gmg_apply's history and of gmg_cg_solve (every dot, and the update with its partial ||r||^2) run per virtual
+ * rank -- the same kernels on the same row counts; every rank but the last must own an even number of rows (GMG_ERR_UNSUPPORTED
+ * otherwise: its successor's part of a folded vector would lose the 16-byte alignment a rank's own vector has) -- and the
+ * sums are added in rank order before the all-reduce and the square root: the folded CG run then reproduces the scalars, and so x and
+ * the history, of the true-rank run bit for bit (tested with two ranks).  The other Krylov drivers reduce their first stages in
+ * kernels of their own and keep the single reduction.  own_rows = NULL switches it off.  Takes effect at once (no gmg_setup). */
+GMG_API int gmg_comm_set_loopback_rows(gmg_handle_t h, const int64_t *own_rows, int virtual_nranks);
 /* Host-staged transport through callbacks of the host language (MPI in Julia, gloo in the
  * Python tests); lets several ranks share one GPU.  Functional, not fast. */
 GMG_API int gmg_comm_init_host(gmg_handle_t h, int rank, int nranks, gmg_host_exchange_fn exchange,
