@@ -78,6 +78,9 @@ SYMBOLS = {
     "gmg_set_smoother_gauss_seidel": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int],
     "gmg_get_gs_schedule": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                             C.POINTER(C.c_int64)],
+    "gmg_set_smoother_chebyshev": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double],
+    "gmg_get_chebyshev_info": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                               C.POINTER(C.c_double), C.POINTER(C.c_int)],
     "gmg_set_gs_ordering": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64],
     "gmg_get_gs_ordering": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.c_void_p, C.c_int64],
     "gmg_gs_multicolor_order": [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)],

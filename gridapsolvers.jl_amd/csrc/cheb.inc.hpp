@@ -1,0 +1,273 @@
+// cheb.inc.hpp -- ChebyshevSmoother(M, degree) over the preconditioner M of a smoother slot, M in {JacobiLinearSolver, PatchSolver,
+// BlockJacobiSolver} (included at the end of gmg_amd.hip).  The reference has no such smoother: like the Gauss-Seidel orderings it is an
+// addition of the device library next to the reference's types, on one GPU.
+//
+// One pass of degree m on (x, r) is Saad, Iterative Methods, Alg. 12.1 in the residual form of the smoothers here, with
+// z = M^-1 r the un-relaxed preconditioner of the slot (what gmg_precond_apply returns):
+//
+//   theta = (lmax + lmin)/2   delta = (lmax - lmin)/2   sigma = theta/delta   rho_0 = 1/sigma
+//   sweep 0:            d = (1/theta) z                                  ; x += d ; r -= A d
+//   sweep k = 1..m-1:   rho_k = 1/(2 sigma - rho_{k-1})
+//                       d = (rho_k rho_{k-1}) d + (2 rho_k/delta) z      ; x += d ; r -= A d
+//
+// The 2m - 1 coefficients are computed on the host in double in exactly this order, once per setup (cheb_coefficients), and reach the
+// kernels as arguments.  In the kernels every product is rounded, then the sum (__dmul_rn / __dadd_rn; the library is built with
+// -ffp-contract=off anyway), so a*d + b*z in numpy is the same arithmetic.  Sweep 0 never reads d -- L.dx, which holds whatever the
+// prolongation or the pass before left there -- and writes x = d where the pass starts from x = 0.
+//
+// SPECTRUM BOUNDS.  Given lambda_max: used as it is, with lambda_min (default lambda_max / eig_ratio).  Otherwise gmg_setup estimates
+// lambda_max(M^-1 A) per smoothed level and slot (pre and post share the estimate when they share M) by eig_steps power steps from the
+// start vector v_i = 1 + ((i * 2654435761) mod 1024)/1024 (0-based row i, unsigned 64-bit), normalised: w = M^-1 (A v) ;
+// lambda_est = ||w||_2 ; v = w/lambda_est -- the level's mat-vec, the slot's preconditioner and the dot kernel, nothing new.  Then
+// lambda_max = eig_safety lambda_est, lambda_min = lambda_max/eig_ratio (PETSc's interval convention).  KNOWN WEAKNESS: a few power
+// steps under-estimate a clustered top of the spectrum (Jacobi on Q1 32^3: 1.336 after 10 steps against 1.494, so 1.1 lambda_est is
+// still below lambda_max); pass lambda_max or raise eig_steps where that matters.  A value refresh (gmg_update_values + gmg_setup)
+// estimates again.
+//
+// KERNELS (all HBM-bound streaming):
+//   cheb_update_kernel<FIRST, DINV>   the pointwise update d = [a d +] b z ; x (+)= d with z = dinv .* r (Jacobi M, DINV) or z as it
+//                                     is (patch M in operator form, after spmv_set(S.M, r, z)).  16-byte accesses where every pointer
+//                                     is 16-byte aligned, a scalar tail for an odd n, scalar throughout otherwise.
+//   patch_gather[_sell]_cheb_kernel   (kernels.hpp) patch M in the contribution-buffer forms: the update rides in the gather's epilogue.
+// Each sweep is followed by the level's apply_A_sub (r -= A d).  d lives in L.dx, z of the operator form in the level's residual
+// buffer the pass does not use: no new device buffer.
+//
+// REFUSED: Gauss-Seidel slots (GMG_ERR_UNSUPPORTED at gmg_set_smoother_chebyshev), handles with a communicator (GMG_ERR_UNSUPPORTED at
+// gmg_setup).  The pass-level shortcuts of the Richardson-Jacobi passes (fold_level, emits_s0, smooth_persistent, r_dead) do not apply.
+
+namespace {
+
+typedef double cheb_d2 __attribute__((ext_vector_type(2)));
+
+template <bool FIRST, bool DINV>
+__device__ __forceinline__ double cheb_step(double a, double b, double dinv, double z, double d)
+{
+  if (DINV) z = __dmul_rn(dinv, z);
+  const double t = __dmul_rn(b, z);
+  return FIRST ? t : __dadd_rn(__dmul_rn(a, d), t);
+}
+
+// vec != 0: dinv, z, d, x are all 16-byte aligned -- pairs of rows per lane, then the odd last row
+template <bool FIRST, bool DINV>
+__global__ void cheb_update_kernel(int64_t n, double a, double b, const double *__restrict__ dinv, const double *__restrict__ z,
+                                   double *__restrict__ d, double *__restrict__ x, int x_zero, int vec)
+{
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+  int64_t done = 0;
+  if (vec) {
+    const int64_t n2 = n >> 1;
+    const cheb_d2 *z2 = reinterpret_cast<const cheb_d2 *>(z), *q2 = reinterpret_cast<const cheb_d2 *>(dinv);
+    cheb_d2 *d2 = reinterpret_cast<cheb_d2 *>(d), *x2 = reinterpret_cast<cheb_d2 *>(x);
+    for (int64_t i = tid; i < n2; i += nth) {
+      const cheb_d2 zz = z2[i];
+      cheb_d2 qq = {1.0, 1.0}, dd = {0.0, 0.0};
+      if (DINV) qq = q2[i];
+      if (!FIRST) dd = d2[i];
+      cheb_d2 out;
+      out.x = cheb_step<FIRST, DINV>(a, b, qq.x, zz.x, dd.x);
+      out.y = cheb_step<FIRST, DINV>(a, b, qq.y, zz.y, dd.y);
+      d2[i] = out;
+      if (x_zero) x2[i] = out;
+      else {
+        cheb_d2 xx = x2[i];
+        xx.x = __dadd_rn(xx.x, out.x);
+        xx.y = __dadd_rn(xx.y, out.y);
+        x2[i] = xx;
+      }
+    }
+    done = n2 * 2;
+  }
+  for (int64_t i = done + tid; i < n; i += nth) {
+    const double out = cheb_step<FIRST, DINV>(a, b, DINV ? dinv[i] : 1.0, z[i], FIRST ? 0.0 : d[i]);
+    d[i] = out;
+    x[i] = x_zero ? out : __dadd_rn(x[i], out);
+  }
+}
+
+// start vector of the power iteration (not yet normalised)
+__global__ void cheb_start_kernel(int64_t n, double *__restrict__ v)
+{
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    v[i] = 1.0 + (double)(((uint64_t)i * 2654435761ull) % 1024ull) / 1024.0;
+}
+
+// v = w / s (v may be w)
+__global__ void cheb_div_kernel(int64_t n, const double *w, double s, double *v)
+{
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) v[i] = w[i] / s;
+}
+
+// the 2m - 1 coefficients, in the order of the header comment: b[0] = 1/theta ; a[k] = rho_k rho_{k-1}, b[k] = 2 rho_k / delta
+void cheb_coefficients(int m, double lmin, double lmax, std::vector<double> &a, std::vector<double> &b)
+{
+  a.assign((size_t)m, 0.0); b.assign((size_t)m, 0.0);
+  const double theta = (lmax + lmin) / 2.0, delta = (lmax - lmin) / 2.0, sigma = theta / delta;
+  double rho = 1.0 / sigma;
+  b[0] = 1.0 / theta;
+  for (int k = 1; k < m; ++k) {
+    const double rho_k = 1.0 / (2.0 * sigma - rho);
+    a[(size_t)k] = rho_k * rho;
+    b[(size_t)k] = (2.0 * rho_k) / delta;
+    rho = rho_k;
+  }
+}
+
+bool cheb_same_M(const Smoother &p, const Smoother &q)
+{
+  if (p.kind != q.kind) return false;
+  if (p.kind == SM_JACOBI) return true;
+  return p.kind == SM_PATCH && p.tab && p.tab == q.tab && p.patch_kind == q.patch_kind;
+}
+
+} // namespace
+
+// z = M^-1 r, the un-relaxed preconditioner of the slot
+void gmg_solver::cheb_precond(Level &L, Smoother &S, const double *r, double *z)
+{
+  if (S.kind == SM_JACOBI) {
+    hipLaunchKernelGGL(jacobi_apply_kernel, dim3(grid_for(L.n)), dim3(256), 0, stream, L.n, L.dinv, r, z);
+    HIP_CHECK(hipGetLastError());
+  } else
+    patch_precond(L, S, r, 1.0, false, z, nullptr);
+}
+
+// spectrum bounds (given, or from the power iteration) and the coefficients of the slot.  same_M: the level's other slot, already set up
+void gmg_solver::cheb_setup(int l, Smoother &S, const Smoother *same_M)
+{
+  Level &L = lev[l];
+  const std::string where = "Chebyshev smoother on level " + std::to_string(l) + ": ";
+  REQUIRE(S.kind == SM_JACOBI || S.kind == SM_PATCH, GMG_ERR_UNSUPPORTED, where + "M must be a Jacobi or a patch solver");
+  if (S.cheb_lmax_in > 0.0) {
+    S.cheb_lest = NAN;
+    S.cheb_lmax = S.cheb_lmax_in;
+  } else {
+    if (same_M && same_M->cheb && !(same_M->cheb_lmax_in > 0.0) && same_M->cheb_eig_steps == S.cheb_eig_steps && cheb_same_M(*same_M, S))
+      S.cheb_lest = same_M->cheb_lest;
+    else {
+      // v, A v and M^-1 A v in the level's work vectors (nothing of a solve is alive during setup)
+      const int64_t n = L.n;
+      double *v = L.rbuf[0], *t = L.rbuf[1], *w = L.dx;
+      hipLaunchKernelGGL(cheb_start_kernel, dim3(grid_for(n)), dim3(256), 0, stream, n, v);
+      HIP_CHECK(hipGetLastError());
+      double lam = norm(n, v);
+      for (int s = 0; s <= S.cheb_eig_steps; ++s) {
+        REQUIRE(std::isfinite(lam) && lam > 0.0, GMG_ERR_SINGULAR, where + "the power iteration on M^-1 A broke down (norm " + std::to_string(lam) + ")");
+        if (s == S.cheb_eig_steps) break;
+        hipLaunchKernelGGL(cheb_div_kernel, dim3(grid_for(n)), dim3(256), 0, stream, n, s == 0 ? v : w, lam, v);   // (s == 0: the start vector, normalised)
+        HIP_CHECK(hipGetLastError());
+        apply_A_set(l, v, t);
+        cheb_precond(L, S, t, w);
+        lam = norm(n, w);
+      }
+      S.cheb_lest = lam;
+    }
+    S.cheb_lmax = S.cheb_eig_safety * S.cheb_lest;
+  }
+  S.cheb_lmin = S.cheb_lmin_in > 0.0 ? S.cheb_lmin_in : S.cheb_lmax / S.cheb_eig_ratio;
+  REQUIRE(S.cheb_lmin > 0.0 && S.cheb_lmin < S.cheb_lmax, GMG_ERR_INVALID, where + "the bounds must satisfy 0 < lambda_min < lambda_max (" +
+          std::to_string(S.cheb_lmin) + ", " + std::to_string(S.cheb_lmax) + ")");
+  cheb_coefficients(S.cheb_degree, S.cheb_lmin, S.cheb_lmax, S.cheb_a, S.cheb_b);
+}
+
+// one pass of degree m on (x, r), r in place in one of the level's residual buffers (returned)
+double *gmg_solver::cheb_pass(int l, Smoother &S, double *x, const double *r_in, bool x_zero)
+{
+  Level &L = lev[l];
+  const int64_t n = L.n;
+  REQUIRE((int)S.cheb_b.size() == S.cheb_degree && S.cheb_degree >= 1, GMG_ERR_STATE, "Chebyshev smoother: no coefficients (gmg_setup first)");
+  double *r = nullptr;
+  if (r_in == L.rbuf[0] || r_in == L.rbuf[1]) r = const_cast<double *>(r_in);
+  else { r = L.rbuf[0]; copy(r, r_in, n); }
+  double *d = L.dx;
+  double *zbuf = (r == L.rbuf[0]) ? L.rbuf[1] : L.rbuf[0];   // z = M r of the operator form: the residual buffer this pass does not use
+  const bool contrib_form = S.kind == SM_PATCH && !S.use_M;
+  const auto aligned16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+  for (int k = 0; k < S.cheb_degree; ++k) {
+    const bool first = k == 0;
+    const double a = S.cheb_a[(size_t)k], b = S.cheb_b[(size_t)k];
+    const int xz = (x_zero && first) ? 1 : 0;
+    if (contrib_form) {
+      patch_contrib(S, r);
+      const int grid = (int)std::max<int64_t>(1, (n + 255) / 256);
+      if (S.d_isoff) {
+        if (first) hipLaunchKernelGGL((patch_gather_sell_cheb_kernel<true>), dim3(grid), dim3(256), 0, stream, n, S.d_isoff, S.d_isinc, S.d_contrib, a, b, xz, d, x);
+        else hipLaunchKernelGGL((patch_gather_sell_cheb_kernel<false>), dim3(grid), dim3(256), 0, stream, n, S.d_isoff, S.d_isinc, S.d_contrib, a, b, xz, d, x);
+      } else {
+        if (first) hipLaunchKernelGGL((patch_gather_cheb_kernel<true>), dim3(grid), dim3(256), 0, stream, n, S.d_iptr, S.d_inc, S.d_contrib, a, b, xz, d, x);
+        else hipLaunchKernelGGL((patch_gather_cheb_kernel<false>), dim3(grid), dim3(256), 0, stream, n, S.d_iptr, S.d_inc, S.d_contrib, a, b, xz, d, x);
+      }
+    } else if (S.kind == SM_PATCH) {
+      spmv_set(S.M, r, zbuf);
+      const int vec = (aligned16(zbuf) && aligned16(d) && aligned16(x)) ? 1 : 0;
+      const int grid = grid_for(vec ? (n + 1) / 2 : n);
+      if (first) hipLaunchKernelGGL((cheb_update_kernel<true, false>), dim3(grid), dim3(256), 0, stream, n, a, b, (const double *)nullptr, zbuf, d, x, xz, vec);
+      else hipLaunchKernelGGL((cheb_update_kernel<false, false>), dim3(grid), dim3(256), 0, stream, n, a, b, (const double *)nullptr, zbuf, d, x, xz, vec);
+    } else {
+      const int vec = (aligned16(L.dinv) && aligned16(r) && aligned16(d) && aligned16(x)) ? 1 : 0;
+      const int grid = grid_for(vec ? (n + 1) / 2 : n);
+      if (first) hipLaunchKernelGGL((cheb_update_kernel<true, true>), dim3(grid), dim3(256), 0, stream, n, a, b, L.dinv, r, d, x, xz, vec);
+      else hipLaunchKernelGGL((cheb_update_kernel<false, true>), dim3(grid), dim3(256), 0, stream, n, a, b, L.dinv, r, d, x, xz, vec);
+    }
+    HIP_CHECK(hipGetLastError());
+    apply_A_sub(l, d, r);
+  }
+  return r;
+}
+
+extern "C" {
+
+int gmg_set_smoother_chebyshev(gmg_handle_t h, int lev, int which, int degree, double lambda_min, double lambda_max, int eig_steps,
+                               double eig_ratio, double eig_safety)
+{
+  return guarded(h, [&] {
+    check_level(h, lev, true);
+    REQUIRE(which == GMG_PRE || which == GMG_POST || which == GMG_PRE_AND_POST, GMG_ERR_INVALID, "bad `which`");
+    REQUIRE(degree >= 1, GMG_ERR_INVALID, "The degree must be a positive integer.");
+    REQUIRE(!(lambda_min > 0.0 && lambda_max > 0.0) || lambda_min < lambda_max, GMG_ERR_INVALID, "lambda_min must be smaller than lambda_max.");
+    REQUIRE(eig_ratio > 1.0, GMG_ERR_INVALID, "eig_ratio must be greater than 1.");
+    REQUIRE(eig_safety >= 1.0, GMG_ERR_INVALID, "eig_safety must be at least 1.");
+    REQUIRE(eig_steps >= 1, GMG_ERR_INVALID, "eig_steps must be a positive integer.");
+    REQUIRE(!std::isnan(lambda_min) && !std::isnan(lambda_max), GMG_ERR_INVALID, "lambda_min / lambda_max must not be NaN.");
+    Level &L = h->lev[lev];
+    const bool on_pre = which != GMG_POST, on_post = which != GMG_PRE;
+    // the slot as gmg_setup will see it: a post-smoother that shares the pre-smoother is the pre-smoother's slot
+    const Smoother &P = L.pre, &Q = L.post_shares_pre ? L.pre : L.post;
+    for (const Smoother *sp : {on_pre ? &P : nullptr, on_post ? &Q : nullptr}) {
+      if (!sp) continue;
+      REQUIRE(sp->assigned, GMG_ERR_STATE, "gmg_set_smoother_chebyshev: the slot has no smoother yet (gmg_set_smoother_jacobi / gmg_set_smoother_patch first)");
+      REQUIRE(sp->kind != SM_GAUSS_SEIDEL, GMG_ERR_UNSUPPORTED, "gmg_set_smoother_chebyshev: M must be a Jacobi or a patch solver, the slot holds a Gauss-Seidel smoother");
+    }
+    // a slot of its own for the side that is changed alone
+    if (which != GMG_PRE_AND_POST && L.post_shares_pre) { L.post = L.pre; L.post_shares_pre = false; }
+    for (Smoother *sp : {on_pre ? &L.pre : nullptr, (on_post && !L.post_shares_pre) ? &L.post : nullptr}) {
+      if (!sp) continue;
+      sp->cheb = true;
+      sp->cheb_degree = degree; sp->cheb_eig_steps = eig_steps;
+      sp->cheb_lmin_in = lambda_min > 0.0 ? lambda_min : 0.0;
+      sp->cheb_lmax_in = lambda_max > 0.0 ? lambda_max : 0.0;
+      sp->cheb_eig_ratio = eig_ratio; sp->cheb_eig_safety = eig_safety;
+      sp->cheb_a.clear(); sp->cheb_b.clear();
+    }
+    L.clear_overlap_hints();
+    h->touch();
+  });
+}
+
+int gmg_get_chebyshev_info(gmg_handle_t h, int lev, int which, int *degree, double *lambda_est, double *lambda_min, double *lambda_max,
+                           int *eig_steps)
+{
+  return guarded(h, [&] {
+    check_ready(h);
+    check_level(h, lev, true);
+    REQUIRE(which == GMG_PRE || which == GMG_POST, GMG_ERR_INVALID, "which must be GMG_PRE or GMG_POST");
+    const Smoother &S = which == GMG_PRE ? h->lev[lev].pre : h->lev[lev].post;
+    REQUIRE(S.cheb, GMG_ERR_STATE, "this slot has no Chebyshev smoother");
+    if (degree) *degree = S.cheb_degree;
+    if (lambda_est) *lambda_est = S.cheb_lest;
+    if (lambda_min) *lambda_min = S.cheb_lmin;
+    if (lambda_max) *lambda_max = S.cheb_lmax;
+    if (eig_steps) *eig_steps = S.cheb_eig_steps;
+  });
+}
+
+} // extern "C"

@@ -396,6 +396,14 @@ struct Smoother {
   DevCSR M;
   std::vector<int32_t> h_ublock;   // host copies of the de-duplication result (setup only)
   std::vector<int64_t> h_uboff;
+  bool assigned = false;           // a gmg_set_smoother_* call filled this slot (gmg_set_smoother_chebyshev needs one)
+  // ChebyshevSmoother over this slot's M (cheb.inc.hpp): the pass is the Chebyshev recurrence instead of niter Richardson sweeps;
+  // niter and omega are unused.  *_in: what gmg_set_smoother_chebyshev was given (<= 0: estimate / derive); the rest is filled by setup.
+  bool cheb = false;
+  int cheb_degree = 0, cheb_eig_steps = 0;
+  double cheb_lmin_in = 0.0, cheb_lmax_in = 0.0, cheb_eig_ratio = 0.0, cheb_eig_safety = 0.0;
+  double cheb_lest = 0.0, cheb_lmin = 0.0, cheb_lmax = 0.0;
+  std::vector<double> cheb_a, cheb_b;   // sweep k: d = cheb_a[k] d + cheb_b[k] z (cheb_a[0] unused: sweep 0 does not read d)
   // every device array above was freed with the handle's allocations
   void reset_device()
   {
@@ -3119,7 +3127,7 @@ struct gmg_solver {
   }
   bool emits_s0(const Level &L, const Smoother &S, const DevCSR &producer)
   {
-    if (!(pat_emit && comm.nranks == 1 && producer.pat && S.kind == SM_JACOBI && one_gather() && S.niter > 0 && L.sbuf[0] != nullptr && L.dinv != nullptr)) return false;
+    if (!(pat_emit && comm.nranks == 1 && producer.pat && S.kind == SM_JACOBI && !S.cheb && one_gather() && S.niter > 0 && L.sbuf[0] != nullptr && L.dinv != nullptr)) return false;
     // levels whose sweeps gather r itself have no use for s_0 -- unless the pass runs as one launch (small levels), which starts from it
     const int l = (int)(&L - &lev[0]);
     if (rsweep_level(L) && !smooth_persistent(l, S, nullptr, nullptr, nullptr, false, S.niter, true)) return false;
@@ -3210,12 +3218,17 @@ struct gmg_solver {
   void build_gs(int l, bool values_only = false);
   void gs_solve(Level &L, int dir, const double *r, double *dx, int xmode = 0, double *x = nullptr);
   void gs_pass(int l, Smoother &S, double *x, double *r, bool x_zero);
+  // Chebyshev smoother (cheb.inc.hpp)
+  void cheb_precond(Level &L, Smoother &S, const double *r, double *z);
+  void cheb_setup(int l, Smoother &S, const Smoother *same_M);
+  double *cheb_pass(int l, Smoother &S, double *x, const double *r_in, bool x_zero);
+  void patch_contrib(Smoother &S, const double *r);
 
   // May the transfer T in front of the pass S of level l run as that pass's head?  One rank, a Jacobi pass that runs as one launch
   // with T's table next to its own in LDS (T in the per-lane pattern form, its table in the LDS form).
   bool fold_level(int l, const Smoother &S, const DevCSR &T)
   {
-    if (!persist_fold || comm.nranks != 1 || S.kind != SM_JACOBI || !one_gather() || S.niter < 2) return false;
+    if (!persist_fold || comm.nranks != 1 || S.kind != SM_JACOBI || S.cheb || !one_gather() || S.niter < 2) return false;
     return smooth_persistent(l, S, nullptr, nullptr, nullptr, false, S.niter, true, false, 1, &T, nullptr);
   }
   // One launch for the whole pass on small single-GPU levels in the shared-offset pattern form (see sells_smooth_kernel).
@@ -3230,7 +3243,7 @@ struct gmg_solver {
     Level &L = lev[l];
     const DevCSR &M = L.A;
     // replicated levels have no halo; levels in the overlapping layout run the sweeps between two exchanges like a single-GPU level
-    if (!persist || (comm.nranks > 1 && L.halo.present && !L.halo.ovl) || niter < 2) return false;
+    if (!persist || S.cheb || (comm.nranks > 1 && L.halo.present && !L.halo.ovl) || niter < 2) return false;   // (a Chebyshev slot sweeps launch by launch)
     if (!(M.sell && M.pat && M.pat_shared && !M.pat_coded && M.pat_k == 3 && M.pat_nruns % 3 == 0)) return false;
     const int nu = M.pat_k * M.pat_nruns;
     const size_t lds_own = (size_t)M.pat_np * nu * 16 + (size_t)M.pat_np * 8 + 16;
@@ -3443,6 +3456,9 @@ struct gmg_solver {
     L.fold_pending = 0; L.fold_src = nullptr;
     const DevCSR *fold_T = fold == 1 ? &lev[l - 1].R : fold == 2 ? &L.P : nullptr;
     REQUIRE(!fold || (S.kind == SM_JACOBI && one_gather() && r_internal && fold_level(l, S, *fold_T)), GMG_ERR_STATE, "a folded transfer met a pass that does not run as one launch");
+    // ChebyshevSmoother over the slot's M: its own recurrence, r in place (cheb.inc.hpp).  No pass-level shortcut applies: r_dead is not
+    // acted on, and fold_level / emits_s0 / smooth_persistent answer "no" for such a slot.
+    if (S.cheb) return cheb_pass(l, S, x, r_in, x_zero);
     if (S.niter <= 0) {
       if (x_zero) zero(x, n);
       if (!r_internal) { copy(L.rbuf[0], r_in, n); return L.rbuf[0]; }
@@ -5637,21 +5653,9 @@ void gmg_solver::build_patch_operator(Level &L, Smoother &S)
                  sig_rep.size(), (long long)P.nnz, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
 }
 
-// dx = (omega *) sum_p scatter(inv(A_pp) r_p) ; relax: x += dx
-void gmg_solver::patch_precond(Level &L, Smoother &S, const double *r, double omega, bool relax, double *dx, double *x)
+// contrib = inv(A_pp) r_p of every patch (the contribution-buffer forms)
+void gmg_solver::patch_contrib(Smoother &S, const double *r)
 {
-  if (S.use_M) {
-    // dx = sum_p R_p^T inv(A_pp) R_p r as one pattern mat-vec; the relaxation dx .= omega .* dx ; x .+= dx
-    // (RichardsonSmoothers.jl:92-93) rides in its epilogue
-    if (relax && omega != 0.0) spmv_addto(S.M, r, dx, x, omega);
-    else {
-      spmv_set(S.M, r, dx);
-      if (relax) hipLaunchKernelGGL(relax_update_kernel, dim3(grid_for(L.n)), dim3(256), 0, stream, L.n, omega, dx, x);
-      else if (omega != 1.0) hipLaunchKernelGGL(scale_inplace_kernel, dim3(grid_for(L.n)), dim3(256), 0, stream, L.n, omega, dx);
-      HIP_CHECK(hipGetLastError());
-    }
-    return;
-  }
   if (S.npatch > 0) {
     if (S.dedup) {
       const int grid = (int)((S.npatch + kPatchChunk - 1) / kPatchChunk);
@@ -5667,6 +5671,24 @@ void gmg_solver::patch_precond(Level &L, Smoother &S, const double *r, double om
     }
     HIP_CHECK(hipGetLastError());
   }
+}
+
+// dx = (omega *) sum_p scatter(inv(A_pp) r_p) ; relax: x += dx
+void gmg_solver::patch_precond(Level &L, Smoother &S, const double *r, double omega, bool relax, double *dx, double *x)
+{
+  if (S.use_M) {
+    // dx = sum_p R_p^T inv(A_pp) R_p r as one pattern mat-vec; the relaxation dx .= omega .* dx ; x .+= dx
+    // (RichardsonSmoothers.jl:92-93) rides in its epilogue
+    if (relax && omega != 0.0) spmv_addto(S.M, r, dx, x, omega);
+    else {
+      spmv_set(S.M, r, dx);
+      if (relax) hipLaunchKernelGGL(relax_update_kernel, dim3(grid_for(L.n)), dim3(256), 0, stream, L.n, omega, dx, x);
+      else if (omega != 1.0) hipLaunchKernelGGL(scale_inplace_kernel, dim3(grid_for(L.n)), dim3(256), 0, stream, L.n, omega, dx);
+      HIP_CHECK(hipGetLastError());
+    }
+    return;
+  }
+  patch_contrib(S, r);
   // distributed level: the owned patches reach into ghost dofs.  consistent!(b) happened at the caller (see smooth()); here the
   // local contributions are gathered for ALL local dofs, the ghost ones are added to their owners (assemble!,
   // PatchSolvers.jl:251-258), then the relaxation runs on the owned entries.
@@ -5977,6 +5999,11 @@ void gmg_solver::setup()
     REQUIRE(!(comm.nranks > 1 && lev[l].halo.present && lev[l].halo.ovl) || (lev[l].pre.kind != SM_GAUSS_SEIDEL && lev[l].post.kind != SM_GAUSS_SEIDEL),
             GMG_ERR_UNSUPPORTED, "Gauss-Seidel smoother on level " + std::to_string(l) + ": the overlapping layout (gmg_set_partition_overlap) is not "
             "supported, rank-block sweeps need the own | ghost layout (gmg_set_partition)");
+  // Chebyshev slots run on one GPU only so far: the estimate and the passes know no halo
+  for (int l = 0; l < nlev - 1; ++l)
+    REQUIRE(comm.kind == COMM_NONE || !(lev[l].pre.cheb || (lev[l].post_shares_pre ? lev[l].pre : lev[l].post).cheb), GMG_ERR_UNSUPPORTED,
+            "Chebyshev smoother on level " + std::to_string(l) + ": handles with a communicator (gmg_comm_init_*) are not supported, the "
+            "Chebyshev smoother runs on one GPU only (partitioned levels are not implemented)");
   // patch smoothers / patch corrections with patches of more than 64 dofs take their blocks from the level's CSR (one thread block
   // per patch): a level kept in row-pattern form only gets its rows back
   for (int l = 0; l < nlev - 1; ++l) {
@@ -6225,8 +6252,12 @@ void gmg_solver::setup()
         L.ptmp = dvec(L.nvec); L.pcor = dvec(L.nvec);
       }
       if (L.pre.kind == SM_PATCH) build_patch(L, L.pre);
+      if (L.pre.cheb) cheb_setup(l, L.pre, nullptr);         // (spectrum bounds + coefficients; a shared post gets them with the copy)
       if (L.post_shares_pre) L.post = L.pre;
-      else if (L.post.kind == SM_PATCH) build_patch(L, L.post);
+      else {
+        if (L.post.kind == SM_PATCH) build_patch(L, L.post);
+        if (L.post.cheb) cheb_setup(l, L.post, &L.pre);
+      }
       if (L.pre.kind == SM_GAUSS_SEIDEL || L.post.kind == SM_GAUSS_SEIDEL) build_gs(l);
       drop_csr_stream(L.P);
       drop_csr_stream(L.R);
@@ -6383,8 +6414,12 @@ void gmg_solver::refresh_values()
       if (l < nlev - 1) {
         if (L.has_pcorr) build_patch(L, L.pcorr, true);
         if (L.pre.kind == SM_PATCH) build_patch(L, L.pre, true);
+        if (L.pre.cheb) cheb_setup(l, L.pre, nullptr);       // (an estimated bound is estimated again on the new values)
         if (L.post_shares_pre) L.post = L.pre;
-        else if (L.post.kind == SM_PATCH) build_patch(L, L.post, true);
+        else {
+          if (L.post.kind == SM_PATCH) build_patch(L, L.post, true);
+          if (L.post.cheb) cheb_setup(l, L.post, &L.pre);
+        }
         if (L.pre.kind == SM_GAUSS_SEIDEL || L.post.kind == SM_GAUSS_SEIDEL) build_gs(l, true);
       } else if (coarse_eff == GMG_COARSE_DENSE_INVERSE) {
         release(d_Ainv, (size_t)n * (size_t)n);
@@ -6985,10 +7020,11 @@ int gmg_set_restriction(gmg_handle_t h, int lev, int64_t nrows, int64_t ncols, i
   });
 }
 
-static void assign_smoother(gmg_handle_t h, int lev, int which, const Smoother &S)
+static void assign_smoother(gmg_handle_t h, int lev, int which, Smoother S)
 {
   Level &L = h->lev[lev];
   REQUIRE(which == GMG_PRE || which == GMG_POST || which == GMG_PRE_AND_POST, GMG_ERR_INVALID, "bad `which`");
+  S.assigned = true;                // (a plain smoother: S.cheb is false, a Chebyshev iteration the slot had is gone)
   if (which == GMG_PRE_AND_POST) { L.pre = S; L.post_shares_pre = true; }
   else if (which == GMG_PRE) { L.pre = S; if (L.post_shares_pre) { L.post_shares_pre = false; } }
   else { L.post = S; L.post_shares_pre = false; }
@@ -8179,6 +8215,12 @@ int gmg_sweep_signature(gmg_handle_t h, int lev, char *buf, int cap)
       const size_t len = std::strlen(buf);
       if (len + 1 < (size_t)cap) std::snprintf(buf + len, (size_t)cap - len, " gs=%s", gs_tag(h->lev[lev]));
     }
+    const Level &Lc = h->lev[lev];
+    if (lev < h->nlev - 1 && (Lc.pre.cheb || Lc.post.cheb)) {   // a level with a Chebyshev slot: the degrees (0: that slot has none)
+      const size_t len = std::strlen(buf);
+      if (len + 1 < (size_t)cap)
+        std::snprintf(buf + len, (size_t)cap - len, " cheb=%d/%d", Lc.pre.cheb ? Lc.pre.cheb_degree : 0, Lc.post.cheb ? Lc.post.cheb_degree : 0);
+    }
   });
 }
 
@@ -8264,3 +8306,4 @@ int gmg_device_bytes(gmg_handle_t h, int64_t *bytes)
 
 #include "block.inc.hpp"
 #include "gs.inc.hpp"
+#include "cheb.inc.hpp"

@@ -5330,4 +5330,52 @@ __global__ void patch_gather_sell_kernel(int64_t n, const int64_t *__restrict__ 
   dx[i] = s;
 }
 
+// The Chebyshev forms of the two gathers (ChebyshevSmoother over a patch solver, cheb.inc.hpp).  z_i = sum contrib in the order of the
+// gathers above, then the recurrence in the epilogue: d_i = b z_i in the first sweep of a pass (FIRST: d is not read, it may hold
+// anything), d_i = a d_i + b z_i afterwards -- each product rounded, then the sum -- and x_i += d_i (x_i = d_i where x_zero holds).
+// Kernels of their own next to the Richardson forms, which keep their code and their bits.
+template <bool FIRST>
+__device__ __forceinline__ void cheb_epilogue(int64_t i, double z, double a, double b, int x_zero, double *__restrict__ d, double *__restrict__ x)
+{
+  const double t = __dmul_rn(b, z);
+  const double di = FIRST ? t : __dadd_rn(__dmul_rn(a, d[i]), t);
+  d[i] = di;
+  x[i] = x_zero ? di : __dadd_rn(x[i], di);
+}
+
+template <bool FIRST>
+__global__ void patch_gather_cheb_kernel(int64_t n, const int64_t *__restrict__ iptr, const int64_t *__restrict__ inc,
+                                         const double *__restrict__ contrib, double a, double b, int x_zero,
+                                         double *__restrict__ d, double *__restrict__ x)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double s = 0.0;
+  for (int64_t k = iptr[i]; k < iptr[i + 1]; ++k) s += contrib[inc[k]];
+  cheb_epilogue<FIRST>(i, s, a, b, x_zero, d, x);
+}
+
+template <bool FIRST>
+__global__ void patch_gather_sell_cheb_kernel(int64_t n, const int64_t *__restrict__ soff, const int32_t *__restrict__ sinc,
+                                              const double *__restrict__ contrib, double a, double b, int x_zero,
+                                              double *__restrict__ d, double *__restrict__ x)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t slice = i >> 6;
+  const int lane = (int)(i & 63);
+  const int64_t base = soff[slice];
+  const int w = (int)((soff[slice + 1] - base) >> 6);
+  const int32_t *ip = sinc + base + lane;
+  double s = 0.0;
+  int j = 0;
+  for (; j + 4 <= w; j += 4) {                               // (the unrolling of patch_gather_sell_kernel: the same sums in the same order)
+    const int32_t i0 = ip[(int64_t)j * 64], i1 = ip[(int64_t)(j + 1) * 64], i2 = ip[(int64_t)(j + 2) * 64], i3 = ip[(int64_t)(j + 3) * 64];
+    const double c0 = contrib[i0], c1 = contrib[i1], c2 = contrib[i2], c3 = contrib[i3];
+    s += c0; s += c1; s += c2; s += c3;
+  }
+  for (; j < w; ++j) s += contrib[ip[(int64_t)j * 64]];
+  cheb_epilogue<FIRST>(i, s, a, b, x_zero, d, x);
+}
+
 } // namespace gmg

@@ -35,6 +35,7 @@ using GridapSolvers.SolverInterfaces: ConvergenceLog, SolverTolerances
 using GridapSolvers.LinearSolvers: RichardsonSmoother, JacobiLinearSolver, GaussSeidelSmoother, LinearSolverFromSmoother
 
 export HipGMGLinearSolver, HipCGSolver, HipFGMRESSolver, HipMINRESSolver, PatchTable, HipPatchProlongation
+export ChebyshevSmoother, chebyshev_info
 export HipRichardsonLinearSolver, HipBlockTriangularSolver, HipBlockDiagonalSolver, HipBlockFGMRESSolver, block_mul!, block_cg_solve!
 export block_minres_solve!
 export HipGMRESSolver, HipBlockGMRESSolver
@@ -295,6 +296,53 @@ function _set_smoother(h, lev, which, sm::GaussSeidelSmoother)
                  h, lev, which, sm.niter, sm.ω, t))
 end
 
+# ChebyshevSmoother(M; degree, lambda_max, lambda_min, eig_ratio, eig_safety, eig_steps): a type of this binding -- the reference has no
+# Chebyshev smoother.  M is what RichardsonSmoother takes here (JacobiLinearSolver() or a PatchTable); one pass is the Chebyshev
+# recurrence of `degree` sweeps in M^-1 A on [lambda_min, lambda_max] (gmg_set_smoother_chebyshev).  lambda_max = nothing: gmg_setup
+# estimates it per level with eig_steps power steps and takes eig_safety times the estimate; lambda_min = nothing: lambda_max / eig_ratio.
+# Usable wherever a RichardsonSmoother over the same M is, on one GPU (HipDistributedGMG* do not take it).
+struct ChebyshevSmoother{A}
+  M          :: A
+  degree     :: Int
+  lambda_max :: Union{Nothing,Float64}
+  lambda_min :: Union{Nothing,Float64}
+  eig_ratio  :: Float64
+  eig_safety :: Float64
+  eig_steps  :: Int
+  function ChebyshevSmoother(M::A; degree::Integer=3, lambda_max=nothing, lambda_min=nothing, eig_ratio::Real=10.0,
+                             eig_safety::Real=1.1, eig_steps::Integer=10) where A
+    (M isa JacobiLinearSolver || M isa PatchTable) || error("ChebyshevSmoother: M must be JacobiLinearSolver() or a PatchTable")
+    degree >= 1 || error("The degree must be a positive integer.")
+    (lambda_max === nothing || lambda_max > 0) || error("lambda_max must be a positive real number (or nothing: estimated by the setup).")
+    (lambda_min === nothing || lambda_min > 0) || error("lambda_min must be a positive real number (or nothing: lambda_max / eig_ratio).")
+    (lambda_max === nothing || lambda_min === nothing || lambda_min < lambda_max) || error("lambda_min must be smaller than lambda_max.")
+    eig_ratio > 1 || error("eig_ratio must be greater than 1.")
+    eig_safety >= 1 || error("eig_safety must be at least 1.")
+    eig_steps >= 1 || error("eig_steps must be a positive integer.")
+    new{A}(M, Int(degree), lambda_max === nothing ? nothing : Float64(lambda_max), lambda_min === nothing ? nothing : Float64(lambda_min),
+           Float64(eig_ratio), Float64(eig_safety), Int(eig_steps))
+  end
+end
+
+# the slot's M through its own setter (niter and omega are unused), then the Chebyshev iteration over it
+function _set_smoother(h, lev, which, sm::ChebyshevSmoother)
+  _set_smoother(h, lev, which, RichardsonSmoother(sm.M, 1, 1.0))
+  check(h, ccall((:gmg_set_smoother_chebyshev, libgmgamd), Cint, (Ptr{Cvoid},Cint,Cint,Cint,Float64,Float64,Cint,Float64,Float64),
+                 h, lev, which, sm.degree, sm.lambda_min === nothing ? 0.0 : sm.lambda_min, sm.lambda_max === nothing ? 0.0 : sm.lambda_max,
+                 sm.eig_steps, sm.eig_ratio, sm.eig_safety))
+end
+
+# gmg_get_chebyshev_info: what the setup fixed for the ChebyshevSmoother of a slot (lev is 1-based, which = :pre or :post);
+# lambda_est is NaN where the bounds were given
+function chebyshev_info(ns::HipGMGNumericalSetup, lev::Integer=1; which::Symbol=:pre)
+  deg, steps = Ref(Cint(0)), Ref(Cint(0))
+  est, lmin, lmax = Ref(0.0), Ref(0.0), Ref(0.0)
+  check(ns.handle, ccall((:gmg_get_chebyshev_info, libgmgamd), Cint,
+                         (Ptr{Cvoid},Cint,Cint,Ref{Cint},Ref{Float64},Ref{Float64},Ref{Float64},Ref{Cint}),
+                         ns.handle, lev-1, which === :post ? GMG_POST : GMG_PRE, deg, est, lmin, lmax, steps))
+  return (degree=Int(deg[]), lambda_est=est[], lambda_min=lmin[], lambda_max=lmax[], eig_steps=Int(steps[]))
+end
+
 # the visiting order of a level's Gauss-Seidel sweeps (inert on a level without such a smoother); takes effect at gmg_setup
 function _set_gs_ordering(h, lev, o)
   if o isa Symbol
@@ -503,7 +551,7 @@ _gmres_side(::Nothing) = (Cint(0), nothing)
 _gmres_side(P::HipGMGLinearSolver) = (Cint(1), P)
 function _gmres_side(P::Tuple{Any,HipGMGLinearSolver})
   if P[1] isa LinearSolverFromSmoother
-    (P[1].smoother isa Union{RichardsonSmoother,GaussSeidelSmoother} && P[1].smoother === P[2].pre_smoothers[1]) ||
+    (P[1].smoother isa Union{RichardsonSmoother,GaussSeidelSmoother,ChebyshevSmoother} && P[1].smoother === P[2].pre_smoothers[1]) ||
       error("LinearSolverFromSmoother must wrap the GMG's finest pre-smoother")
     return (Cint(3), P[2])
   end

@@ -11,6 +11,7 @@ julia/GridapSolversAMD.jl.
     JacobiLinearSolver()            JacobiLinearSolvers.jl:6        JacobiLinearSolver
     RichardsonSmoother(M,niter,w)   RichardsonSmoothers.jl:21-30    RichardsonSmoother
     PatchSolver / BlockJacobiSolver PatchBasedSmoothers/*.jl        PatchSolver / BlockJacobiSolver
+    (none: an addition of the device library)                       ChebyshevSmoother(M, degree, ...)
     GMGLinearSolver(mats,P,R;...)   GMGLinearSolvers.jl:48-69       GMGLinearSolver
     CGSolver(Pl;...)                Krylov/CGSolvers.jl:19          CGSolver
     FGMRESSolver(m,Pr;...)          Krylov/FGMRESSolvers.jl:26      FGMRESSolver
@@ -38,7 +39,7 @@ import numpy as np
 from . import abi
 
 __all__ = [
-    "JacobiLinearSolver", "RichardsonSmoother", "GaussSeidelSmoother", "SymGaussSeidelSmoother", "multicolor_order", "PatchSolver", "BlockJacobiSolver", "LUSolver",
+    "JacobiLinearSolver", "RichardsonSmoother", "ChebyshevSmoother", "GaussSeidelSmoother", "SymGaussSeidelSmoother", "multicolor_order", "PatchSolver", "BlockJacobiSolver", "LUSolver",
     "GMGLinearSolver", "CGSolver", "FGMRESSolver", "MINRESSolver", "GMRESSolver", "ConvergenceLog", "PatchProlongationOperator",
     "RichardsonLinearSolver", "BlockDiagonalSolver", "BlockTriangularSolver", "SchurComplementSolver", "LinearSystemBlock", "NonlinearSystemBlock", "MatrixBlock", "LinearSolverFromSmoother",
     "NullSpace", "NullspaceSolver", "is_orthonormal", "is_orthogonal", "make_orthonormal_", "gram_schmidt_", "modified_gram_schmidt_",
@@ -117,6 +118,39 @@ class RichardsonSmoother:
         self.M, self.niter, self.omega = M, int(niter), float(omega)
 
 
+class ChebyshevSmoother:
+    """ChebyshevSmoother(M, degree=3, lambda_max=None, lambda_min=None, eig_ratio=10.0, eig_safety=1.1, eig_steps=10): a Chebyshev
+    polynomial of `degree` in M^-1 A where RichardsonSmoother(M, niter, omega) runs niter damped sweeps (gmg_set_smoother_chebyshev).
+    No reference counterpart; one GPU only.
+
+    lambda_max given: the interval is [lambda_min, lambda_max], lambda_min defaulting to lambda_max / eig_ratio.  Otherwise the setup
+    estimates lambda_max(M^-1 A) per level by eig_steps power steps and takes lambda_max = eig_safety * estimate (PETSc's
+    convention); see GMGNumericalSetup.chebyshev_info.  A few power steps under-estimate a clustered top of the spectrum: pass
+    lambda_max or raise eig_steps where that matters."""
+
+    def __init__(self, M, degree=3, lambda_max=None, lambda_min=None, eig_ratio=10.0, eig_safety=1.1, eig_steps=10):
+        if not isinstance(M, (JacobiLinearSolver, PatchSolver)):
+            raise TypeError("ChebyshevSmoother: M must be JacobiLinearSolver, PatchSolver or BlockJacobiSolver")
+        if not int(degree) >= 1:
+            raise ValueError("The degree must be a positive integer.")
+        if lambda_max is not None and not float(lambda_max) > 0.0:
+            raise ValueError("lambda_max must be a positive real number (or None: estimated by the setup).")
+        if lambda_min is not None and not float(lambda_min) > 0.0:
+            raise ValueError("lambda_min must be a positive real number (or None: lambda_max / eig_ratio).")
+        if lambda_max is not None and lambda_min is not None and not float(lambda_min) < float(lambda_max):
+            raise ValueError("lambda_min must be smaller than lambda_max.")
+        if not float(eig_ratio) > 1.0:
+            raise ValueError("eig_ratio must be greater than 1.")
+        if not float(eig_safety) >= 1.0:
+            raise ValueError("eig_safety must be at least 1.")
+        if not int(eig_steps) >= 1:
+            raise ValueError("eig_steps must be a positive integer.")
+        self.M, self.degree = M, int(degree)
+        self.lambda_max = None if lambda_max is None else float(lambda_max)
+        self.lambda_min = None if lambda_min is None else float(lambda_min)
+        self.eig_ratio, self.eig_safety, self.eig_steps = float(eig_ratio), float(eig_safety), int(eig_steps)
+
+
 class GaussSeidelSmoother:
     """GaussSeidelSmoother(niter=1, omega=1.0, type=:symmetric) -- SymGaussSeidelSmoothers.jl:105-118.
 
@@ -181,8 +215,8 @@ class LinearSolverFromSmoother:
     """LinearSolverFromSmoother(smoother) -- LinearSolverFromSmoothers.jl:2-4: x = 0; r = copy(b); solve!(x,smoother,r)."""
 
     def __init__(self, smoother):
-        if not isinstance(smoother, (RichardsonSmoother, GaussSeidelSmoother)):
-            raise TypeError("smoother must be a RichardsonSmoother or a GaussSeidelSmoother")
+        if not isinstance(smoother, (RichardsonSmoother, GaussSeidelSmoother, ChebyshevSmoother)):
+            raise TypeError("smoother must be a RichardsonSmoother, a GaussSeidelSmoother or a ChebyshevSmoother")
         self.smoother = smoother
 
 
@@ -725,8 +759,15 @@ class GMGNumericalSetup:
         if isinstance(sm, GaussSeidelSmoother):
             abi.check(h, lib.gmg_set_smoother_gauss_seidel(h, l, which, sm.niter, sm.omega, sm._TYPES[sm.type]))
             return
+        if isinstance(sm, ChebyshevSmoother):
+            # the slot's M through its own setter (niter and omega are unused), then the Chebyshev iteration over it
+            self._set_smoother(l, which, RichardsonSmoother(sm.M, 1, 1.0))
+            abi.check(h, lib.gmg_set_smoother_chebyshev(h, l, which, sm.degree, 0.0 if sm.lambda_min is None else sm.lambda_min,
+                                                        0.0 if sm.lambda_max is None else sm.lambda_max, sm.eig_steps, sm.eig_ratio,
+                                                        sm.eig_safety))
+            return
         if not isinstance(sm, RichardsonSmoother):
-            raise TypeError("smoothers must be RichardsonSmoother or GaussSeidelSmoother objects")
+            raise TypeError("smoothers must be RichardsonSmoother, GaussSeidelSmoother or ChebyshevSmoother objects")
         if isinstance(sm.M, JacobiLinearSolver):
             abi.check(h, lib.gmg_set_smoother_jacobi(h, l, which, sm.niter, sm.omega))
         else:
@@ -894,6 +935,18 @@ class GMGNumericalSetup:
         v = C.c_int64(0)
         abi.check(self.h, self._lib.gmg_device_bytes(self.h, C.byref(v)))
         return v.value
+
+    def chebyshev_info(self, lev=0, which="pre"):
+        """gmg_get_chebyshev_info: what the setup fixed for the ChebyshevSmoother of a slot (which = "pre" / "post") ->
+        dict(degree, lambda_est (NaN where the bounds were given), lambda_min, lambda_max, eig_steps); GmgError (ERR_STATE) on a
+        slot without one."""
+        if which not in ("pre", "post"):
+            raise ValueError('which must be "pre" or "post"')
+        deg, steps = C.c_int(0), C.c_int(0)
+        v = [C.c_double(0.0) for _ in range(3)]
+        abi.check(self.h, self._lib.gmg_get_chebyshev_info(self.h, lev, abi.PRE if which == "pre" else abi.POST, C.byref(deg),
+                                                           C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(steps)))
+        return dict(degree=deg.value, lambda_est=v[0].value, lambda_min=v[1].value, lambda_max=v[2].value, eig_steps=steps.value)
 
     def gs_schedule(self, lev=0, forward=True):
         """gmg_get_gs_schedule: what the setup of the level's Gauss-Seidel smoother built for one direction ->

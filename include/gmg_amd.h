@@ -234,7 +234,36 @@ GMG_API int gmg_get_gs_ordering(gmg_handle_t h, int lev, int *kind, int64_t *nco
 GMG_API int gmg_gs_multicolor_order(int64_t nrows, const int64_t *ptr, const int32_t *col, int32_t *order, int32_t *color,
                                     int64_t *ncolors);
 
-/* Patch-corrected prolongation  y = P x - sum_p R_p^T A_pp^-1 R_p (A P x)  over the given patches
+/* ChebyshevSmoother(M, degree) over the preconditioner M of a smoother slot, M = JacobiLinearSolver / PatchSolver / BlockJacobiSolver.
+ * The reference has no such smoother; it is an addition of this library (like the Gauss-Seidel orderings), on one GPU.
+ * Call it AFTER gmg_set_smoother_jacobi / gmg_set_smoother_patch[_matrices] on the same slot: it turns that slot's Richardson
+ * iteration into the Chebyshev one (the slot's niter and omega are then unused).  Setting a plain smoother on the slot again clears it.
+ * One pass of degree m on (x, r), with z = M^-1 r the un-relaxed preconditioner (Saad, Alg. 12.1, residual form):
+ *   theta = (lmax + lmin)/2 ; delta = (lmax - lmin)/2 ; sigma = theta/delta ; rho_0 = 1/sigma
+ *   sweep 0:           d = (1/theta) z                               ; x += d ; r -= A d
+ *   sweep k = 1..m-1:  rho_k = 1/(2 sigma - rho_{k-1}) ; d = (rho_k rho_{k-1}) d + (2 rho_k/delta) z ; x += d ; r -= A d
+ * The coefficients are computed on the host in double in this order, once per setup; the kernels round each product, then the sum.
+ * Bounds: lambda_max > 0 is used as it is, with lambda_min > 0 or, for lambda_min <= 0, lambda_max / eig_ratio.  lambda_max <= 0:
+ * gmg_setup estimates lambda_est = lambda_max(M^-1 A) per level and slot (pre and post share it when they share M) by eig_steps power
+ * steps w = M^-1 (A v) ; lambda_est = ||w||_2 ; v = w / lambda_est from v_i = 1 + ((i * 2654435761) mod 1024)/1024 (0-based row i,
+ * unsigned 64-bit), normalised; then lambda_max = eig_safety * lambda_est and lambda_min as above.  A few power steps UNDER-estimate a
+ * clustered top of the spectrum (Jacobi on Q1 32^3: 1.336 after 10 steps, true 1.494): pass lambda_max or raise eig_steps where that
+ * matters.  The reference-style defaults of the host layers: degree 3, eig_steps 10, eig_safety 1.1, eig_ratio 10.
+ * gmg_update_values[_csc] + gmg_setup estimate again where the bound was not given.
+ * Errors: GMG_ERR_STATE if the slot has no smoother yet; GMG_ERR_UNSUPPORTED on a Gauss-Seidel slot; GMG_ERR_INVALID for degree < 1,
+ * lambda_min >= lambda_max when both are given, eig_ratio <= 1, eig_safety < 1 or eig_steps < 1.  A handle with a communicator
+ * (gmg_comm_init_*) and a Chebyshev slot is refused at gmg_setup with GMG_ERR_UNSUPPORTED.
+ * gmg_smooth runs one pass; gmg_precond_apply on such a slot returns z = M^-1 r, the operator whose spectrum is estimated;
+ * gmg_sweep_signature of a level with such a slot ends in " cheb=<pre degree>/<post degree>" (0 for a slot without).  The one-launch
+ * passes, folded transfers and the other shortcuts of the Richardson-Jacobi passes do not apply to such a slot. */
+GMG_API int gmg_set_smoother_chebyshev(gmg_handle_t h, int lev, int which, int degree, double lambda_min, double lambda_max,
+                                       int eig_steps, double eig_ratio, double eig_safety);
+/* What the last gmg_setup fixed for the slot (which = GMG_PRE or GMG_POST): lambda_est is NaN where the bounds were given.  Any of the
+ * outputs may be NULL.  GMG_ERR_STATE before gmg_setup or on a slot without a Chebyshev smoother. */
+GMG_API int gmg_get_chebyshev_info(gmg_handle_t h, int lev, int which, int *degree, double *lambda_est, double *lambda_min,
+                                   double *lambda_max, int *eig_steps);
+
+/* Patch-corrected prolongation y = P x - sum_p R_p^T A_pp^-1 R_p (A P x)  over the given patches
  * (PatchProlongationOperator, PatchBasedSmoothers/PatchTransferOperators.jl:153-172 with rhs = lhs = the
  * level operator; used by the reference for grad-div problems, test/Applications/StokesGMG.jl:125-133).
  * Same patch-table format as gmg_set_smoother_patch. */
