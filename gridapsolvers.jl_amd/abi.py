@@ -17,6 +17,7 @@ PRE, POST, PRE_AND_POST = 0, 1, 2
 PATCH_LU, PATCH_NOPIVOT = 0, 1
 GS_SYMMETRIC, GS_FORWARD, GS_BACKWARD = 0, 1, 2
 GS_ORDER_NATURAL, GS_ORDER_MULTICOLOR, GS_ORDER_GIVEN = 0, 1, 2
+CHEB_EIG_POWER, CHEB_EIG_LANCZOS = 0, 1
 OP_A, OP_P, OP_R = 0, 1, 2
 LEVEL_KRYLOV = -1          # GMG_LEVEL_KRYLOV: the separate Krylov operator of a finest level in the overlapping layout
 COARSE_DENSE_INVERSE, COARSE_CG_JACOBI, COARSE_HOST_CALLBACK = 0, 1, 2
@@ -81,6 +82,8 @@ SYMBOLS = {
     "gmg_set_smoother_chebyshev": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double],
     "gmg_get_chebyshev_info": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                C.POINTER(C.c_double), C.POINTER(C.c_int)],
+    "gmg_set_chebyshev_eig_method": [C.c_void_p, C.c_int, C.c_int, C.c_int],
+    "gmg_get_chebyshev_eig": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "gmg_set_gs_ordering": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64],
     "gmg_get_gs_ordering": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.c_void_p, C.c_int64],
     "gmg_gs_multicolor_order": [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)],
@@ -106,6 +109,8 @@ SYMBOLS = {
     "gmg_apply": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Result), C.c_void_p, C.c_int],
     "gmg_cg_solve": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
                      C.POINTER(Result), C.c_void_p, C.c_int],
+    "gmg_cg_set_trace": [C.c_void_p, C.c_int],
+    "gmg_cg_get_trace": [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int],
     "gmg_fgmres_solve": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                          C.c_double, C.c_double, C.c_int, C.POINTER(Result), C.c_void_p, C.c_int],
     "gmg_fgmres_solve_pl": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

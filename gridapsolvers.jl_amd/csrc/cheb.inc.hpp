@@ -21,8 +21,26 @@
 // lambda_est = ||w||_2 ; v = w/lambda_est -- the level's mat-vec, the slot's preconditioner and the dot kernel, nothing new.  Then
 // lambda_max = eig_safety lambda_est, lambda_min = lambda_max/eig_ratio (PETSc's interval convention).  KNOWN WEAKNESS: a few power
 // steps under-estimate a clustered top of the spectrum (Jacobi on Q1 32^3: 1.336 after 10 steps against 1.494, so 1.1 lambda_est is
-// still below lambda_max); pass lambda_max or raise eig_steps where that matters.  A value refresh (gmg_update_values + gmg_setup)
-// estimates again.
+// still below lambda_max).  THE REMEDY is the Lanczos estimate below (gmg_set_chebyshev_eig_method: 1.455 after the same 10 steps, so
+// 1.1 lambda_est covers lambda_max); a given lambda_max or more eig_steps do as well.  A value refresh (gmg_update_values + gmg_setup)
+// estimates again, by the slot's method.
+//
+// LANCZOS ESTIMATE (GMG_CHEB_EIG_LANCZOS; POWER stays the default).  eig_steps steps of CG on A with preconditioner M from r = the same
+// start vector, normalised; lambda_est is the largest eigenvalue of the Lanczos tridiagonal that CG builds:
+//   r = v ; gamma_old = 1 ; k = 0
+//   while k < eig_steps:
+//     z = M^-1 r ; gamma = dot(z, r)    stop unless gamma is finite and > 0 ; for k > 0 also stop if gamma < 1e-24 * gamma_0
+//     beta = gamma / gamma_old ; p = z + beta p   (k = 0: p = z)
+//     w = A p ; pw = dot(p, w)          stop unless pw is finite and > 0
+//     alpha = gamma / pw ; r -= alpha w ; record (alpha, beta) ; gamma_old = gamma ; k += 1
+//   T (k x k): T[i,i] = 1/alpha_i + (i > 0 ? beta_i/alpha_{i-1} : 0) ; T[i,i+1] = T[i+1,i] = sqrt(beta_{i+1})/alpha_i   (textbook form)
+// The 1e-24 stop is a condition, not a tolerance: the residual has dropped twelve digits in the M^-1 norm, the Krylov space is exhausted
+// in double and further steps add rounding noise only (levels of 1, 9 and 27 rows stop after 1, 6 and 7 steps with the exact
+// lambda_max).  A stop with no step recorded is GMG_ERR_SINGULAR.  Driven from the host like the power iteration -- the level's
+// mat-vec, cheb_precond, the dot kernel, xpby_kernel and axpy_kernel, a fetch per dot; r, z, w in the level's work vectors, p in a vector
+// that lives for the estimate only -- and the largest eigenvalue of T (at most eig_steps rows) by Sturm bisection on the host
+// (cheb_tridiag_lambda_max).  Per step: one mat-vec, one M^-1 and two dots against one mat-vec, one M^-1 and one norm.  What it buys is
+// a robust default interval, not a faster solve.  Pre and post share one estimate when they share M, eig_steps and the method.
 //
 // KERNELS (all HBM-bound streaming):
 //   cheb_update_kernel<FIRST, DINV>   the pointwise update d = [a d +] b z ; x (+)= d with z = dinv .* r (Jacobi M, DINV) or z as it
@@ -112,6 +130,39 @@ void cheb_coefficients(int m, double lmin, double lmax, std::vector<double> &a, 
   }
 }
 
+// largest eigenvalue of the symmetric tridiagonal (diagonal d[0..k), off-diagonal e[0..k-1)) by Sturm bisection: the number of
+// eigenvalues below x is the number of negative pivots of T - x I.  Bisected until the interval is two neighbouring doubles.
+double cheb_tridiag_lambda_max(const std::vector<double> &d, const std::vector<double> &e)
+{
+  const int k = (int)d.size();
+  if (k == 1) return d[0];
+  double lo = d[0], hi = d[0];
+  for (int i = 0; i < k; ++i) {                              // Gershgorin
+    const double rad = (i > 0 ? std::fabs(e[(size_t)i - 1]) : 0.0) + (i + 1 < k ? std::fabs(e[(size_t)i]) : 0.0);
+    lo = std::min(lo, d[(size_t)i] - rad); hi = std::max(hi, d[(size_t)i] + rad);
+  }
+  const double scale = std::max(std::fabs(lo), std::fabs(hi));
+  const double eps = std::numeric_limits<double>::epsilon(), tiny = std::numeric_limits<double>::min();
+  hi += 4.0 * eps * scale + tiny;                            // all k eigenvalues are below hi
+  const auto below = [&](double x) {
+    int c = 0;
+    double q = d[0] - x;
+    if (q < 0.0) ++c;
+    for (int i = 1; i < k; ++i) {
+      if (q == 0.0) q = eps * scale + tiny;
+      q = d[(size_t)i] - x - e[(size_t)i - 1] * e[(size_t)i - 1] / q;
+      if (q < 0.0) ++c;
+    }
+    return c;
+  };
+  for (int it = 0; it < 4096; ++it) {
+    const double mid = lo + (hi - lo) / 2.0;
+    if (!(mid > lo && mid < hi)) break;
+    if (below(mid) == k) hi = mid; else lo = mid;
+  }
+  return lo + (hi - lo) / 2.0;
+}
+
 bool cheb_same_M(const Smoother &p, const Smoother &q)
 {
   if (p.kind != q.kind) return false;
@@ -131,7 +182,56 @@ void gmg_solver::cheb_precond(Level &L, Smoother &S, const double *r, double *z)
     patch_precond(L, S, r, 1.0, false, z, nullptr);
 }
 
-// spectrum bounds (given, or from the power iteration) and the coefficients of the slot.  same_M: the level's other slot, already set up
+// GMG_CHEB_EIG_LANCZOS: eig_steps steps of CG on A with preconditioner M from the normalised start vector, driven from the host (a fetch
+// per dot: setup work); lambda_est = the largest eigenvalue of the textbook Lanczos tridiagonal of the recorded (alpha, beta).  r, z, w in
+// the level's work vectors, p in a vector that lives for the estimate only.  Sets S.cheb_steps_done.
+double gmg_solver::cheb_lanczos(int l, Smoother &S, const std::string &where)
+{
+  Level &L = lev[l];
+  const int64_t n = L.n;
+  double *r = L.rbuf[0], *z = L.rbuf[1], *w = L.dx, *p = dvec(L.nvec);
+  struct Free { gmg_solver &G; double *&p; size_t n; ~Free() { (void)hipStreamSynchronize(G.stream); G.release(p, n); } } free_p{*this, p, (size_t)L.nvec};
+  hipLaunchKernelGGL(cheb_start_kernel, dim3(grid_for(n)), dim3(256), 0, stream, n, r);
+  HIP_CHECK(hipGetLastError());
+  const double nv = norm(n, r);
+  REQUIRE(std::isfinite(nv) && nv > 0.0, GMG_ERR_SINGULAR, where + "the start vector of the Lanczos estimate has norm " + std::to_string(nv));
+  hipLaunchKernelGGL(cheb_div_kernel, dim3(grid_for(n)), dim3(256), 0, stream, n, r, nv, r);
+  HIP_CHECK(hipGetLastError());
+  std::vector<double> al, be;
+  double gamma_old = 1.0, gamma0 = 0.0;
+  for (int k = 0; k < S.cheb_eig_steps; ++k) {
+    cheb_precond(L, S, r, z);
+    const double gamma = dot(n, z, r);
+    if (!(std::isfinite(gamma) && gamma > 0.0)) break;
+    if (k == 0) gamma0 = gamma;
+    else if (gamma < 1e-24 * gamma0) break;                  // the Krylov space is exhausted in double
+    const double beta = gamma / gamma_old;
+    if (k == 0) copy(p, z, n);
+    else hipLaunchKernelGGL(xpby_kernel, dim3(grid_for(n)), dim3(256), 0, stream, n, z, beta, p);
+    HIP_CHECK(hipGetLastError());
+    apply_A_set(l, p, w);
+    const double pw = dot(n, p, w);
+    if (!(std::isfinite(pw) && pw > 0.0)) break;
+    const double alpha = gamma / pw;
+    hipLaunchKernelGGL(axpy_kernel, dim3(grid_for(n)), dim3(256), 0, stream, n, -alpha, w, r);
+    HIP_CHECK(hipGetLastError());
+    al.push_back(alpha); be.push_back(beta);
+    gamma_old = gamma;
+  }
+  const int k = (int)al.size();
+  REQUIRE(k > 0, GMG_ERR_SINGULAR, where + "the Lanczos estimate recorded no step: M^-1 A is not positive definite on level " +
+          std::to_string(l) + " (use eig_method = power or pass lambda_max)");
+  std::vector<double> d((size_t)k), e((size_t)k - 1);
+  for (int i = 0; i < k; ++i) {
+    d[(size_t)i] = 1.0 / al[(size_t)i] + (i > 0 ? be[(size_t)i] / al[(size_t)i - 1] : 0.0);
+    if (i + 1 < k) e[(size_t)i] = std::sqrt(be[(size_t)i + 1]) / al[(size_t)i];
+  }
+  S.cheb_steps_done = k;
+  return cheb_tridiag_lambda_max(d, e);
+}
+
+// spectrum bounds (given, or from the power iteration / the Lanczos estimate) and the coefficients of the slot.  same_M: the level's other
+// slot, already set up
 void gmg_solver::cheb_setup(int l, Smoother &S, const Smoother *same_M)
 {
   Level &L = lev[l];
@@ -140,9 +240,14 @@ void gmg_solver::cheb_setup(int l, Smoother &S, const Smoother *same_M)
   if (S.cheb_lmax_in > 0.0) {
     S.cheb_lest = NAN;
     S.cheb_lmax = S.cheb_lmax_in;
+    S.cheb_steps_done = 0;
   } else {
-    if (same_M && same_M->cheb && !(same_M->cheb_lmax_in > 0.0) && same_M->cheb_eig_steps == S.cheb_eig_steps && cheb_same_M(*same_M, S))
+    if (same_M && same_M->cheb && !(same_M->cheb_lmax_in > 0.0) && same_M->cheb_eig_steps == S.cheb_eig_steps &&
+        same_M->cheb_eig_method == S.cheb_eig_method && cheb_same_M(*same_M, S)) {
       S.cheb_lest = same_M->cheb_lest;
+      S.cheb_steps_done = same_M->cheb_steps_done;
+    } else if (S.cheb_eig_method == GMG_CHEB_EIG_LANCZOS)
+      S.cheb_lest = cheb_lanczos(l, S, where);
     else {
       // v, A v and M^-1 A v in the level's work vectors (nothing of a solve is alive during setup)
       const int64_t n = L.n;
@@ -160,6 +265,7 @@ void gmg_solver::cheb_setup(int l, Smoother &S, const Smoother *same_M)
         lam = norm(n, w);
       }
       S.cheb_lest = lam;
+      S.cheb_steps_done = S.cheb_eig_steps;
     }
     S.cheb_lmax = S.cheb_eig_safety * S.cheb_lest;
   }
@@ -246,10 +352,46 @@ int gmg_set_smoother_chebyshev(gmg_handle_t h, int lev, int which, int degree, d
       sp->cheb_lmin_in = lambda_min > 0.0 ? lambda_min : 0.0;
       sp->cheb_lmax_in = lambda_max > 0.0 ? lambda_max : 0.0;
       sp->cheb_eig_ratio = eig_ratio; sp->cheb_eig_safety = eig_safety;
+      sp->cheb_eig_method = GMG_CHEB_EIG_POWER; sp->cheb_steps_done = 0;
       sp->cheb_a.clear(); sp->cheb_b.clear();
     }
     L.clear_overlap_hints();
     h->touch();
+  });
+}
+
+int gmg_set_chebyshev_eig_method(gmg_handle_t h, int lev, int which, int method)
+{
+  return guarded(h, [&] {
+    check_level(h, lev, true);
+    REQUIRE(which == GMG_PRE || which == GMG_POST || which == GMG_PRE_AND_POST, GMG_ERR_INVALID, "bad `which`");
+    REQUIRE(method == GMG_CHEB_EIG_POWER || method == GMG_CHEB_EIG_LANCZOS, GMG_ERR_INVALID,
+            "gmg_set_chebyshev_eig_method: the method must be GMG_CHEB_EIG_POWER or GMG_CHEB_EIG_LANCZOS");
+    Level &L = h->lev[lev];
+    const bool on_pre = which != GMG_POST, on_post = which != GMG_PRE;
+    for (const Smoother *sp : {on_pre ? &L.pre : nullptr, on_post ? (L.post_shares_pre ? &L.pre : &L.post) : nullptr})
+      REQUIRE(!sp || sp->cheb, GMG_ERR_STATE, "gmg_set_chebyshev_eig_method: the slot has no Chebyshev smoother (gmg_set_smoother_chebyshev first)");
+    // a slot of its own for the side that is changed alone
+    if (which != GMG_PRE_AND_POST && L.post_shares_pre) { L.post = L.pre; L.post_shares_pre = false; }
+    for (Smoother *sp : {on_pre ? &L.pre : nullptr, (on_post && !L.post_shares_pre) ? &L.post : nullptr}) {
+      if (!sp) continue;
+      sp->cheb_eig_method = method; sp->cheb_steps_done = 0;
+      sp->cheb_a.clear(); sp->cheb_b.clear();
+    }
+    h->touch();
+  });
+}
+
+int gmg_get_chebyshev_eig(gmg_handle_t h, int lev, int which, int *method, int *steps_done)
+{
+  return guarded(h, [&] {
+    check_ready(h);
+    check_level(h, lev, true);
+    REQUIRE(which == GMG_PRE || which == GMG_POST, GMG_ERR_INVALID, "which must be GMG_PRE or GMG_POST");
+    const Smoother &S = which == GMG_PRE ? h->lev[lev].pre : h->lev[lev].post;
+    REQUIRE(S.cheb, GMG_ERR_STATE, "this slot has no Chebyshev smoother");
+    if (method) *method = S.cheb_eig_method;
+    if (steps_done) *steps_done = S.cheb_steps_done;
   });
 }
 

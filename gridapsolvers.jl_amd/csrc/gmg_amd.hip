@@ -26,6 +26,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -401,6 +402,7 @@ struct Smoother {
   // niter and omega are unused.  *_in: what gmg_set_smoother_chebyshev was given (<= 0: estimate / derive); the rest is filled by setup.
   bool cheb = false;
   int cheb_degree = 0, cheb_eig_steps = 0;
+  int cheb_eig_method = 0, cheb_steps_done = 0;   // gmg_set_chebyshev_eig_method ; steps the last estimate took
   double cheb_lmin_in = 0.0, cheb_lmax_in = 0.0, cheb_eig_ratio = 0.0, cheb_eig_safety = 0.0;
   double cheb_lest = 0.0, cheb_lmin = 0.0, cheb_lmax = 0.0;
   std::vector<double> cheb_a, cheb_b;   // sweep k: d = cheb_a[k] d + cheb_b[k] z (cheb_a[0] unused: sweep 0 does not read d)
@@ -582,7 +584,7 @@ struct KrylovOps {
 struct gmg_block_solver;
 static void block_forget(gmg_block_solver *B, gmg_solver *g);   // block.inc.hpp
 static double cg_core(gmg_solver &S, int64_t n, const double *db, double *dx, double *w, double *p, double *z, double *r,
-                      const KrylovOps &ops, bool flexible, ConvLog &log);
+                      const KrylovOps &ops, bool flexible, ConvLog &log, bool traced = false);
 static double minres_core(gmg_solver &S, int64_t n, int64_t nv, const double *db, double *dx, double *const vec[9], double *parts,
                           const KrylovOps &ops, ConvLog &log);
 static double gmres_core(gmg_solver &S, int64_t n, int64_t nv, const double *db, double *dx, const KrylovOps &ops, int m0,
@@ -676,6 +678,16 @@ struct gmg_solver {
   double *h_cr = nullptr, *h_cx = nullptr;   // pinned staging of the host callback
   bool reduce_local = false;                 // reductions over a REPLICATED vector: no all-reduce across ranks
   int krylov_depth = 0;                      // nesting of cg_core calls (each level owns its scalar slots)
+  // gmg_cg_set_trace: alpha_k in d_trace[k], beta_k in d_trace[trace_cap + k] of the outermost CG of gmg_cg_solve.  An allocation of
+  // its own (free_all leaves it alone, like the null space), counted by gmg_device_bytes.
+  double *d_trace = nullptr;
+  int trace_cap = 0, trace_count = 0;
+  int64_t trace_bytes = 0;
+  void trace_release()
+  {
+    if (d_trace) { (void)hipStreamSynchronize(stream); (void)hipFree(d_trace); dev_bytes -= trace_bytes; }
+    d_trace = nullptr; trace_cap = trace_count = 0; trace_bytes = 0;
+  }
   // distributed runs: levels >= rep_from are REPLICATED (every rank holds the global operators and
   // computes them redundantly, no halo traffic on small levels).  The restricted residual of the last
   // distributed level is assembled with one all-reduce (own rows scattered by global id).
@@ -947,7 +959,7 @@ struct gmg_solver {
     for (void *p : allocs) (void)hipFree(p);
     allocs.clear();
     d_perr_dev = nullptr;
-    dev_bytes = ns.bytes;                                    // the null space is not part of a setup: it stays
+    dev_bytes = ns.bytes + trace_bytes;                      // the null space and the CG trace are not part of a setup: they stay
     for (auto &L : lev) {
       L.A = DevCSR(); L.P = DevCSR(); L.R = DevCSR(); L.G = DevCSR();
       L.dinv = L.x = L.dx = L.rcur = nullptr;
@@ -3221,6 +3233,7 @@ struct gmg_solver {
   // Chebyshev smoother (cheb.inc.hpp)
   void cheb_precond(Level &L, Smoother &S, const double *r, double *z);
   void cheb_setup(int l, Smoother &S, const Smoother *same_M);
+  double cheb_lanczos(int l, Smoother &S, const std::string &where);
   double *cheb_pass(int l, Smoother &S, double *x, const double *r_in, bool x_zero);
   void patch_contrib(Smoother &S, const double *r);
 
@@ -4427,7 +4440,7 @@ KrylovOps gmg_solver::level0_ops(int use_precond)
 
 // solve!(x,ns::CGNumericalSetup,b), Krylov/CGSolvers.jl:73-120
 static double cg_core(gmg_solver &S, int64_t n, const double *db, double *dx, double *w, double *p, double *z, double *r,
-               const KrylovOps &ops, bool flexible, ConvLog &log)
+               const KrylovOps &ops, bool flexible, ConvLog &log, bool traced)
 {
   // Scalars stay on the device: gamma (ping-pong), delta and dot(p,w) live in d_scalars and the vector
   // kernels form beta / alpha from them, so an iteration has ONE host round trip (the residual norm that
@@ -4439,6 +4452,11 @@ static double cg_core(gmg_solver &S, int64_t n, const double *db, double *dx, do
   const int sbase = kScalarSlots - 8 * S.krylov_depth;
   const int kG0 = sbase, kG1 = sbase + 1, kDelta = sbase + 2, kPW = sbase + 3;
   int g_old = kG0, g_new = kG1;
+  // traced (gmg_cg_solve with gmg_cg_set_trace on; never a nested CG): the kernels that form alpha_k and beta_k also store them.  The
+  // count restarts here, so a re-run by with_persist_retry leaves one consistent trace.
+  double *const tr_a = traced ? S.d_trace : nullptr, *const tr_b = traced ? S.d_trace + S.trace_cap : nullptr;
+  int it = 0;
+  if (traced) S.trace_count = 0;
   ops.resid(dx, db, r);                                  // CGSolvers.jl:79  w = A x ; r = b - w
   // :80 fill!(p,0): folded into the first p = z + beta*p ; :81 fill!(z,0): only the flexible variant reads z before writing it
   if (flexible) S.zero(z, n);
@@ -4468,7 +4486,7 @@ static double cg_core(gmg_solver &S, int64_t n, const double *db, double *dx, do
     }
     hipLaunchKernelGGL(xpby_dev_kernel, dim3(xgrid), dim3(kBlock), 0, S.stream, n, z, S.d_scalars + g_new,
                        S.d_scalars + g_old, (ops.precond && flexible) ? S.d_scalars + kDelta : nullptr, p, first ? 1 : 0,
-                       ngp ? S.d_partials : nullptr, ngp); // :101
+                       ngp ? S.d_partials : nullptr, ngp, tr_b ? tr_b + it : nullptr); // :101
     HIP_CHECK(hipGetLastError());
     int npw = 0;
     if (fuse && ops.apply_dot) npw = ops.apply_dot(p, w, S.d_partials);   // :104-105 in one kernel (> 0), or :104 alone (-1)
@@ -4481,7 +4499,7 @@ static double cg_core(gmg_solver &S, int64_t n, const double *db, double *dx, do
       // (option cg_split, default 0: measured equal to the single kernel, profiles/xnext_ab_128.md)
       // r -= alpha w and ||r|| first, x += alpha p behind the launch that posts the norm: it runs while the host decides
       hipLaunchKernelGGL(cg_update_r_kernel, dim3(nb), dim3(kBlock), 0, S.stream, n, S.d_scalars + g_new, S.d_scalars + kPW, w, r,
-                         nparts, npw ? S.d_partials : nullptr, npw); // :109
+                         nparts, npw ? S.d_partials : nullptr, npw, tr_a ? tr_a + it : nullptr); // :109
       HIP_CHECK(hipGetLastError());
       S.finish_reduction(nb, 0, true, nparts, true);
       hipLaunchKernelGGL(cg_update_x_kernel, dim3(nb), dim3(kBlock), 0, S.stream, n, S.d_scalars + g_new, S.d_scalars + kPW, p, dx);   // :108
@@ -4493,14 +4511,14 @@ static double cg_core(gmg_solver &S, int64_t n, const double *db, double *dx, do
         const int64_t o = S.vr_off[(size_t)q], nq = S.vr_off[(size_t)q + 1] - o;
         const int nbq = (int)std::max<int64_t>(1, std::min<int64_t>(kRedBlocks, (nq + kBlock - 1) / kBlock));
         hipLaunchKernelGGL(cg_update_kernel, dim3(nbq), dim3(kBlock), 0, S.stream, nq, S.d_scalars + g_new, S.d_scalars + kPW, p + o, w + o,
-                           dx + o, r + o, nparts, (const double *)nullptr, 0);
+                           dx + o, r + o, nparts, (const double *)nullptr, 0, tr_a ? tr_a + it : nullptr);   // (every launch stores the same alpha)
         hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kBlock), 0, S.stream, nbq, nparts, sums + q, 0);
         HIP_CHECK(hipGetLastError());
       }
       S.vr_finish(0, true);
     } else {
     hipLaunchKernelGGL(cg_update_kernel, dim3(nb), dim3(kBlock), 0, S.stream, n, S.d_scalars + g_new, S.d_scalars + kPW, p, w, dx, r,
-                       nparts, npw ? S.d_partials : nullptr, npw); // :108-109
+                       nparts, npw ? S.d_partials : nullptr, npw, tr_a ? tr_a + it : nullptr); // :108-109
     HIP_CHECK(hipGetLastError());
     S.finish_reduction(nb, 0, true, nparts, true);
     }
@@ -4508,6 +4526,8 @@ static double cg_core(gmg_solver &S, int64_t n, const double *db, double *dx, do
     done = log.update(resn);                             // :112
     std::swap(g_old, g_new);
     first = false;
+    ++it;
+    if (traced) S.trace_count = it;
   }
   // the posted norm no longer implies that x is complete: the last x += alpha p was issued behind it.  The outermost solve hands x
   // to its caller (who may read it from another stream); a nested one is consumed in stream order.
@@ -6685,6 +6705,7 @@ int gmg_destroy(gmg_handle_t h)
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
   h->ns_clear();
+  h->trace_release();
   h->free_all();
   for (auto &L : h->lev) {
     if (L.halo.h_send) (void)hipHostFree(L.halo.h_send);
@@ -7384,6 +7405,8 @@ int gmg_cg_solve(gmg_handle_t h, const double *b, double *x, int memspace, int m
     REQUIRE(b && x, GMG_ERR_INVALID, "null vector");
     REQUIRE(maxiter >= 0, GMG_ERR_INVALID, "maxiter < 0");
     REQUIRE(use_precond >= 0 && use_precond <= 3, GMG_ERR_INVALID, "use_precond must be 0, 1, 2 or 3");
+    REQUIRE(!h->d_trace || maxiter <= h->trace_cap, GMG_ERR_INVALID, "gmg_cg_solve: maxiter = " + std::to_string(maxiter) +
+            " exceeds the capacity of the trace, " + std::to_string(h->trace_cap) + " (gmg_cg_set_trace)");
     h->with_persist_retry(x, h->user_n(), memspace, false, [&] {
       gmg_solver &S = *h;
       Level &L0 = S.lev[S.kl()];
@@ -7396,10 +7419,44 @@ int gmg_cg_solve(gmg_handle_t h, const double *b, double *x, int memspace, int m
       ConvLog log;
       log.configure(maxiter, atol, rtol);
       KrylovOps ops = S.level0_ops(use_precond);
-      const double resn = cg_core(S, n, db, dx, S.cg_w, S.cg_p, S.cg_z, S.cg_r, ops, flexible != 0, log);
+      const double resn = cg_core(S, n, db, dx, S.cg_w, S.cg_p, S.cg_z, S.cg_r, ops, flexible != 0, log, S.d_trace != nullptr);
       S.out_vec(x, dx, n, memspace);
       log.export_to(res, hist, hist_cap, resn);              // :118
     });
+  });
+}
+
+int gmg_cg_set_trace(gmg_handle_t h, int capacity)
+{
+  return guarded(h, [&] {
+    REQUIRE(h, GMG_ERR_INVALID, "null handle");
+    REQUIRE(capacity >= 0, GMG_ERR_INVALID, "gmg_cg_set_trace: capacity < 0");
+    if (capacity == h->trace_cap) { h->trace_count = 0; return; }
+    h->trace_release();
+    if (capacity == 0) return;
+    const size_t bytes = 2 * (size_t)capacity * sizeof(double);
+    void *p = nullptr;
+    HIP_CHECK(hipMalloc(&p, bytes));
+    h->d_trace = reinterpret_cast<double *>(p);
+    h->trace_cap = capacity;
+    h->trace_bytes = (int64_t)bytes; h->dev_bytes += (int64_t)bytes;
+    HIP_CHECK(hipMemsetAsync(h->d_trace, 0, bytes, h->stream));
+  });
+}
+
+int gmg_cg_get_trace(gmg_handle_t h, int *count, double *alpha, double *beta, int cap)
+{
+  return guarded(h, [&] {
+    REQUIRE(h, GMG_ERR_INVALID, "null handle");
+    REQUIRE(h->d_trace, GMG_ERR_STATE, "gmg_cg_get_trace: tracing is off (gmg_cg_set_trace)");
+    const int k = h->trace_count;
+    if (count) *count = k;
+    if (!alpha && !beta) return;
+    REQUIRE(cap >= k, GMG_ERR_INVALID, "gmg_cg_get_trace: room for " + std::to_string(cap) + " values, " + std::to_string(k) + " recorded");
+    if (k == 0) return;
+    if (alpha) HIP_CHECK(hipMemcpyAsync(alpha, h->d_trace, sizeof(double) * (size_t)k, hipMemcpyDeviceToHost, h->stream));
+    if (beta) HIP_CHECK(hipMemcpyAsync(beta, h->d_trace + h->trace_cap, sizeof(double) * (size_t)k, hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->stream));
   });
 }
 

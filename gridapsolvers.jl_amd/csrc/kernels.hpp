@@ -3887,9 +3887,11 @@ __global__ void xpby_kernel(int64_t n, const double *__restrict__ z, double beta
 // first != 0: p is the zero vector of CGSolvers.jl:80 and is not read.
 // gparts != nullptr: gamma is still in the producer's partials (dot_partial_kernel): every workgroup sums them (sum_partials_all) and
 // workgroup 0 stores the scalar for the kernels that read it later.  blockDim.x == kBlock.
+// trace_beta / trace_alpha of the CG kernels (gmg_cg_set_trace): one lane also stores the scalar it formed; nullptr = an untraced solve.
 __global__ __launch_bounds__(kBlock) void xpby_dev_kernel(int64_t n, const double *__restrict__ z, double *__restrict__ gamma,
                                                           const double *__restrict__ gamma_old, const double *__restrict__ delta,
-                                                          double *__restrict__ p, int first, const double *__restrict__ gparts, int ngparts)
+                                                          double *__restrict__ p, int first, const double *__restrict__ gparts, int ngparts,
+                                                          double *__restrict__ trace_beta)
 {
   __shared__ double sh[5];
   double g;
@@ -3898,6 +3900,7 @@ __global__ __launch_bounds__(kBlock) void xpby_dev_kernel(int64_t n, const doubl
     if (blockIdx.x == 0 && threadIdx.x == 0) gamma[0] = g;
   } else g = gamma[0];
   const double beta = delta ? (g - delta[0]) / gamma_old[0] : g / gamma_old[0];
+  if (trace_beta && blockIdx.x == 0 && threadIdx.x == 0) trace_beta[0] = beta;   // gmg_cg_set_trace: beta_k as this launch uses it
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     p[i] = z[i] + beta * (first ? 0.0 : p[i]);
 }
@@ -3917,7 +3920,8 @@ __global__ __launch_bounds__(kBlock) void cg_update_kernel(int64_t n, const doub
                                                            double *__restrict__ pw, const double *__restrict__ p,
                                                            const double *__restrict__ w, double *__restrict__ x,
                                                            double *__restrict__ r, double *__restrict__ partials,
-                                                           const double *__restrict__ pwparts, int npwparts)
+                                                           const double *__restrict__ pwparts, int npwparts,
+                                                           double *__restrict__ trace_alpha)
 {
   __shared__ double sh[5];
   double pwv;
@@ -3927,6 +3931,7 @@ __global__ __launch_bounds__(kBlock) void cg_update_kernel(int64_t n, const doub
     __syncthreads();                                         // sh is reused below
   } else pwv = pw[0];
   const double alpha = gamma[0] / pwv;
+  if (trace_alpha && blockIdx.x == 0 && threadIdx.x == 0) trace_alpha[0] = alpha;   // gmg_cg_set_trace: alpha_k as this launch uses it
   double s = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
     x[i] += alpha * p[i];
@@ -3943,7 +3948,8 @@ __global__ __launch_bounds__(kBlock) void cg_update_kernel(int64_t n, const doub
 __global__ __launch_bounds__(kBlock) void cg_update_r_kernel(int64_t n, const double *__restrict__ gamma,
                                                              double *__restrict__ pw, const double *__restrict__ w,
                                                              double *__restrict__ r, double *__restrict__ partials,
-                                                             const double *__restrict__ pwparts, int npwparts)
+                                                             const double *__restrict__ pwparts, int npwparts,
+                                                             double *__restrict__ trace_alpha)
 {
   __shared__ double sh[5];
   double pwv;
@@ -3953,6 +3959,7 @@ __global__ __launch_bounds__(kBlock) void cg_update_r_kernel(int64_t n, const do
     __syncthreads();                                         // sh is reused below
   } else pwv = pw[0];
   const double alpha = gamma[0] / pwv;
+  if (trace_alpha && blockIdx.x == 0 && threadIdx.x == 0) trace_alpha[0] = alpha;
   double s = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
     const double rn = r[i] - alpha * w[i];

@@ -33,9 +33,11 @@ using Gridap.Algebra
 using GridapSolvers
 using GridapSolvers.SolverInterfaces: ConvergenceLog, SolverTolerances
 using GridapSolvers.LinearSolvers: RichardsonSmoother, JacobiLinearSolver, GaussSeidelSmoother, LinearSolverFromSmoother
+using GridapSolvers.LinearSolvers: LanczosDiagnostic, estimate!      # Krylov/KrylovUtils.jl:58-90, the reference's own type
 
 export HipGMGLinearSolver, HipCGSolver, HipFGMRESSolver, HipMINRESSolver, PatchTable, HipPatchProlongation
 export ChebyshevSmoother, chebyshev_info
+export LanczosDiagnostic, estimate!, cg_set_trace!, cg_trace
 export HipRichardsonLinearSolver, HipBlockTriangularSolver, HipBlockDiagonalSolver, HipBlockFGMRESSolver, block_mul!, block_cg_solve!
 export block_minres_solve!
 export HipGMRESSolver, HipBlockGMRESSolver
@@ -51,6 +53,7 @@ const GMG_PRE, GMG_POST, GMG_PRE_AND_POST = Cint(0), Cint(1), Cint(2)
 const GMG_PATCH_LU, GMG_PATCH_NOPIVOT = Cint(0), Cint(1)
 const GMG_GS_SYMMETRIC, GMG_GS_FORWARD, GMG_GS_BACKWARD = Cint(0), Cint(1), Cint(2)
 const GMG_GS_ORDER_NATURAL, GMG_GS_ORDER_MULTICOLOR, GMG_GS_ORDER_GIVEN = Cint(0), Cint(1), Cint(2)
+const GMG_CHEB_EIG_POWER, GMG_CHEB_EIG_LANCZOS = Cint(0), Cint(1)
 
 struct GmgResult
   niters::Int32
@@ -300,6 +303,9 @@ end
 # Chebyshev smoother.  M is what RichardsonSmoother takes here (JacobiLinearSolver() or a PatchTable); one pass is the Chebyshev
 # recurrence of `degree` sweeps in M^-1 A on [lambda_min, lambda_max] (gmg_set_smoother_chebyshev).  lambda_max = nothing: gmg_setup
 # estimates it per level with eig_steps power steps and takes eig_safety times the estimate; lambda_min = nothing: lambda_max / eig_ratio.
+# eig_method = :power (default) or :lanczos (gmg_set_chebyshev_eig_method): eig_steps steps of CG with preconditioner M from the same
+# start vector, the estimate being the largest eigenvalue of the Lanczos tridiagonal CG builds -- a much better top Ritz value on a
+# clustered spectrum for one more dot per step; what it buys is a robust default interval, not a faster solve.
 # Usable wherever a RichardsonSmoother over the same M is, on one GPU (HipDistributedGMG* do not take it).
 struct ChebyshevSmoother{A}
   M          :: A
@@ -309,8 +315,9 @@ struct ChebyshevSmoother{A}
   eig_ratio  :: Float64
   eig_safety :: Float64
   eig_steps  :: Int
+  eig_method :: Symbol
   function ChebyshevSmoother(M::A; degree::Integer=3, lambda_max=nothing, lambda_min=nothing, eig_ratio::Real=10.0,
-                             eig_safety::Real=1.1, eig_steps::Integer=10) where A
+                             eig_safety::Real=1.1, eig_steps::Integer=10, eig_method::Symbol=:power) where A
     (M isa JacobiLinearSolver || M isa PatchTable) || error("ChebyshevSmoother: M must be JacobiLinearSolver() or a PatchTable")
     degree >= 1 || error("The degree must be a positive integer.")
     (lambda_max === nothing || lambda_max > 0) || error("lambda_max must be a positive real number (or nothing: estimated by the setup).")
@@ -319,8 +326,9 @@ struct ChebyshevSmoother{A}
     eig_ratio > 1 || error("eig_ratio must be greater than 1.")
     eig_safety >= 1 || error("eig_safety must be at least 1.")
     eig_steps >= 1 || error("eig_steps must be a positive integer.")
+    eig_method in (:power, :lanczos) || error("eig_method must be :power or :lanczos.")
     new{A}(M, Int(degree), lambda_max === nothing ? nothing : Float64(lambda_max), lambda_min === nothing ? nothing : Float64(lambda_min),
-           Float64(eig_ratio), Float64(eig_safety), Int(eig_steps))
+           Float64(eig_ratio), Float64(eig_safety), Int(eig_steps), eig_method)
   end
 end
 
@@ -330,17 +338,25 @@ function _set_smoother(h, lev, which, sm::ChebyshevSmoother)
   check(h, ccall((:gmg_set_smoother_chebyshev, libgmgamd), Cint, (Ptr{Cvoid},Cint,Cint,Cint,Float64,Float64,Cint,Float64,Float64),
                  h, lev, which, sm.degree, sm.lambda_min === nothing ? 0.0 : sm.lambda_min, sm.lambda_max === nothing ? 0.0 : sm.lambda_max,
                  sm.eig_steps, sm.eig_ratio, sm.eig_safety))
+  if sm.eig_method !== :power
+    check(h, ccall((:gmg_set_chebyshev_eig_method, libgmgamd), Cint, (Ptr{Cvoid},Cint,Cint,Cint), h, lev, which, GMG_CHEB_EIG_LANCZOS))
+  end
 end
 
 # gmg_get_chebyshev_info: what the setup fixed for the ChebyshevSmoother of a slot (lev is 1-based, which = :pre or :post);
-# lambda_est is NaN where the bounds were given
+# lambda_est is NaN where the bounds were given; eig_steps_done: the steps the estimate took (:power: eig_steps; :lanczos: fewer where
+# the Krylov space was exhausted; 0 where the bounds were given)
 function chebyshev_info(ns::HipGMGNumericalSetup, lev::Integer=1; which::Symbol=:pre)
   deg, steps = Ref(Cint(0)), Ref(Cint(0))
   est, lmin, lmax = Ref(0.0), Ref(0.0), Ref(0.0)
   check(ns.handle, ccall((:gmg_get_chebyshev_info, libgmgamd), Cint,
                          (Ptr{Cvoid},Cint,Cint,Ref{Cint},Ref{Float64},Ref{Float64},Ref{Float64},Ref{Cint}),
                          ns.handle, lev-1, which === :post ? GMG_POST : GMG_PRE, deg, est, lmin, lmax, steps))
-  return (degree=Int(deg[]), lambda_est=est[], lambda_min=lmin[], lambda_max=lmax[], eig_steps=Int(steps[]))
+  meth, done = Ref(Cint(0)), Ref(Cint(0))
+  check(ns.handle, ccall((:gmg_get_chebyshev_eig, libgmgamd), Cint, (Ptr{Cvoid},Cint,Cint,Ref{Cint},Ref{Cint}),
+                         ns.handle, lev-1, which === :post ? GMG_POST : GMG_PRE, meth, done))
+  return (degree=Int(deg[]), lambda_est=est[], lambda_min=lmin[], lambda_max=lmax[], eig_steps=Int(steps[]),
+          eig_method=meth[] == GMG_CHEB_EIG_LANCZOS ? :lanczos : :power, eig_steps_done=Int(done[]))
 end
 
 # the visiting order of a level's Gauss-Seidel sweeps (inert on a level without such a smoother); takes effect at gmg_setup
@@ -501,14 +517,54 @@ end
 # ---------------------------------------------------------------------------------
 # Outer Krylov solvers that keep the whole iteration on the device
 # ---------------------------------------------------------------------------------
-struct HipCGSolver{A} <: Gridap.Algebra.LinearSolver
+# diagnostic = LanczosDiagnostic(maxiter+1) (CGSolvers.jl:19, KrylovUtils.jl:58-81): the device records alpha_k and beta_k of the solve
+# (gmg_cg_set_trace, allocated by numerical_setup); solve! fetches them and replays CGSolvers.jl:87,114-115,128-138 on the host, so
+# that estimate!(diagnostic) is the reference's condition-number estimate of the preconditioned operator.  The reference hits a
+# BoundsError in the iteration that outgrows the diagnostic; here the constructor refuses length(diagnostic.delta) < maxiter.
+struct HipCGSolver{A,D} <: Gridap.Algebra.LinearSolver
   Pl       :: A
   log      :: ConvergenceLog{Float64}
   flexible :: Bool
+  diag     :: D
 end
-function HipCGSolver(Pl::HipGMGLinearSolver; maxiter=1000, atol=1e-12, rtol=1.e-6, flexible=false, verbose=0, name="CG-MI355X")
+function HipCGSolver(Pl::HipGMGLinearSolver; maxiter=1000, atol=1e-12, rtol=1.e-6, diagnostic=nothing, flexible=false, verbose=0, name="CG-MI355X")
   tols = SolverTolerances{Float64}(;maxiter=maxiter,atol=atol,rtol=rtol)     # CGSolvers.jl:19-23
-  return HipCGSolver(Pl, ConvergenceLog(name,tols;verbose=verbose), flexible)
+  (diagnostic === nothing || diagnostic isa LanczosDiagnostic) || error("diagnostic must be a LanczosDiagnostic (or nothing)")
+  (diagnostic === nothing || length(diagnostic.delta) >= maxiter) ||
+    error("the LanczosDiagnostic holds $(length(diagnostic.delta)) iterations, the solver may take $maxiter")
+  return HipCGSolver(Pl, ConvergenceLog(name,tols;verbose=verbose), flexible, diagnostic)
+end
+
+# gmg_cg_set_trace / gmg_cg_get_trace: alpha_k, beta_k of the outermost CG of gmg_cg_solve (capacity 0: off, buffer released)
+cg_set_trace!(h::Ptr{Cvoid}, capacity::Integer) = check(h, ccall((:gmg_cg_set_trace, libgmgamd), Cint, (Ptr{Cvoid},Cint), h, capacity))
+function cg_trace(h::Ptr{Cvoid})
+  k = Ref(Cint(0))
+  check(h, ccall((:gmg_cg_get_trace, libgmgamd), Cint, (Ptr{Cvoid},Ref{Cint},Ptr{Float64},Ptr{Float64},Cint), h, k, C_NULL, C_NULL, 0))
+  α, β = zeros(Int(k[])), zeros(Int(k[]))
+  GC.@preserve α β begin
+    check(h, ccall((:gmg_cg_get_trace, libgmgamd), Cint, (Ptr{Cvoid},Ref{Cint},Ptr{Float64},Ptr{Float64},Cint), h, k, α, β, length(α)))
+  end
+  return α, β
+end
+
+# what solve! does to the diagnostic (CGSolvers.jl:87,114-115,128-138) for the recorded scalars, in the reference's order of operations.
+# VERBATIM the reference: the off-diagonal is sqrt(beta_k)/alpha_k where the textbook Lanczos matrix has sqrt(beta_k)/alpha_{k-1}.
+# A negative beta_k (flexible = true or an indefinite Pl only) stores NaN where the reference's sqrt would throw.
+function _replay_diagnostic!(x::LanczosDiagnostic, α::Vector{Float64}, β::Vector{Float64})
+  GridapSolvers.SolverInterfaces.reset!(x)                                   # :87
+  α_last = 1.0                                                               # :83
+  for (αk, βk) in zip(α, β)
+    if iszero(x.k[])                                                         # :130-132
+      δ = 1.0 / αk
+      γ = 0.0
+    else                                                                     # :134-135
+      δ = (1.0 / αk) + (βk / α_last)
+      γ = (βk >= 0 ? sqrt(βk) : NaN) / αk
+    end
+    GridapSolvers.SolverInterfaces.update!(x, δ, γ)                          # :137
+    α_last = αk                                                              # :115
+  end
+  return x
 end
 
 struct HipFGMRESSolver{A} <: Gridap.Algebra.LinearSolver
@@ -581,6 +637,9 @@ function Gridap.Algebra.numerical_setup(ss::HipKrylovSymbolicSetup, A::AbstractM
   # (GMRES: one handle holds Pr and Pl, GMRESSolvers.jl:96-97)
   P = ss.solver isa HipGMRESSolver ? ss.solver.gmg : ss.solver isa HipFGMRESSolver ? ss.solver.Pr : ss.solver.Pl
   P_ns = numerical_setup(symbolic_setup(P,A),A)                              # CGSolvers.jl:52
+  if ss.solver isa HipCGSolver && ss.solver.diag !== nothing                 # the allocation happens here, never in a solve
+    cg_set_trace!(P_ns.handle, max(length(ss.solver.diag.delta), 1))
+  end
   return HipKrylovNumericalSetup(ss.solver, P_ns)
 end
 function Gridap.Algebra.numerical_setup!(ns::HipKrylovNumericalSetup, A::AbstractMatrix)
@@ -600,6 +659,7 @@ function Gridap.Algebra.solve!(x::Vector{Float64}, ns::HipKrylovNumericalSetup{<
       h, b, x, GMG_MEM_HOST, tols.maxiter, tols.atol, tols.rtol, s.flexible ? 1 : 0, 1, res, hist, length(hist)))
   end
   _fill_log!(s.log, res[], hist)
+  s.diag === nothing || _replay_diagnostic!(s.diag, cg_trace(h)...)
   return x
 end
 
