@@ -1,6 +1,6 @@
 // cheb.inc.hpp -- ChebyshevSmoother(M, degree) over the preconditioner M of a smoother slot, M in {JacobiLinearSolver, PatchSolver,
 // BlockJacobiSolver} (included at the end of gmg_amd.hip).  The reference has no such smoother: like the Gauss-Seidel orderings it is an
-// addition of the device library next to the reference's types, on one GPU.
+// addition of the device library next to the reference's types, on one GPU and on partitioned handles (SEVERAL RANKS below).
 //
 // One pass of degree m on (x, r) is Saad, Iterative Methods, Alg. 12.1 in the residual form of the smoothers here, with
 // z = M^-1 r the un-relaxed preconditioner of the slot (what gmg_precond_apply returns):
@@ -50,8 +50,31 @@
 // Each sweep is followed by the level's apply_A_sub (r -= A d).  d lives in L.dx, z of the operator form in the level's residual
 // buffer the pass does not use: no new device buffer.
 //
-// REFUSED: Gauss-Seidel slots (GMG_ERR_UNSUPPORTED at gmg_set_smoother_chebyshev), handles with a communicator (GMG_ERR_UNSUPPORTED at
-// gmg_setup).  The pass-level shortcuts of the Richardson-Jacobi passes (fold_level, emits_s0, smooth_persistent, r_dead) do not apply.
+// SEVERAL RANKS.  A Chebyshev slot runs on the own | ghost levels (gmg_set_partition) and on the replicated levels of a handle with a
+// communicator, real or loopback; a handle without one keeps its kernels, launches and bits.  On an own | ghost level recurrence,
+// coefficients and roundings are those above on the n_own owned rows.  Jacobi M: the update is pointwise and rank-local.  Patch M, in
+// the order RichardsonSmoother(PatchSolver) uses there: consistent!(r) (exchange), the patch solves, the gather over ALL local dofs
+// into z, assemble!(z) (assemble_add), the pointwise update on the owned rows -- always the contribution-buffer form, which is what the
+// Richardson pass takes on such a level; z lives in the residual buffer the pass does not use.  r -= A d is apply_A_sub: it exchanges d
+// and fixes up the boundary rows.  r lives in a buffer of the level before anything is exchanged, never in a caller's vector.
+//   cheb_update_pack_kernel<FIRST, DINV>   cheb_update_kernel AND the pack of d's send entries in one launch (option cheb_pack_fused,
+//                                     default 1), on levels whose pack can fuse (can_fuse_pack: every sent row is a boundary row).  The
+//                                     level's row -> boundary-row index table (Level::bidx, -1 off the boundary) leads the lane that
+//                                     updates row i to the row's send slots (d_pk_ptr / d_pk_slot), and that lane stores the value it has
+//                                     just written to d[i]: no lane reads a d another lane is writing.  Plain vector stores; apply_A_sub
+//                                     then runs prepacked and the halo_pack_kernel launch of every sweep is gone.  Same bits either way;
+//                                     where the pack cannot fuse the unfused form runs whatever the option says.
+// The estimates are unchanged in form: the mat-vec is apply_A_set (with its exchange), M^-1 as in the pass, dot / norm all-reduced over
+// the ranks, so the Lanczos stops and the GMG_ERR_SINGULAR decisions are taken on reduced scalars by all ranks together.  On replicated
+// levels the reductions stay local and every rank gets the same estimate.  The start vector is the formula above with i the 0-based
+// index of the row among THE HANDLE'S OWN ROWS, normalised in the global norm: on a folded (loopback) handle that is the stacked index
+// and the estimate is the single-GPU estimate of the folded matrix; between true ranks the vector, and therefore lambda_est after a few
+// steps, DEPENDS ON THE PARTITION (gmg_get_chebyshev_info reports the value).
+//
+// REFUSED: Gauss-Seidel slots (GMG_ERR_UNSUPPORTED at gmg_set_smoother_chebyshev).  At gmg_setup, GMG_ERR_UNSUPPORTED naming the level:
+// the overlapping layout (gmg_set_partition_overlap), levels of a redistributed rank subset (gmg_set_redistribution), and a handle that has a
+// communicator but no declared layout (gmg_set_replication never called).  The pass-level shortcuts of the Richardson-Jacobi passes
+// (fold_level, emits_s0, smooth_persistent, r_dead) do not apply.
 
 namespace {
 
@@ -99,6 +122,61 @@ __global__ void cheb_update_kernel(int64_t n, double a, double b, const double *
     const double out = cheb_step<FIRST, DINV>(a, b, DINV ? dinv[i] : 1.0, z[i], FIRST ? 0.0 : d[i]);
     d[i] = out;
     x[i] = x_zero ? out : __dadd_rn(x[i], out);
+  }
+}
+
+// the send slots pk_slot[pk_ptr[q] .. pk_ptr[q + 1]) of boundary row q take the value the lane has just written to d (every slot is
+// below the length of sendbuf: gmg_setup)
+__device__ __forceinline__ void cheb_pack_row(int32_t q, double v, const int64_t *__restrict__ pk_ptr, const int32_t *__restrict__ pk_slot,
+                                              double *__restrict__ sendbuf)
+{
+  if (q >= 0)
+    for (int64_t k = pk_ptr[q]; k < pk_ptr[q + 1]; ++k) sendbuf[pk_slot[k]] = v;
+}
+
+// cheb_update_kernel on an own | ghost level whose pack can fuse + the pack of d's send entries: the lane of row i stores the value it
+// wrote to d[i] into the row's send slots, q = bidx[i].  Same body, same roundings; bidx (an allocation of its own) is read in pairs
+// next to the 16-byte accesses.
+template <bool FIRST, bool DINV>
+__global__ void cheb_update_pack_kernel(int64_t n, double a, double b, const double *__restrict__ dinv, const double *__restrict__ z,
+                                        double *__restrict__ d, double *__restrict__ x, int x_zero, int vec,
+                                        const int32_t *__restrict__ bidx, const int64_t *__restrict__ pk_ptr,
+                                        const int32_t *__restrict__ pk_slot, double *__restrict__ sendbuf)
+{
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+  int64_t done = 0;
+  if (vec) {
+    const int64_t n2 = n >> 1;
+    const cheb_d2 *z2 = reinterpret_cast<const cheb_d2 *>(z), *q2 = reinterpret_cast<const cheb_d2 *>(dinv);
+    cheb_d2 *d2 = reinterpret_cast<cheb_d2 *>(d), *x2 = reinterpret_cast<cheb_d2 *>(x);
+    const int2 *b2 = reinterpret_cast<const int2 *>(bidx);
+    for (int64_t i = tid; i < n2; i += nth) {
+      const cheb_d2 zz = z2[i];
+      const int2 bq = b2[i];
+      cheb_d2 qq = {1.0, 1.0}, dd = {0.0, 0.0};
+      if (DINV) qq = q2[i];
+      if (!FIRST) dd = d2[i];
+      cheb_d2 out;
+      out.x = cheb_step<FIRST, DINV>(a, b, qq.x, zz.x, dd.x);
+      out.y = cheb_step<FIRST, DINV>(a, b, qq.y, zz.y, dd.y);
+      d2[i] = out;
+      if (x_zero) x2[i] = out;
+      else {
+        cheb_d2 xx = x2[i];
+        xx.x = __dadd_rn(xx.x, out.x);
+        xx.y = __dadd_rn(xx.y, out.y);
+        x2[i] = xx;
+      }
+      cheb_pack_row(bq.x, out.x, pk_ptr, pk_slot, sendbuf);
+      cheb_pack_row(bq.y, out.y, pk_ptr, pk_slot, sendbuf);
+    }
+    done = n2 * 2;
+  }
+  for (int64_t i = done + tid; i < n; i += nth) {
+    const double out = cheb_step<FIRST, DINV>(a, b, DINV ? dinv[i] : 1.0, z[i], FIRST ? 0.0 : d[i]);
+    d[i] = out;
+    x[i] = x_zero ? out : __dadd_rn(x[i], out);
+    cheb_pack_row(bidx[i], out, pk_ptr, pk_slot, sendbuf);
   }
 }
 
@@ -172,14 +250,18 @@ bool cheb_same_M(const Smoother &p, const Smoother &q)
 
 } // namespace
 
-// z = M^-1 r, the un-relaxed preconditioner of the slot
-void gmg_solver::cheb_precond(Level &L, Smoother &S, const double *r, double *z)
+// z = M^-1 r, the un-relaxed preconditioner of the slot.  Patch M on an own | ghost level: consistent!(r) first (r and z are vectors of
+// the level, with ghost room), then the local solves and assemble!(z) inside patch_precond
+void gmg_solver::cheb_precond(int l, Smoother &S, double *r, double *z)
 {
+  Level &L = lev[l];
   if (S.kind == SM_JACOBI) {
     hipLaunchKernelGGL(jacobi_apply_kernel, dim3(grid_for(L.n)), dim3(256), 0, stream, L.n, L.dinv, r, z);
     HIP_CHECK(hipGetLastError());
-  } else
+  } else {
+    if (comm.nranks > 1 && L.halo.present && !L.halo.ovl) exchange(l, r);
     patch_precond(L, S, r, 1.0, false, z, nullptr);
+  }
 }
 
 // GMG_CHEB_EIG_LANCZOS: eig_steps steps of CG on A with preconditioner M from the normalised start vector, driven from the host (a fetch
@@ -200,7 +282,7 @@ double gmg_solver::cheb_lanczos(int l, Smoother &S, const std::string &where)
   std::vector<double> al, be;
   double gamma_old = 1.0, gamma0 = 0.0;
   for (int k = 0; k < S.cheb_eig_steps; ++k) {
-    cheb_precond(L, S, r, z);
+    cheb_precond(l, S, r, z);
     const double gamma = dot(n, z, r);
     if (!(std::isfinite(gamma) && gamma > 0.0)) break;
     if (k == 0) gamma0 = gamma;
@@ -242,6 +324,9 @@ void gmg_solver::cheb_setup(int l, Smoother &S, const Smoother *same_M)
     S.cheb_lmax = S.cheb_lmax_in;
     S.cheb_steps_done = 0;
   } else {
+    // a replicated level of a handle with several ranks: every rank holds the whole vectors, the reductions of the estimate stay local
+    struct Local { bool &flag; bool saved; ~Local() { flag = saved; } } local{reduce_local, reduce_local};
+    if (comm.nranks > 1 && rep_from >= 0 && l >= rep_from) reduce_local = true;
     if (same_M && same_M->cheb && !(same_M->cheb_lmax_in > 0.0) && same_M->cheb_eig_steps == S.cheb_eig_steps &&
         same_M->cheb_eig_method == S.cheb_eig_method && cheb_same_M(*same_M, S)) {
       S.cheb_lest = same_M->cheb_lest;
@@ -261,7 +346,7 @@ void gmg_solver::cheb_setup(int l, Smoother &S, const Smoother *same_M)
         hipLaunchKernelGGL(cheb_div_kernel, dim3(grid_for(n)), dim3(256), 0, stream, n, s == 0 ? v : w, lam, v);   // (s == 0: the start vector, normalised)
         HIP_CHECK(hipGetLastError());
         apply_A_set(l, v, t);
-        cheb_precond(L, S, t, w);
+        cheb_precond(l, S, t, w);
         lam = norm(n, w);
       }
       S.cheb_lest = lam;
@@ -286,13 +371,50 @@ double *gmg_solver::cheb_pass(int l, Smoother &S, double *x, const double *r_in,
   else { r = L.rbuf[0]; copy(r, r_in, n); }
   double *d = L.dx;
   double *zbuf = (r == L.rbuf[0]) ? L.rbuf[1] : L.rbuf[0];   // z = M r of the operator form: the residual buffer this pass does not use
-  const bool contrib_form = S.kind == SM_PATCH && !S.use_M;
+  // own | ghost level of several ranks: patch M is consistent!(r), local solves, gather over all local dofs, assemble!(z) -- then the
+  // pointwise update on the owned rows; where the pack can fuse, the update also fills the send buffer of d's exchange
+  const bool dist = comm.nranks > 1 && L.halo.present && !L.halo.ovl;
+  const bool contrib_form = S.kind == SM_PATCH && !S.use_M && !dist;
+  const bool pack = dist && can_fuse_pack(l) && L.bidx != nullptr && opt_int("GMG_CHEB_PACK_FUSED", 1) != 0;
+  // launches of one sweep on such a level, for the profiled level's count (gmg_get_kernel_stats)
+  int sweep_launches = 0;
+  if (dist) {
+    const HaloPlan &H = L.halo;
+    const int pack_launch = H.nsend() > 0 && !H.nbr.empty() ? 1 : 0;
+    sweep_launches = 1 + (pack ? 0 : pack_launch) + 1 + (L.split && L.nbnd > 0 ? 1 : 0);   // update, pack of d, own columns, boundary fix-up
+    if (S.kind == SM_PATCH) {
+      sweep_launches += pack_launch + (S.npatch > 0 ? 1 : 0) + 1;                          // pack of r, patch solves, gather
+      for (size_t k = 0; k < H.nbr.size(); ++k) sweep_launches += H.snd_ptr[k + 1] > H.snd_ptr[k] ? 1 : 0;   // assemble!: one add per neighbour
+    }
+  }
   const auto aligned16 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
   for (int k = 0; k < S.cheb_degree; ++k) {
     const bool first = k == 0;
     const double a = S.cheb_a[(size_t)k], b = S.cheb_b[(size_t)k];
     const int xz = (x_zero && first) ? 1 : 0;
-    if (contrib_form) {
+    const bool prof = dist && (l == prof_level) && prof_used + 2 <= prof_ev.size();
+    if (prof) HIP_CHECK(hipEventRecord(prof_ev[prof_used], stream));
+    if (dist) {
+      const bool jac = S.kind == SM_JACOBI;
+      const double *z = r;
+      if (!jac) { cheb_precond(l, S, r, zbuf); z = zbuf; }
+      const double *q = jac ? L.dinv : nullptr;
+      const int vec = ((!jac || aligned16(q)) && aligned16(z) && aligned16(d) && aligned16(x)) ? 1 : 0;
+      const int grid = grid_for(vec ? (n + 1) / 2 : n);
+      if (pack) {
+        const HaloPlan &H = L.halo;
+#define CHEB_PACK_LAUNCH(F, D) hipLaunchKernelGGL((cheb_update_pack_kernel<F, D>), dim3(grid), dim3(256), 0, stream, n, a, b, q, z, d, x, xz, vec, \
+                                                  L.bidx, H.d_pk_ptr, H.d_pk_slot, H.d_sendbuf)
+        if (first) { if (jac) CHEB_PACK_LAUNCH(true, true); else CHEB_PACK_LAUNCH(true, false); }
+        else { if (jac) CHEB_PACK_LAUNCH(false, true); else CHEB_PACK_LAUNCH(false, false); }
+#undef CHEB_PACK_LAUNCH
+      } else {
+#define CHEB_LAUNCH(F, D) hipLaunchKernelGGL((cheb_update_kernel<F, D>), dim3(grid), dim3(256), 0, stream, n, a, b, q, z, d, x, xz, vec)
+        if (first) { if (jac) CHEB_LAUNCH(true, true); else CHEB_LAUNCH(true, false); }
+        else { if (jac) CHEB_LAUNCH(false, true); else CHEB_LAUNCH(false, false); }
+#undef CHEB_LAUNCH
+      }
+    } else if (contrib_form) {
       patch_contrib(S, r);
       const int grid = (int)std::max<int64_t>(1, (n + 255) / 256);
       if (S.d_isoff) {
@@ -315,7 +437,13 @@ double *gmg_solver::cheb_pass(int l, Smoother &S, double *x, const double *r_in,
       else hipLaunchKernelGGL((cheb_update_kernel<false, true>), dim3(grid), dim3(256), 0, stream, n, a, b, L.dinv, r, d, x, xz, vec);
     }
     HIP_CHECK(hipGetLastError());
-    apply_A_sub(l, d, r);
+    apply_A_sub(l, d, r, nullptr, pack);                     // (the distributed product: exchanges d, prepacked where the update packed it)
+    if (prof) {
+      HIP_CHECK(hipEventRecord(prof_ev[prof_used + 1], stream));
+      prof_w[prof_used / 2] = sweep_launches;
+      prof_xm[prof_used / 2] = -1;
+      prof_used += 2;
+    }
   }
   return r;
 }

@@ -494,6 +494,9 @@ struct Level {
   double *gh_dict = nullptr;
   int64_t gh_nent = 0;              // ghost entries of the boundary rows; gh_ndict: GhostFix::ndict of the sliced form (gmg_get_halo_info)
   int gh_ndict = 0;
+  // own | ghost level whose pack can fuse, with a Gauss-Seidel or a Chebyshev slot: index of row i among the boundary rows (the rows
+  // with a ghost column, in the order gh_rows lists them), -1 for the others -- gs_update_pack_kernel / cheb_update_pack_kernel
+  int32_t *bidx = nullptr;
   // the restriction of an own | ghost level split the same way (round 5): R keeps the own columns -- and with them a row-pattern
   // layout -- and runs while consistent!(r) is in flight, the ghost columns of the coarse rows next to the box faces are added afterwards
   bool r_split = false;
@@ -3231,7 +3234,7 @@ struct gmg_solver {
   void gs_solve(Level &L, int dir, const double *r, double *dx, int xmode = 0, double *x = nullptr);
   void gs_pass(int l, Smoother &S, double *x, double *r, bool x_zero);
   // Chebyshev smoother (cheb.inc.hpp)
-  void cheb_precond(Level &L, Smoother &S, const double *r, double *z);
+  void cheb_precond(int l, Smoother &S, double *r, double *z);
   void cheb_setup(int l, Smoother &S, const Smoother *same_M);
   double cheb_lanczos(int l, Smoother &S, const std::string &where);
   double *cheb_pass(int l, Smoother &S, double *x, const double *r_in, bool x_zero);
@@ -6019,11 +6022,17 @@ void gmg_solver::setup()
     REQUIRE(!(comm.nranks > 1 && lev[l].halo.present && lev[l].halo.ovl) || (lev[l].pre.kind != SM_GAUSS_SEIDEL && lev[l].post.kind != SM_GAUSS_SEIDEL),
             GMG_ERR_UNSUPPORTED, "Gauss-Seidel smoother on level " + std::to_string(l) + ": the overlapping layout (gmg_set_partition_overlap) is not "
             "supported, rank-block sweeps need the own | ghost layout (gmg_set_partition)");
-  // Chebyshev slots run on one GPU only so far: the estimate and the passes know no halo
-  for (int l = 0; l < nlev - 1; ++l)
-    REQUIRE(comm.kind == COMM_NONE || !(lev[l].pre.cheb || (lev[l].post_shares_pre ? lev[l].pre : lev[l].post).cheb), GMG_ERR_UNSUPPORTED,
-            "Chebyshev smoother on level " + std::to_string(l) + ": handles with a communicator (gmg_comm_init_*) are not supported, the "
-            "Chebyshev smoother runs on one GPU only (partitioned levels are not implemented)");
+  // Chebyshev slots on a handle with a communicator (cheb.inc.hpp): own | ghost levels and replicated levels of a declared layout
+  for (int l = 0; l < nlev - 1; ++l) {
+    if (comm.kind == COMM_NONE || !(lev[l].pre.cheb || (lev[l].post_shares_pre ? lev[l].pre : lev[l].post).cheb)) continue;
+    const std::string where = "Chebyshev smoother on level " + std::to_string(l) + ": ";
+    REQUIRE(rep_from >= 0, GMG_ERR_UNSUPPORTED, where + "the handle has a communicator (gmg_comm_init_*) but no layout (gmg_set_replication "
+            "was never called): the spectrum estimate has no rule for which of its reductions cross the ranks");
+    REQUIRE(!(lev[l].halo.present && lev[l].halo.ovl), GMG_ERR_UNSUPPORTED, where + "the overlapping layout (gmg_set_partition_overlap) is not "
+            "supported, the passes and the estimate need the own | ghost layout (gmg_set_partition)");
+    REQUIRE(!(redist.present && l >= sub_from && l < rep_from), GMG_ERR_UNSUPPORTED, where + "a level of a redistributed rank subset "
+            "(gmg_set_redistribution) is not supported, its reductions would need a communicator of the subset");
+  }
   // patch smoothers / patch corrections with patches of more than 64 dofs take their blocks from the level's CSR (one thread block
   // per patch): a level kept in row-pattern form only gets its rows back
   for (int l = 0; l < nlev - 1; ++l) {
@@ -6182,6 +6191,7 @@ void gmg_solver::setup()
         HaloPlan &Hp = L.halo;
         std::vector<int32_t> bidx((size_t)L.n, -1);
         for (size_t q = 0; q < brows.size(); ++q) bidx[brows[q]] = (int32_t)q;
+        L.bidx = nullptr;
         bool ok = halo_fuse_pack != 0 && Hp.nsend() < (int64_t)INT32_MAX;
         std::vector<int64_t> pkp(brows.size() + 1, 0);
         for (int64_t sidx = 0; sidx < Hp.nsend() && ok; ++sidx) {
@@ -6196,6 +6206,11 @@ void gmg_solver::setup()
           for (int64_t sidx = 0; sidx < Hp.nsend(); ++sidx) slot[(size_t)fill[bidx[Hp.h_snd_idx[sidx]]]++] = (int32_t)sidx;
           Hp.d_pk_ptr = upload(pkp);
           Hp.d_pk_slot = upload(slot);
+          // the update kernels of Gauss-Seidel and Chebyshev slots find a row's send slots through its boundary-row index
+          bool wanted = false;
+          if (l < nlev - 1)
+            for (const Smoother *sp : {&L.pre, L.post_shares_pre ? &L.pre : &L.post}) wanted = wanted || sp->kind == SM_GAUSS_SEIDEL || sp->cheb;
+          if (wanted) L.bidx = upload(bidx);
         } else { Hp.d_pk_ptr = nullptr; Hp.d_pk_slot = nullptr; }
         if (timing) std::fprintf(stderr, "[gmg_setup] level %d halo: %lld boundary rows, %lld send slots, pack fused into the fix-up: %s\n", l,
                                  (long long)brows.size(), (long long)Hp.nsend(), Hp.d_pk_ptr ? "yes" : "no");
@@ -7209,7 +7224,7 @@ const OptionKey kOptionKeys[] = {
   {"GMG_PERSIST_SHARED", false}, {"GMG_PROF_STRIDE", true}, {"GMG_REFRESH", true}, {"GMG_SELL", false}, {"GMG_SELL_BLOCK", false},
   {"GMG_SELL_DEFER", false}, {"GMG_SELL_MAXPAD", false}, {"GMG_SELL_UN", false}, {"GMG_SETUP_TIMING", true}, {"GMG_VDICT", false},
   {"GMG_XCD_REMAP", false}, {"GMG_XCD_REMAP_BIG", false}, {"GMG_X0_ZERO", true}, {"GMG_HOST_POLL", true}, {"GMG_HOST_CHUNK_BYTES", true}, {"GMG_PAT_FMA", false}, {"GMG_PAT_R2", false}, {"GMG_RED_FUSED", false}, {"GMG_GMRES_FUSED", true}, {"GMG_FGMRES_FUSED", true}, {"GMG_NULLSPACE_FUSED", true}, {"GMG_PAT_R2MV", false}, {"GMG_PAT_R2_OCC", false}, {"GMG_PAT_PAIR_P", false}, {"GMG_PAT_R2MV_DOT", false}, {"GMG_PERSIST_WPB", false}, {"GMG_HOST_TIMELINE", true}, {"GMG_PAT_R2MV_MIN", false}, {"GMG_PAT_BCAST", false}, {"GMG_PAT_R2_WGS", false}, {"GMG_PAT_ZWALK", false}, {"GMG_PAT_ZWALK_T", false}, {"GMG_PAT_ZWALK_ROWS", false}, {"GMG_PAT_ZWALK_MV", false}, {"GMG_PAT_ZWALK_WIDE", false}, {"GMG_PAT_ZWALK_WIDE_ROWS", false}, {"GMG_PAT_FUSE2", false}, {"GMG_PAT_FUSE2_W", false}, {"GMG_PAT_FUSE2_T", false}, {"GMG_PAT_FUSE2_ROWS", false}, {"GMG_PAT_FUSE2_BOX", false}, {"GMG_PAT_BOX", false}, {"GMG_PAT_WIDE_GRID", false}, {"GMG_PAT_BOX_T", false}, {"GMG_PAT_BOX_MIN_ROWS", false}, {"GMG_PAT_BOX_MAX_ROWS", false},
-  {"GMG_PERSIST_FORCE_TIMEOUT", true}, {"GMG_PAT_XNEXT", false}, {"GMG_PAT_CLOSE", false}, {"GMG_CG_SPLIT", true}, {"GMG_GS_WIDE", true}, {"GMG_GS_PACK_FUSED", true},
+  {"GMG_PERSIST_FORCE_TIMEOUT", true}, {"GMG_PAT_XNEXT", false}, {"GMG_PAT_CLOSE", false}, {"GMG_CG_SPLIT", true}, {"GMG_GS_WIDE", true}, {"GMG_GS_PACK_FUSED", true}, {"GMG_CHEB_PACK_FUSED", true},
 };
 // "pat_tile", "PAT_TILE" and "GMG_PAT_TILE" name the same option
 const OptionKey *find_option(const char *key)

@@ -42,7 +42,7 @@
 // reference with one part at that level); the overlapping layout is refused at gmg_setup.
 //   gs_update_pack_kernel  dx .= w dx ; x .+= dx AND the pack of dx's send entries in one launch (option gs_pack_fused, default 1), on
 //                   levels whose pack can fuse (can_fuse_pack: every sent row is a boundary row).  THE CHOICE: a row -> boundary-row
-//                   index table of the level (GsLevel::bidx, -1 off the boundary) leads the lane that updates row i to the row's
+//                   index table of the level (Level::bidx, -1 off the boundary) leads the lane that updates row i to the row's
 //                   send slots (the level's d_pk_ptr / d_pk_slot), and that lane stores the value it has just written to dx[i]:
 //                   nobody reads dx[i] while another lane scales it.  Same roundings as gs_update_kernel.  Where the x update folds
 //                   into gs_wide_kernel there is no update launch and the pack stays halo_pack_kernel.
@@ -74,7 +74,6 @@ struct GsLevel {
   int order_kind = GMG_GS_ORDER_NATURAL;
   int64_t ncolors = 0;
   std::vector<int32_t> order;
-  int32_t *bidx = nullptr;   // own | ghost level: index of row i among the boundary rows (rows with a ghost column), -1 for the others
 };
 
 // rows of sets [s0, s1): dx[i] = (r[i] - sum_j a_ij dx[j]) / a_ii over the strict triangle in table order
@@ -405,18 +404,8 @@ void gmg_solver::build_gs(int l, bool values_only)
               std::to_string(std::min<int64_t>((int64_t)L.gs_order.size(), An.nrows)) + ")");
       G.order = L.gs_order;
     }
-    if (own_ghost && L.halo.d_pk_ptr) {                       // row -> boundary-row index, in the order gmg_setup numbers the boundary rows
-      const HostCSR &W = L.sA ? expanded : L.hA;
-      std::vector<int32_t> bidx((size_t)L.n, -1);
-      int32_t q = 0;
-      for (int64_t i = 0; i < L.n; ++i) {
-        bool any = false;
-        for (int64_t k = W.ptr[(size_t)i]; k < W.ptr[(size_t)i + 1] && !any; ++k) any = W.col[(size_t)k] >= L.n;
-        if (any) bidx[(size_t)i] = q++;
-      }
-      REQUIRE((int64_t)q == L.nbnd, GMG_ERR_STATE, "Gauss-Seidel smoother: boundary rows of level " + std::to_string(l) + " do not match the halo split");
-      G.bidx = upload(bidx);
-    }
+    // (the row -> boundary-row index table of gs_update_pack_kernel is the level's: Level::bidx, built with the halo split by gmg_setup)
+    REQUIRE(!(own_ghost && L.halo.d_pk_ptr) || L.bidx != nullptr, GMG_ERR_STATE, "Gauss-Seidel smoother: no boundary-row index table on level " + std::to_string(l));
   }
   REQUIRE(L.gs != nullptr, GMG_ERR_STATE, "Gauss-Seidel smoother: value refresh without a schedule");
   const std::vector<int32_t> &order = L.gs->order;
@@ -492,11 +481,11 @@ void gmg_solver::gs_pass(int l, Smoother &S, double *x, double *r, bool x_zero)
       const bool prof = (l == prof_level) && prof_used + 2 <= prof_ev.size();
       if (prof) HIP_CHECK(hipEventRecord(prof_ev[prof_used], stream));
       // own | ghost level whose pack can fuse: the update launch also fills the send buffer of dx's exchange (gs_update_pack_kernel)
-      const bool pack = !fold && can_fuse_pack(l) && L.gs->bidx != nullptr && opt_int("GMG_GS_PACK_FUSED", 1) != 0;
+      const bool pack = !fold && can_fuse_pack(l) && L.bidx != nullptr && opt_int("GMG_GS_PACK_FUSED", 1) != 0;
       gs_solve(L, dir, r, L.dx, fold ? (xz ? 2 : 1) : 0, x);   // :187-188 / :196-197
       if (pack) {
         hipLaunchKernelGGL(gs_update_pack_kernel, dim3(grid_for(n)), dim3(256), 0, stream, n, S.omega, S.omega != 1.0 ? 1 : 0, xz ? 1 : 0, L.dx, x,
-                           L.gs->bidx, L.halo.d_pk_ptr, L.halo.d_pk_slot, L.halo.d_sendbuf);
+                           L.bidx, L.halo.d_pk_ptr, L.halo.d_pk_slot, L.halo.d_sendbuf);
         HIP_CHECK(hipGetLastError());
       } else if (!fold) {
         hipLaunchKernelGGL(gs_update_kernel, dim3(grid_for(n)), dim3(256), 0, stream, n, S.omega, S.omega != 1.0 ? 1 : 0, xz ? 1 : 0, L.dx, x);   // :189-190

@@ -306,7 +306,9 @@ end
 # eig_method = :power (default) or :lanczos (gmg_set_chebyshev_eig_method): eig_steps steps of CG with preconditioner M from the same
 # start vector, the estimate being the largest eigenvalue of the Lanczos tridiagonal CG builds -- a much better top Ritz value on a
 # clustered spectrum for one more dot per step; what it buys is a robust default interval, not a faster solve.
-# Usable wherever a RichardsonSmoother over the same M is, on one GPU (HipDistributedGMG* do not take it).
+# Usable wherever a RichardsonSmoother over the same M is, on one GPU.  The library itself also runs it on the own | ghost and replicated
+# levels of a partitioned handle (gmg_set_smoother_chebyshev, SEVERAL RANKS in include/gmg_amd.h); HipDistributedGMG* of this file do not
+# take it yet -- the Python driver does (DistributedGMG(chebyshev = ...)).
 struct ChebyshevSmoother{A}
   M          :: A
   degree     :: Int

@@ -20,7 +20,7 @@ import time
 import numpy as np
 
 from . import abi, partition as pa, poisson as po
-from .solvers import ConvergenceLog, GaussSeidelSmoother, _vec
+from .solvers import ChebyshevSmoother, ConvergenceLog, GaussSeidelSmoother, JacobiLinearSolver, _vec
 
 
 def rccl_path():
@@ -119,7 +119,7 @@ class DistributedGMG:
                  order=1, niter=10, omega=2.0 / 3.0, mode="preconditioner", cycle_type="v_cycle",
                  gmg_maxiter=1, gmg_atol=1e-14, gmg_rtol=1e-8, local_hierarchy=None, lengths=None, rep_from=None,
                  smoother="jacobi", depth=None, patch_tables=None, pcorr_tables=None, cells_global=None, options=None,
-                 stream_rows=0, finest_depth=0, sub_from=None, sub_ranks=None, gs_orders=None, loopback_rows=None):
+                 stream_rows=0, finest_depth=0, sub_from=None, sub_ranks=None, gs_orders=None, loopback_rows=None, chebyshev=None):
         """smoother = "jacobi": Richardson(Jacobi, niter, omega); "patch": Richardson(PatchSolver, niter, omega) with the
         vertex-star patches OWNED by this rank (partition.local_vertex_star_patches) and caller-assembled patch matrices --
         a rank's local matrix has the owned rows only, so the blocks of patches reaching into ghost dofs come from the
@@ -132,6 +132,12 @@ class DistributedGMG:
         list indexed by level, gs_orders, whose entry l is this rank's permutation of the level's owned rows (None: the smoother's
         ordering; a folded partition takes the permutation of the folded own block; a replicated level one of its global rows).  Needs the own | ghost layout: depth / finest_depth other than None / 0 raise
         ValueError.
+        chebyshev = a mapping of ChebyshevSmoother's keyword arguments (degree, lambda_max, lambda_min, eig_ratio, eig_safety, eig_steps,
+        eig_method; {} = its defaults): ChebyshevSmoother(M, ...) pre and post on every smoothed level over the M that `smoother` names
+        ("jacobi": JacobiLinearSolver, "patch": PatchSolver); niter / omega are then unused.  On the partitioned levels the recurrence
+        runs on the owned rows with the distributed product, on the replicated ones as on one GPU; an estimated lambda_max comes from
+        all-reduced scalars (chebyshev_info).  Needs the own | ghost layout on all ranks: together with a GaussSeidelSmoother, with
+        depth / finest_depth other than None / 0 or with sub_from it raises ValueError.
         local_hierarchy: ready-made local operators (dict like partition.build_local_hierarchy's: levels = objects with A, P, R, n_own,
         n_ghost, nbr_rank, snd_ptr, snd_idx, rcv_ptr, replicated; rep_from; rep_gid) -- e.g. from dpartition for the vector-valued
         Stokes velocity hierarchy; then patch_tables[l] = (patch_ptr, dofs, blocks) supplies the smoother's patches per level
@@ -153,6 +159,15 @@ class DistributedGMG:
         a CSR copy (what a per-rank assembler that produces its rows plane by plane would do)."""
         import torch.distributed as dist
         gs = smoother if isinstance(smoother, GaussSeidelSmoother) else None
+        cheb = None
+        if chebyshev is not None:
+            if gs is not None:
+                raise ValueError("chebyshev goes with smoother = \"jacobi\" or \"patch\": there is no Chebyshev iteration over a Gauss-Seidel smoother")
+            if (depth is not None and np.any(np.asarray(depth) != 0)) or finest_depth:
+                raise ValueError("a Chebyshev smoother needs the own | ghost layout on every partitioned level: depth / finest_depth must be None / 0")
+            if sub_from is not None:
+                raise ValueError("a Chebyshev smoother does not run on the levels of a rank subset: sub_from must be None")
+            cheb = ChebyshevSmoother(JacobiLinearSolver(), **dict(chebyshev))   # (validation only: the errors are the constructor's)
         if gs is not None:
             if (depth is not None and np.any(np.asarray(depth) != 0)) or finest_depth:
                 raise ValueError("a Gauss-Seidel smoother needs the own | ghost layout on every partitioned level: depth / finest_depth must be None / 0")
@@ -272,6 +287,12 @@ class DistributedGMG:
                     self._set_patch_smoother(l, L, niter, omega)
                 else:
                     abi.check(h, lib.gmg_set_smoother_jacobi(h, l, abi.PRE_AND_POST, niter, omega))
+                if cheb is not None:
+                    abi.check(h, lib.gmg_set_smoother_chebyshev(h, l, abi.PRE_AND_POST, cheb.degree, 0.0 if cheb.lambda_min is None else cheb.lambda_min,
+                                                                0.0 if cheb.lambda_max is None else cheb.lambda_max, cheb.eig_steps, cheb.eig_ratio,
+                                                                cheb.eig_safety))
+                    if cheb.eig_method != "power":
+                        abi.check(h, lib.gmg_set_chebyshev_eig_method(h, l, abi.PRE_AND_POST, cheb._EIG_METHODS[cheb.eig_method]))
                 if pcorr_tables is not None and pcorr_tables[l] is not None:
                     pp, pl, G = pcorr_tables[l]
                     pp64, pl64 = np.ascontiguousarray(pp, dtype=np.int64), np.ascontiguousarray(pl, dtype=np.int64)
@@ -492,6 +513,21 @@ class DistributedGMG:
         buf = C.create_string_buffer(256)
         abi.check(self.h, self._lib.gmg_sweep_signature(self.h, lev, buf, 256))
         return buf.value.decode()
+
+    def chebyshev_info(self, level=0, which="pre"):
+        """gmg_get_chebyshev_info / gmg_get_chebyshev_eig of a slot (which = "pre" / "post"), as GMGNumericalSetup.chebyshev_info ->
+        dict(degree, lambda_est (NaN where the bounds were given), lambda_min, lambda_max, eig_steps, eig_method, eig_steps_done).  On a
+        partitioned level lambda_est comes from scalars reduced over the ranks: the same value on every rank, but one that depends on the
+        partition (the start vector is indexed by the rank's own rows)."""
+        if which not in ("pre", "post"):
+            raise ValueError('which must be "pre" or "post"')
+        w = abi.PRE if which == "pre" else abi.POST
+        deg, steps, meth, done = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        v = [C.c_double(0.0) for _ in range(3)]
+        abi.check(self.h, self._lib.gmg_get_chebyshev_info(self.h, level, w, C.byref(deg), C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(steps)))
+        abi.check(self.h, self._lib.gmg_get_chebyshev_eig(self.h, level, w, C.byref(meth), C.byref(done)))
+        return dict(degree=deg.value, lambda_est=v[0].value, lambda_min=v[1].value, lambda_max=v[2].value, eig_steps=steps.value,
+                    eig_method=("power", "lanczos")[meth.value], eig_steps_done=done.value)
 
     def gs_schedule(self, level=0, forward=True):
         """gmg_get_gs_schedule: what the setup of the level's Gauss-Seidel smoother built for one direction, on a partitioned level the

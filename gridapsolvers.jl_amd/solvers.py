@@ -124,7 +124,7 @@ class ChebyshevSmoother:
     """ChebyshevSmoother(M, degree=3, lambda_max=None, lambda_min=None, eig_ratio=10.0, eig_safety=1.1, eig_steps=10,
     eig_method="power"): a Chebyshev
     polynomial of `degree` in M^-1 A where RichardsonSmoother(M, niter, omega) runs niter damped sweeps (gmg_set_smoother_chebyshev).
-    No reference counterpart; one GPU only.
+    No reference counterpart.  On partitioned handles: multigpu.DistributedGMG(..., chebyshev={...}).
 
     lambda_max given: the interval is [lambda_min, lambda_max], lambda_min defaulting to lambda_max / eig_ratio.  Otherwise the setup
     estimates lambda_max(M^-1 A) per level by eig_steps power steps and takes lambda_max = eig_safety * estimate (PETSc's

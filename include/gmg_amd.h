@@ -235,7 +235,8 @@ GMG_API int gmg_gs_multicolor_order(int64_t nrows, const int64_t *ptr, const int
                                     int64_t *ncolors);
 
 /* ChebyshevSmoother(M, degree) over the preconditioner M of a smoother slot, M = JacobiLinearSolver / PatchSolver / BlockJacobiSolver.
- * The reference has no such smoother; it is an addition of this library (like the Gauss-Seidel orderings), on one GPU.
+ * The reference has no such smoother; it is an addition of this library (like the Gauss-Seidel orderings), on one GPU and on the
+ * own | ghost and replicated levels of a partitioned handle (SEVERAL RANKS below).
  * Call it AFTER gmg_set_smoother_jacobi / gmg_set_smoother_patch[_matrices] on the same slot: it turns that slot's Richardson
  * iteration into the Chebyshev one (the slot's niter and omega are then unused).  Setting a plain smoother on the slot again clears it.
  * One pass of degree m on (x, r), with z = M^-1 r the un-relaxed preconditioner (Saad, Alg. 12.1, residual form):
@@ -251,8 +252,19 @@ GMG_API int gmg_gs_multicolor_order(int64_t nrows, const int64_t *ptr, const int
  * matters.  The reference-style defaults of the host layers: degree 3, eig_steps 10, eig_safety 1.1, eig_ratio 10.
  * gmg_update_values[_csc] + gmg_setup estimate again where the bound was not given.
  * Errors: GMG_ERR_STATE if the slot has no smoother yet; GMG_ERR_UNSUPPORTED on a Gauss-Seidel slot; GMG_ERR_INVALID for degree < 1,
- * lambda_min >= lambda_max when both are given, eig_ratio <= 1, eig_safety < 1 or eig_steps < 1.  A handle with a communicator
- * (gmg_comm_init_*) and a Chebyshev slot is refused at gmg_setup with GMG_ERR_UNSUPPORTED.
+ * lambda_min >= lambda_max when both are given, eig_ratio <= 1, eig_safety < 1 or eig_steps < 1.
+ * SEVERAL RANKS (communicator of several ranks, real or loopback).  A Chebyshev slot runs on own | ghost levels (gmg_set_partition) and on
+ * the replicated levels (>= the level of gmg_set_replication).  On an own | ghost level the recurrence runs on the n_own owned rows;
+ * patch M is consistent!(r), the patch solves, the gather over all local dofs, assemble!(z), then the update; r -= A d is the distributed
+ * product with its halo exchange.  Where the level's pack can fuse, the update also fills the send buffer of d's exchange
+ * (cheb_update_pack_kernel; option cheb_pack_fused, same bits).  The estimates use the distributed product and all-reduced dot / norm
+ * (local on replicated levels), so every rank takes the same stops and GMG_ERR_SINGULAR decisions.  The start vector is the formula
+ * above with i the 0-based index of the row among THE HANDLE'S OWN ROWS, normalised in the global norm: a folded (loopback) handle
+ * gets the single-GPU estimate of the folded matrix, while between true ranks the vector -- and therefore lambda_est after a few steps --
+ * DEPENDS ON THE PARTITION (gmg_get_chebyshev_info reports the value; pass lambda_max where that matters).
+ * Refused at gmg_setup with GMG_ERR_UNSUPPORTED, naming the level: a level in the overlapping layout (gmg_set_partition_overlap); a level
+ * of a redistributed rank subset (gmg_set_redistribution); a handle that has a communicator (gmg_comm_init_*) but no declared layout
+ * (gmg_set_replication never called).
  * gmg_smooth runs one pass; gmg_precond_apply on such a slot returns z = M^-1 r, the operator whose spectrum is estimated;
  * gmg_sweep_signature of a level with such a slot ends in " cheb=<pre degree>/<post degree>" (0 for a slot without).  The one-launch
  * passes, folded transfers and the other shortcuts of the Richardson-Jacobi passes do not apply to such a slot. */
@@ -404,6 +416,9 @@ GMG_API int gmg_set_options(gmg_handle_t h, int mode, int cycle, int maxiter, do
  *                    pack of dx's send entries are one launch, gs_update_pack_kernel; 0: gs_update_kernel, then halo_pack_kernel.
  *                    Inert where the update folds into gs_wide_kernel or the pack cannot fuse.  Same bits either way: the A/B
  *                    switch of tools/gs_dist_timing.py)
+ *   Chebyshev        cheb_pack_fused* (1: on an own | ghost level whose pack can fuse, the pointwise update of a Chebyshev sweep and the
+ *                    pack of d's send entries are one launch, cheb_update_pack_kernel; 0: cheb_update_kernel, then halo_pack_kernel.
+ *                    Inert where the pack cannot fuse.  Same bits either way: the A/B switch of tools/chebyshev_dist_timing.py)
  *   coarsest level   coarse_host_max (1500) coarse_host_fallback_max (6000) coarse_auto_cg_min (20000: a dense-inverse request on a
  *                    coarsest level of at least this many dofs is served by the device CG-Jacobi solver instead) gj_mfma (1) gj_wide_min (4096)
  *   patch smoother   patch_dedup (1) patch_source_dedup (1) patch_operator (1)
