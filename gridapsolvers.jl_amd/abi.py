@@ -18,6 +18,8 @@ PATCH_LU, PATCH_NOPIVOT = 0, 1
 GS_SYMMETRIC, GS_FORWARD, GS_BACKWARD = 0, 1, 2
 GS_ORDER_NATURAL, GS_ORDER_MULTICOLOR, GS_ORDER_GIVEN = 0, 1, 2
 CHEB_EIG_POWER, CHEB_EIG_LANCZOS = 0, 1
+PMULT_SYMMETRIC, PMULT_FORWARD, PMULT_BACKWARD = 0, 1, 2
+PATCH_COLORING_GREEDY, PATCH_COLORING_GIVEN = 0, 1
 OP_A, OP_P, OP_R = 0, 1, 2
 LEVEL_KRYLOV = -1          # GMG_LEVEL_KRYLOV: the separate Krylov operator of a finest level in the overlapping layout
 COARSE_DENSE_INVERSE, COARSE_CG_JACOBI, COARSE_HOST_CALLBACK = 0, 1, 2
@@ -87,6 +89,10 @@ SYMBOLS = {
     "gmg_set_gs_ordering": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64],
     "gmg_get_gs_ordering": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.c_void_p, C.c_int64],
     "gmg_gs_multicolor_order": [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)],
+    "gmg_set_smoother_patch_multiplicative": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int],
+    "gmg_set_patch_coloring": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64],
+    "gmg_get_patch_coloring": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_int64],
+    "gmg_patch_multicolor": [C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)],
     "gmg_set_prolongation_patch_correction": [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
                                               C.c_int],
     "gmg_set_prolongation_patch_correction_rhs": [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -470,6 +470,8 @@ int gmg_set_smoother_chebyshev(gmg_handle_t h, int lev, int which, int degree, d
       if (!sp) continue;
       REQUIRE(sp->assigned, GMG_ERR_STATE, "gmg_set_smoother_chebyshev: the slot has no smoother yet (gmg_set_smoother_jacobi / gmg_set_smoother_patch first)");
       REQUIRE(sp->kind != SM_GAUSS_SEIDEL, GMG_ERR_UNSUPPORTED, "gmg_set_smoother_chebyshev: M must be a Jacobi or a patch solver, the slot holds a Gauss-Seidel smoother");
+      REQUIRE(!sp->pmult, GMG_ERR_UNSUPPORTED, "gmg_set_smoother_chebyshev: the slot holds a multiplicative patch smoother (Chebyshev over the "
+              "multiplicative sweep is not supported)");
     }
     // a slot of its own for the side that is changed alone
     if (which != GMG_PRE_AND_POST && L.post_shares_pre) { L.post = L.pre; L.post_shares_pre = false; }

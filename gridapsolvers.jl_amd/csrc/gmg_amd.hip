@@ -224,6 +224,7 @@ struct PatStream {
   std::vector<uint16_t> rowpid;
   std::vector<int32_t> rowbase;
   bool complete() const { return rows_seen == nrows; }
+  bool eager = false;   // made by gmg_set_matrix from a whole CSR (try_eager_pattern), not streamed by the caller: the rows can be had back
 };
 
 // ----------------------------------------------------------------------------
@@ -353,6 +354,8 @@ struct DevCSR {
 
 enum SmootherKind { SM_JACOBI = 0, SM_PATCH = 1, SM_GAUSS_SEIDEL = 2 };
 
+struct PmultTables;                // pmult.inc.hpp
+
 struct Smoother {
   int kind = SM_JACOBI;
   int niter = 10;             // GMGLinearSolvers.jl:52 default RichardsonSmoother(Jacobi,10)
@@ -406,6 +409,14 @@ struct Smoother {
   double cheb_lmin_in = 0.0, cheb_lmax_in = 0.0, cheb_eig_ratio = 0.0, cheb_eig_safety = 0.0;
   double cheb_lest = 0.0, cheb_lmin = 0.0, cheb_lmax = 0.0;
   std::vector<double> cheb_a, cheb_b;   // sweep k: d = cheb_a[k] d + cheb_b[k] z (cheb_a[0] unused: sweep 0 does not read d)
+  // MultiplicativePatchSmoother over this slot's patch blocks (pmult.inc.hpp): the pass is niter coloured block Gauss-Seidel sweeps over
+  // the patches (niter, omega of the slot; pmult_type: which directions) instead of niter additive Richardson sweeps.  The blocks
+  // come from build_patch as for the additive form; neither the incidence lists nor the operator M are built.
+  bool pmult = false;
+  int pmult_type = 0;                   // GMG_PMULT_SYMMETRIC / FORWARD / BACKWARD
+  int pmult_color_kind = 0;             // gmg_set_patch_coloring: 0 greedy, 1 given
+  std::vector<int32_t> pmult_color_in;  // the caller's colouring (kind 1)
+  std::shared_ptr<PmultTables> pm;      // colouring in use + the patches grouped by colour (filled by gmg_setup)
   // every device array above was freed with the handle's allocations
   void reset_device()
   {
@@ -414,6 +425,7 @@ struct Smoother {
     d_ublock = nullptr; d_uboff = nullptr; d_ubinv = nullptr; d_iptr = nullptr; d_inc = nullptr; d_isoff = nullptr; d_isinc = nullptr;
     d_contrib = nullptr;
     n_binv = n_ubinv = n_uboff = 0; dedup = false; nuniq = 0; npatch = 0; built = false;
+    pm.reset();
   }
 };
 
@@ -517,6 +529,7 @@ struct Level {
   double *rcur = nullptr;         // buffer holding the current residual after a cycle
 };
 const char *gs_tag(const Level &L);   // gs.inc.hpp: the directions the level's Gauss-Seidel tables hold (gmg_sweep_signature)
+std::string pmult_tag(const Level &L); // pmult.inc.hpp: directions and colours of the level's multiplicative patch slot(s)
 
 // ConvergenceLog + SolverTolerances (ConvergenceLogs.jl:42-150, SolverTolerances.jl:97-128)
 struct ConvLog {
@@ -942,12 +955,15 @@ struct gmg_solver {
     p = nullptr;
   }
   // a SELL matrix never streams its CSR copy: drop (col,val) once D^-1 / patch blocks are built
-  void drop_csr_stream(DevCSR &M)
+  // keep_rows: the level's multiplicative patch sweeps gather rows of A from the CSR (pmult.inc.hpp)
+  void drop_csr_stream(DevCSR &M, bool keep_rows = false)
   {
     if (!M.sell) return;
     HIP_CHECK(hipStreamSynchronize(stream));
-    release(M.col, (size_t)M.nnz + 4096);
-    release(M.val, (size_t)M.nnz + 4096);
+    if (!keep_rows) {
+      release(M.col, (size_t)M.nnz + 4096);
+      release(M.val, (size_t)M.nnz + 4096);
+    }
     if (M.vdict && M.sval) release(M.sval, (size_t)M.zpad);          // values come from the dictionary
   }
   double *dvec(int64_t n)
@@ -1385,6 +1401,7 @@ struct gmg_solver {
     const int64_t W = (std::max<int64_t>(S->wmax, 1) + un - 1) / un * un;
     const bool generic = (int64_t)(S->len.size() + 1) * (12 * W + 4) <= 48 * 1024;
     if (!generic) return false;                              // wide / many patterns: let the general path pick the layout
+    S->eager = true;
     out = S;
     return true;
   }
@@ -3238,6 +3255,10 @@ struct gmg_solver {
   void cheb_setup(int l, Smoother &S, const Smoother *same_M);
   double cheb_lanczos(int l, Smoother &S, const std::string &where);
   double *cheb_pass(int l, Smoother &S, double *x, const double *r_in, bool x_zero);
+  // MultiplicativePatchSmoother (pmult.inc.hpp)
+  void pmult_check(int l) const;
+  void pmult_setup(int l, Smoother &S);
+  void pmult_pass(int l, Smoother &S, double *x, double *r, bool x_zero);
   void patch_contrib(Smoother &S, const double *r);
 
   // May the transfer T in front of the pass S of level l run as that pass's head?  One rank, a Jacobi pass that runs as one launch
@@ -3598,6 +3619,7 @@ struct gmg_solver {
     if (r_internal) r = const_cast<double *>(r_in);
     else { r = L.rbuf[0]; copy(r, r_in, n); }
     if (S.kind == SM_GAUSS_SEIDEL) { gs_pass(l, S, x, r, x_zero); return r; }   // (the first pass writes x where x_zero holds)
+    if (S.pmult) { pmult_pass(l, S, x, r, x_zero); return r; }                  // (the same)
     if (x_zero) zero(x, n);
     // Overlapping layout (gmg_set_partition_overlap): consistent!(r) once per block of `depth` sweeps; inside a block every local row
     // is swept with the patches of the local box -- no assemble!, no exchange of dx (ghost layers are recomputed redundantly and stay
@@ -5013,7 +5035,7 @@ void gmg_solver::build_patch(Level &L, Smoother &S, bool blocks_only)
   };
   // (built after the blocks, and only when the patch-by-patch kernels will run: the row-pattern form of the additive-Schwarz
   // operator needs none of it, and at 4.6 x 10^8 patch entries the lists take 2.8 s of host time)
-  if (npatch == 0 || max_np == 0) { if (!blocks_only) make_incidence(); S.built = true; return; }
+  if (npatch == 0 || max_np == 0) { if (!blocks_only && !S.pmult) make_incidence(); S.built = true; return; }
 
   // ---- inverse blocks, built in batches (bounded scratch) and de-duplicated on the fly -------------------------------
   // Block sources: caller's lu! factors (inverted on the host exactly as ldiv! would solve against the identity), caller's
@@ -5336,6 +5358,10 @@ void gmg_solver::build_patch(Level &L, Smoother &S, bool blocks_only)
   bp_lap("inverse blocks + de-duplication");
   if (S.dedup) release(S.d_boff, (size_t)npatch + 1);        // the de-duplicated solve addresses blocks through ublock / uboff
   S.built = true;
+  if (S.pmult) {                                             // multiplicative sweeps read the blocks alone: no operator M, no incidence lists
+    S.h_ublock.clear(); S.h_ublock.shrink_to_fit(); S.h_uboff.clear();
+    return;
+  }
   build_patch_operator(L, S);
   S.h_ublock.clear(); S.h_ublock.shrink_to_fit(); S.h_uboff.clear();
   bp_lap("patch operator");
@@ -6033,6 +6059,7 @@ void gmg_solver::setup()
     REQUIRE(!(redist.present && l >= sub_from && l < rep_from), GMG_ERR_UNSUPPORTED, where + "a level of a redistributed rank subset "
             "(gmg_set_redistribution) is not supported, its reductions would need a communicator of the subset");
   }
+  for (int l = 0; l < nlev - 1; ++l) pmult_check(l);         // multiplicative patch slots: what is refused, before anything is built
   // patch smoothers / patch corrections with patches of more than 64 dofs take their blocks from the level's CSR (one thread block
   // per patch): a level kept in row-pattern form only gets its rows back
   for (int l = 0; l < nlev - 1; ++l) {
@@ -6042,7 +6069,10 @@ void gmg_solver::setup()
     for (const Smoother *sp : {&L.pre, &L.post, &L.pcorr})
       if (sp->kind == SM_PATCH && sp->tab && !sp->tab->has_blocks)
         for (size_t q = 0; q + 1 < sp->tab->pptr.size(); ++q) big = std::max(big, sp->tab->pptr[q + 1] - sp->tab->pptr[q]);
-    if (big > 64) rows_from_stream(L);
+    // (so does a level with a multiplicative patch slot, whose sweeps gather rows of A: a matrix that gmg_set_matrix turned into a
+    // stream on its own gets its rows back; one streamed by the caller was refused by pmult_check)
+    const bool pm = L.pre.pmult || (L.post_shares_pre ? L.pre : L.post).pmult;
+    if (big > 64 || pm) rows_from_stream(L);
   }
   if (comm.nranks > 1) {
     // Row-pattern-only operators (streamed with gmg_set_operator_rows, or handed over whole before the communicator was initialised)
@@ -6288,10 +6318,12 @@ void gmg_solver::setup()
       }
       if (L.pre.kind == SM_PATCH) build_patch(L, L.pre);
       if (L.pre.cheb) cheb_setup(l, L.pre, nullptr);         // (spectrum bounds + coefficients; a shared post gets them with the copy)
+      if (L.pre.pmult) pmult_setup(l, L.pre);                // (colouring + the patches grouped by colour; shared with the copy as well)
       if (L.post_shares_pre) L.post = L.pre;
       else {
         if (L.post.kind == SM_PATCH) build_patch(L, L.post);
         if (L.post.cheb) cheb_setup(l, L.post, &L.pre);
+        if (L.post.pmult) pmult_setup(l, L.post);
       }
       if (L.pre.kind == SM_GAUSS_SEIDEL || L.post.kind == SM_GAUSS_SEIDEL) build_gs(l);
       drop_csr_stream(L.P);
@@ -6303,7 +6335,7 @@ void gmg_solver::setup()
       L.dinv = build_inv_diag(L.A, nzero);                  // JacobiLinearSolvers.jl:20-23 on the coarsest matrix
       REQUIRE(nzero == 0, GMG_ERR_SINGULAR, "zero diagonal entry on the coarsest level");
     }
-    drop_csr_stream(L.A);
+    drop_csr_stream(L.A, l < nlev - 1 && (L.pre.pmult || L.post.pmult));
   }
   build_coarse();                                           // :195 gmg_coarse_solver_caches
   lap("coarse inverse", nlev - 1);
@@ -6414,6 +6446,8 @@ void gmg_solver::refill_values(DevCSR &A, const double *hval, double *dinv, Refi
     if (A.ptr64) hipLaunchKernelGGL((sell_refill_kernel<int64_t>), dim3(grid), dim3(256), 0, stream, n, (const int64_t *)A.rowptr, A.soff, A.scol, st.d_val, A.sval, dinv, st.d_nzero);
     else hipLaunchKernelGGL((sell_refill_kernel<int32_t>), dim3(grid), dim3(256), 0, stream, n, (const int32_t *)A.rowptr, A.soff, A.scol, st.d_val, A.sval, dinv, st.d_nzero);
     HIP_CHECK(hipGetLastError());
+    // a level that kept its CSR rows next to the slices (multiplicative patch sweeps, pmult.inc.hpp) gets the new values there too
+    if (A.val) HIP_CHECK(hipMemcpyAsync(A.val, st.d_val, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToDevice, stream));
   }
   lap(st.fill_ms);
 }
@@ -7225,6 +7259,7 @@ const OptionKey kOptionKeys[] = {
   {"GMG_SELL_DEFER", false}, {"GMG_SELL_MAXPAD", false}, {"GMG_SELL_UN", false}, {"GMG_SETUP_TIMING", true}, {"GMG_VDICT", false},
   {"GMG_XCD_REMAP", false}, {"GMG_XCD_REMAP_BIG", false}, {"GMG_X0_ZERO", true}, {"GMG_HOST_POLL", true}, {"GMG_HOST_CHUNK_BYTES", true}, {"GMG_PAT_FMA", false}, {"GMG_PAT_R2", false}, {"GMG_RED_FUSED", false}, {"GMG_GMRES_FUSED", true}, {"GMG_FGMRES_FUSED", true}, {"GMG_NULLSPACE_FUSED", true}, {"GMG_PAT_R2MV", false}, {"GMG_PAT_R2_OCC", false}, {"GMG_PAT_PAIR_P", false}, {"GMG_PAT_R2MV_DOT", false}, {"GMG_PERSIST_WPB", false}, {"GMG_HOST_TIMELINE", true}, {"GMG_PAT_R2MV_MIN", false}, {"GMG_PAT_BCAST", false}, {"GMG_PAT_R2_WGS", false}, {"GMG_PAT_ZWALK", false}, {"GMG_PAT_ZWALK_T", false}, {"GMG_PAT_ZWALK_ROWS", false}, {"GMG_PAT_ZWALK_MV", false}, {"GMG_PAT_ZWALK_WIDE", false}, {"GMG_PAT_ZWALK_WIDE_ROWS", false}, {"GMG_PAT_FUSE2", false}, {"GMG_PAT_FUSE2_W", false}, {"GMG_PAT_FUSE2_T", false}, {"GMG_PAT_FUSE2_ROWS", false}, {"GMG_PAT_FUSE2_BOX", false}, {"GMG_PAT_BOX", false}, {"GMG_PAT_WIDE_GRID", false}, {"GMG_PAT_BOX_T", false}, {"GMG_PAT_BOX_MIN_ROWS", false}, {"GMG_PAT_BOX_MAX_ROWS", false},
   {"GMG_PERSIST_FORCE_TIMEOUT", true}, {"GMG_PAT_XNEXT", false}, {"GMG_PAT_CLOSE", false}, {"GMG_CG_SPLIT", true}, {"GMG_GS_WIDE", true}, {"GMG_GS_PACK_FUSED", true}, {"GMG_CHEB_PACK_FUSED", true},
+  {"GMG_PMULT_ONE_LAUNCH", true}, {"GMG_PMULT_ONE_LAUNCH_MAX", true},
 };
 // "pat_tile", "PAT_TILE" and "GMG_PAT_TILE" name the same option
 const OptionKey *find_option(const char *key)
@@ -7697,6 +7732,11 @@ int gmg_precond_apply(gmg_handle_t h, int lev, int which, const double *r, doubl
       double *rr = h->scratch_vec(2, h->lev[0].nvec);
       h->copy(rr, dr, L.n);
       h->gs_pass(lev, S, out, rr, true);
+    } else if (S.pmult) {
+      // the same for the multiplicative patch smoother: x = 0 on a copy of r, so z = dx of the whole pass
+      double *rr = h->scratch_vec(2, h->lev[0].nvec);
+      h->copy(rr, dr, L.n);
+      h->pmult_pass(lev, S, out, rr, true);
     } else if (h->comm.nranks > 1 && L.halo.present) {
       // solve!(x::PVector, ns::PatchNS, b::PVector), PatchSolvers.jl:227-236: consistent!(b), local solves, assemble!(x)
       double *rr = h->scratch_vec(2, h->lev[0].nvec), *oo = h->scratch_vec(3, h->lev[0].nvec);
@@ -8293,6 +8333,10 @@ int gmg_sweep_signature(gmg_handle_t h, int lev, char *buf, int cap)
       if (len + 1 < (size_t)cap)
         std::snprintf(buf + len, (size_t)cap - len, " cheb=%d/%d", Lc.pre.cheb ? Lc.pre.cheb_degree : 0, Lc.post.cheb ? Lc.post.cheb_degree : 0);
     }
+    if (lev < h->nlev - 1 && (Lc.pre.pmult || Lc.post.pmult)) {   // a level with a multiplicative patch slot: directions / colours
+      const size_t len = std::strlen(buf);
+      if (len + 1 < (size_t)cap) std::snprintf(buf + len, (size_t)cap - len, " pmult=%s", pmult_tag(Lc).c_str());
+    }
   });
 }
 
@@ -8379,3 +8423,4 @@ int gmg_device_bytes(gmg_handle_t h, int64_t *bytes)
 #include "block.inc.hpp"
 #include "gs.inc.hpp"
 #include "cheb.inc.hpp"
+#include "pmult.inc.hpp"

@@ -5385,4 +5385,128 @@ __global__ void patch_gather_sell_cheb_kernel(int64_t n, const int64_t *__restri
   cheb_epilogue<FIRST>(i, s, a, b, x_zero, d, x);
 }
 
+// ---- multiplicative patch smoother (coloured block Gauss-Seidel over the patches, pmult.inc.hpp) -------------------------------
+// One patch p:  t_i = r0[rows_p[i]] - sum_k a(rows_p[i], k) dx[k]  (the row in its stored order, summed from 0.0, every product and
+// every sum rounded);  d_i = sum_j inv(A_pp)[i, j] t_j  (as patch_apply_kernel sums);  dx[rows_p[i]] += omega d_i.
+// The patches of one colour share no dof and no stored entry of A couples a dof of one to a dof of another (validated on the host
+// at gmg_setup), so whatever a patch reads of dx no other patch of its colour writes.  dx is read and written inside one launch: a
+// plain pointer.  Ordering between colours: launch boundaries (patch_mult_kernel, patch_mult_big_kernel) or the workgroup barrier
+// of the single workgroup of patch_mult_pass_kernel.  No kernel waits on another workgroup.
+struct PmultArgs {
+  const int32_t *order;    // the non-empty patches grouped by colour; inside a colour the patches of at most 64 dofs come first
+  const int64_t *pptr;
+  const int32_t *pdofs;
+  const int64_t *boff;     // blocks of the plain store (ublock == nullptr) ...
+  const double *binv;
+  const int32_t *ublock;   // ... or of the de-duplicated one
+  const int64_t *uboff;
+  const double *ubinv;
+  const void *rowptr;      // CSR of the level matrix (PtrT row pointers)
+  const int32_t *col;
+  const double *val;
+  const double *r0;        // the residual the pass started from
+  double omega;
+};
+
+__device__ __forceinline__ const double *pmult_block(const PmultArgs &a, int64_t p)
+{
+  return a.ublock ? a.ubinv + a.uboff[a.ublock[p]] : a.binv + a.boff[p];
+}
+
+template <typename PtrT>
+__device__ __forceinline__ double pmult_fresh_residual(const PmultArgs &a, int32_t row, const double *dx)
+{
+  const PtrT *rp = static_cast<const PtrT *>(a.rowptr);
+  double s = 0.0;
+  for (PtrT k = rp[row]; k < rp[row + 1]; ++k) s = __dadd_rn(s, __dmul_rn(a.val[k], dx[a.col[k]]));
+  return __dsub_rn(a.r0[row], s);
+}
+
+// one wave, one patch of 1 .. 64 dofs; st: 64 doubles of LDS owned by the wave.  np is wave-uniform.
+template <typename PtrT>
+__device__ __forceinline__ void pmult_wave_patch(const PmultArgs &a, int64_t p, int lane, double *st, double *dx)
+{
+  const int64_t q0 = a.pptr[p];
+  const int np = (int)(a.pptr[p + 1] - q0);
+  int32_t row = 0;
+  if (lane < np) {
+    row = a.pdofs[q0 + lane];
+    st[lane] = pmult_fresh_residual<PtrT>(a, row, dx);
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  if (lane < np) {
+    const double *binv_row = pmult_block(a, p) + (size_t)lane * np;
+    double d = 0.0;
+    for (int k = 0; k < np; ++k) d += binv_row[k] * st[k];
+    dx[row] = __dadd_rn(dx[row], __dmul_rn(a.omega, d));
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// one workgroup, one patch of any size; tb: np doubles of LDS.  Every thread of the workgroup calls it (np is uniform).
+template <typename PtrT>
+__device__ __forceinline__ void pmult_group_patch(const PmultArgs &a, int64_t p, double *tb, double *dx)
+{
+  const int64_t q0 = a.pptr[p];
+  const int np = (int)(a.pptr[p + 1] - q0);
+  for (int i = threadIdx.x; i < np; i += blockDim.x) tb[i] = pmult_fresh_residual<PtrT>(a, a.pdofs[q0 + i], dx);
+  __syncthreads();                                           // every row of the patch has read dx before any is written
+  const double *binv = pmult_block(a, p);
+  for (int i = threadIdx.x; i < np; i += blockDim.x) {
+    const double *binv_row = binv + (size_t)i * np;
+    double d = 0.0;
+    for (int k = 0; k < np; ++k) d += binv_row[k] * tb[k];
+    const int32_t row = a.pdofs[q0 + i];
+    dx[row] = __dadd_rn(dx[row], __dmul_rn(a.omega, d));
+  }
+  __syncthreads();                                           // tb is free again
+}
+
+// the patches order[first .. first + count) of ONE colour, all of at most 64 dofs: one wave per patch, four per workgroup
+template <typename PtrT>
+__global__ __launch_bounds__(kBlock) void patch_mult_kernel(PmultArgs a, int64_t first, int64_t count, double *dx)
+{
+  __shared__ double st[kBlock / 64][64];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t k = (int64_t)blockIdx.x * (kBlock / 64) + w;
+  if (k >= count) return;
+  pmult_wave_patch<PtrT>(a, a.order[first + k], lane, st[w], dx);
+}
+
+// the patches order[first .. first + count) of ONE colour with more than 64 dofs: one workgroup per patch, t_p in dynamic LDS
+template <typename PtrT>
+__global__ __launch_bounds__(kBlock) void patch_mult_big_kernel(PmultArgs a, int64_t first, double *dx)
+{
+  extern __shared__ double pmult_tb[];
+  pmult_group_patch<PtrT>(a, a.order[first + blockIdx.x], pmult_tb, dx);
+}
+
+// The whole pass of a small level as ONE launch of ONE workgroup: dx = 0, then nsweeps sweeps over the colours (sweep s runs
+// forward where dirs[s & 1] == 0, backward where it is 1), a workgroup barrier after every colour.  cptr[c] .. cptr[c + 1]: the
+// patches of colour c in `order`, the first csmall[c] of them of at most 64 dofs (one wave each), the others worked through by the
+// whole workgroup one after the other.  Every loop bound is uniform over the workgroup, every thread reaches every barrier.
+template <typename PtrT>
+__global__ __launch_bounds__(kBlock) void patch_mult_pass_kernel(PmultArgs a, int64_t n, int ncolors, const int64_t *__restrict__ cptr,
+                                                                 const int64_t *__restrict__ csmall, int nsweeps, int dir0, int dir1,
+                                                                 double *dx)
+{
+  __shared__ double st[kBlock / 64][64];
+  extern __shared__ double pmult_tb[];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int64_t i = threadIdx.x; i < n; i += kBlock) dx[i] = 0.0;
+  __syncthreads();
+  for (int s = 0; s < nsweeps; ++s) {
+    const int backward = (s & 1) ? dir1 : dir0;
+    for (int ci = 0; ci < ncolors; ++ci) {
+      const int c = backward ? ncolors - 1 - ci : ci;
+      const int64_t c0 = cptr[c], c1 = cptr[c + 1], cs = c0 + csmall[c];
+      for (int64_t k = c0 + w; k < cs; k += kBlock / 64) pmult_wave_patch<PtrT>(a, a.order[k], lane, st[w], dx);
+      for (int64_t k = cs; k < c1; ++k) pmult_group_patch<PtrT>(a, a.order[k], pmult_tb, dx);
+      __syncthreads();                                       // the next colour reads what this one wrote
+    }
+  }
+}
+
 } // namespace gmg

@@ -37,6 +37,7 @@ using GridapSolvers.LinearSolvers: LanczosDiagnostic, estimate!      # Krylov/Kr
 
 export HipGMGLinearSolver, HipCGSolver, HipFGMRESSolver, HipMINRESSolver, PatchTable, HipPatchProlongation
 export ChebyshevSmoother, chebyshev_info
+export MultiplicativePatchSmoother, patch_coloring
 export LanczosDiagnostic, estimate!, cg_set_trace!, cg_trace
 export HipRichardsonLinearSolver, HipBlockTriangularSolver, HipBlockDiagonalSolver, HipBlockFGMRESSolver, block_mul!, block_cg_solve!
 export block_minres_solve!
@@ -54,6 +55,7 @@ const GMG_PATCH_LU, GMG_PATCH_NOPIVOT = Cint(0), Cint(1)
 const GMG_GS_SYMMETRIC, GMG_GS_FORWARD, GMG_GS_BACKWARD = Cint(0), Cint(1), Cint(2)
 const GMG_GS_ORDER_NATURAL, GMG_GS_ORDER_MULTICOLOR, GMG_GS_ORDER_GIVEN = Cint(0), Cint(1), Cint(2)
 const GMG_CHEB_EIG_POWER, GMG_CHEB_EIG_LANCZOS = Cint(0), Cint(1)
+const GMG_PMULT_SYMMETRIC, GMG_PMULT_FORWARD, GMG_PMULT_BACKWARD = Cint(0), Cint(1), Cint(2)
 
 struct GmgResult
   niters::Int32
@@ -345,6 +347,63 @@ function _set_smoother(h, lev, which, sm::ChebyshevSmoother)
   end
 end
 
+# MultiplicativePatchSmoother(M; niter, omega, type, coloring): a type of this binding -- block Gauss-Seidel over the patches of a
+# PatchTable (multiplicative Schwarz / Vanka), which the reference names as a TODO (SchwarzLinearSolvers.jl:3,13).  One pass: dx = 0;
+# niter times, forward over the colours (:forward, :symmetric) and backward (:backward, :symmetric), every patch solves its block
+# against the fresh residual (r - A dx)[rows_p] and adds omega times the result to dx[rows_p]; x += dx; r -= A dx
+# (gmg_set_smoother_patch_multiplicative).  coloring = :greedy (first-fit in patch order; two patches share a colour only if they share
+# no dof and no stored entry of A couples them) or a vector with the colour (>= 0) of every patch, which gmg_setup validates
+# (gmg_set_patch_coloring).  One GPU, a level matrix handed over whole.  NOT RUN: no Julia was available where this was written.
+struct MultiplicativePatchSmoother{A}
+  M        :: A
+  niter    :: Int
+  omega    :: Float64
+  type     :: Symbol
+  coloring :: Union{Symbol,Vector{Int32}}
+  function MultiplicativePatchSmoother(M::A; niter::Integer=1, omega::Real=1.0, type::Symbol=:symmetric, coloring=:greedy) where A
+    M isa PatchTable || error("MultiplicativePatchSmoother: M must be a PatchTable")
+    type in (:symmetric, :forward, :backward) || error("The type must be :symmetric, :forward or :backward.")
+    niter > 0 || error("The number of iterations must be a positive integer.")
+    omega > 0 || error("The relaxation parameter must be a positive real number.")
+    if coloring isa Symbol
+      coloring === :greedy || error("The coloring must be :greedy or a vector with one colour >= 0 per patch.")
+      return new{A}(M, Int(niter), Float64(omega), type, coloring)
+    end
+    all(c -> c >= 0, coloring) || error("The coloring must be :greedy or a vector with one colour >= 0 per patch.")
+    new{A}(M, Int(niter), Float64(omega), type, Int32.(coloring))
+  end
+end
+
+# the slot's patch tables and blocks through M's own setter, then the multiplicative sweep over them
+function _set_smoother(h, lev, which, sm::MultiplicativePatchSmoother)
+  _set_smoother(h, lev, which, RichardsonSmoother(sm.M, 1, 1.0))
+  t = sm.type === :symmetric ? GMG_PMULT_SYMMETRIC : sm.type === :forward ? GMG_PMULT_FORWARD : GMG_PMULT_BACKWARD
+  check(h, ccall((:gmg_set_smoother_patch_multiplicative, libgmgamd), Cint, (Ptr{Cvoid},Cint,Cint,Cint,Float64,Cint),
+                 h, lev, which, sm.niter, sm.omega, t))
+  if !(sm.coloring isa Symbol)
+    color = sm.coloring
+    GC.@preserve color begin
+      check(h, ccall((:gmg_set_patch_coloring, libgmgamd), Cint, (Ptr{Cvoid},Cint,Cint,Cint,Ptr{Int32},Int64),
+                     h, lev, which, 1, pointer(color), length(color)))
+    end
+  end
+end
+
+# gmg_get_patch_coloring: the colouring the setup of the slot's MultiplicativePatchSmoother uses -> (ncolors, color); lev is 1-based
+function patch_coloring(ns::HipGMGNumericalSetup, lev::Integer=1; which::Symbol=:pre)
+  w = which === :post ? GMG_POST : GMG_PRE
+  nc = Ref(Int64(0))
+  check(ns.handle, ccall((:gmg_get_patch_coloring, libgmgamd), Cint, (Ptr{Cvoid},Cint,Cint,Ref{Int64},Ptr{Int32},Int64),
+                         ns.handle, lev-1, w, nc, C_NULL, 0))
+  sm = (which === :post ? ns.solver.post_smoothers : ns.solver.pre_smoothers)[lev]
+  color = Vector{Int32}(undef, length(sm.M.patch_ptr) - 1)
+  GC.@preserve color begin
+    check(ns.handle, ccall((:gmg_get_patch_coloring, libgmgamd), Cint, (Ptr{Cvoid},Cint,Cint,Ref{Int64},Ptr{Int32},Int64),
+                           ns.handle, lev-1, w, nc, pointer(color), length(color)))
+  end
+  return Int(nc[]), color
+end
+
 # gmg_get_chebyshev_info: what the setup fixed for the ChebyshevSmoother of a slot (lev is 1-based, which = :pre or :post);
 # lambda_est is NaN where the bounds were given; eig_steps_done: the steps the estimate took (:power: eig_steps; :lanczos: fewer where
 # the Krylov space was exhausted; 0 where the bounds were given)
@@ -609,7 +668,7 @@ _gmres_side(::Nothing) = (Cint(0), nothing)
 _gmres_side(P::HipGMGLinearSolver) = (Cint(1), P)
 function _gmres_side(P::Tuple{Any,HipGMGLinearSolver})
   if P[1] isa LinearSolverFromSmoother
-    (P[1].smoother isa Union{RichardsonSmoother,GaussSeidelSmoother,ChebyshevSmoother} && P[1].smoother === P[2].pre_smoothers[1]) ||
+    (P[1].smoother isa Union{RichardsonSmoother,GaussSeidelSmoother,ChebyshevSmoother,MultiplicativePatchSmoother} && P[1].smoother === P[2].pre_smoothers[1]) ||
       error("LinearSolverFromSmoother must wrap the GMG's finest pre-smoother")
     return (Cint(3), P[2])
   end

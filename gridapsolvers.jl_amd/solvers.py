@@ -12,6 +12,7 @@ julia/GridapSolversAMD.jl.
     RichardsonSmoother(M,niter,w)   RichardsonSmoothers.jl:21-30    RichardsonSmoother
     PatchSolver / BlockJacobiSolver PatchBasedSmoothers/*.jl        PatchSolver / BlockJacobiSolver
     (none: an addition of the device library)                       ChebyshevSmoother(M, degree, ...)
+    (none: SchwarzLinearSolvers.jl:3,13 names it as a TODO)         MultiplicativePatchSmoother(M, niter, omega, type, coloring)
     GMGLinearSolver(mats,P,R;...)   GMGLinearSolvers.jl:48-69       GMGLinearSolver
     CGSolver(Pl;...)                Krylov/CGSolvers.jl:19          CGSolver
     LanczosDiagnostic(n) / estimate!  Krylov/KrylovUtils.jl:58-90   LanczosDiagnostic / estimate_ (the replay of the device's trace)
@@ -41,7 +42,7 @@ import numpy as np
 from . import abi
 
 __all__ = [
-    "JacobiLinearSolver", "RichardsonSmoother", "ChebyshevSmoother", "GaussSeidelSmoother", "SymGaussSeidelSmoother", "multicolor_order", "PatchSolver", "BlockJacobiSolver", "LUSolver",
+    "JacobiLinearSolver", "RichardsonSmoother", "ChebyshevSmoother", "GaussSeidelSmoother", "SymGaussSeidelSmoother", "multicolor_order", "MultiplicativePatchSmoother", "patch_multicolor", "PatchSolver", "BlockJacobiSolver", "LUSolver",
     "GMGLinearSolver", "CGSolver", "LanczosDiagnostic", "estimate_", "FGMRESSolver", "MINRESSolver", "GMRESSolver", "ConvergenceLog", "PatchProlongationOperator",
     "RichardsonLinearSolver", "BlockDiagonalSolver", "BlockTriangularSolver", "SchurComplementSolver", "LinearSystemBlock", "NonlinearSystemBlock", "MatrixBlock", "LinearSolverFromSmoother",
     "NullSpace", "NullspaceSolver", "is_orthonormal", "is_orthogonal", "make_orthonormal_", "gram_schmidt_", "modified_gram_schmidt_",
@@ -221,12 +222,75 @@ def multicolor_order(A):
     return order, color
 
 
+class MultiplicativePatchSmoother:
+    """MultiplicativePatchSmoother(M, niter=1, omega=1.0, type="symmetric", coloring="greedy"): block Gauss-Seidel over the patches of
+    M = PatchSolver / BlockJacobiSolver (multiplicative Schwarz, Vanka), swept colour by colour on the device
+    (gmg_set_smoother_patch_multiplicative).  The reference has the additive patch solver only (SchwarzLinearSolvers.jl:3,13: TODO).
+
+    One pass: dx = 0; niter times, forward over the colours (types forward, symmetric) and backward (backward, symmetric), every patch p
+    solves its block against the fresh residual (r - A dx)[rows_p] and adds omega times the result to dx[rows_p]; x += dx; r -= A dx.
+    No damping parameter has to be found: omega = 1 is the method.
+
+    coloring: "greedy" (first-fit in patch order; patches of one colour share no dof and no stored entry of A couples them) or a 1-D
+    integer array with the colour (>= 0) of every patch, which the setup validates.  GMGNumericalSetup.patch_coloring reports it.
+    One GPU, patch_cols == patch_rows, a level matrix handed over whole."""
+    _TYPES = {"symmetric": abi.PMULT_SYMMETRIC, "forward": abi.PMULT_FORWARD, "backward": abi.PMULT_BACKWARD}
+
+    def __init__(self, M, niter=1, omega=1.0, type="symmetric", coloring="greedy"):
+        if not isinstance(M, PatchSolver):
+            raise TypeError("MultiplicativePatchSmoother: M must be PatchSolver or BlockJacobiSolver")
+        if type not in self._TYPES:
+            raise ValueError("The type must be :symmetric, :forward or :backward.")
+        if not int(niter) > 0:
+            raise ValueError("The number of iterations must be a positive integer.")
+        if not float(omega) > 0.0:
+            raise ValueError("The relaxation parameter must be a positive real number.")
+        self.M, self.niter, self.omega, self.type = M, int(niter), float(omega), type
+        self.coloring = self._check_coloring(coloring, M.patch_ptr.size - 1)
+
+    @staticmethod
+    def _check_coloring(coloring, npatch):
+        msg = 'The coloring must be "greedy" or a 1-D integer array with one colour >= 0 per patch.'
+        if isinstance(coloring, str):
+            if coloring != "greedy":
+                raise ValueError(msg)
+            return coloring
+        if isinstance(coloring, (bytes, dict, set)) or coloring is None:
+            raise ValueError(msg)
+        a = np.asarray(coloring)
+        if a.ndim != 1 or a.dtype.kind not in "iu" or (a.size and (a.min() < 0 or a.max() >= 2 ** 31)):
+            raise ValueError(msg)
+        if a.size != npatch:
+            raise ValueError("The coloring has %d entries, M has %d patches." % (a.size, npatch))
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def patch_multicolor(A, patch_ptr, patch_dofs):
+    """gmg_patch_multicolor on the stored pattern of a square matrix (poisson.CSR, scipy CSR, ...; explicit zeros count) and a patch
+    table -> (color, ncolors): the colouring coloring="greedy" uses.  Host only: no handle, no GPU."""
+    shape, ptr, idx, _val, layout, base = _csr_fields(A)
+    if shape[0] != shape[1]:
+        raise ValueError("patch_multicolor: the matrix must be square")
+    # (the conflict rule symmetrises the pattern, so a CSC pattern gives the same answer as its CSR form)
+    ptr = np.ascontiguousarray(ptr, dtype=np.int64) - base
+    idx = np.ascontiguousarray(idx, dtype=np.int32) - np.int32(base)
+    pp = np.ascontiguousarray(patch_ptr, dtype=np.int64)
+    pd = np.ascontiguousarray(patch_dofs, dtype=np.int32)
+    if pp.ndim != 1 or pp.size < 1:
+        raise ValueError("patch_ptr must have npatch+1 entries")
+    color, nc = np.empty(pp.size - 1, dtype=np.int32), C.c_int64(0)
+    abi.check(None, abi.load().gmg_patch_multicolor(int(shape[0]), C.c_void_p(ptr.ctypes.data), C.c_void_p(idx.ctypes.data), pp.size - 1,
+                                                    C.c_void_p(pp.ctypes.data), C.c_void_p(pd.ctypes.data), C.c_void_p(color.ctypes.data),
+                                                    C.byref(nc)))
+    return color, nc.value
+
+
 class LinearSolverFromSmoother:
     """LinearSolverFromSmoother(smoother) -- LinearSolverFromSmoothers.jl:2-4: x = 0; r = copy(b); solve!(x,smoother,r)."""
 
     def __init__(self, smoother):
-        if not isinstance(smoother, (RichardsonSmoother, GaussSeidelSmoother, ChebyshevSmoother)):
-            raise TypeError("smoother must be a RichardsonSmoother, a GaussSeidelSmoother or a ChebyshevSmoother")
+        if not isinstance(smoother, (RichardsonSmoother, GaussSeidelSmoother, ChebyshevSmoother, MultiplicativePatchSmoother)):
+            raise TypeError("smoother must be a RichardsonSmoother, a GaussSeidelSmoother, a ChebyshevSmoother or a MultiplicativePatchSmoother")
         self.smoother = smoother
 
 
@@ -839,8 +903,16 @@ class GMGNumericalSetup:
             if sm.eig_method != "power":
                 abi.check(h, lib.gmg_set_chebyshev_eig_method(h, l, which, sm._EIG_METHODS[sm.eig_method]))
             return
+        if isinstance(sm, MultiplicativePatchSmoother):
+            # the slot's patch tables and blocks through M's own setter, then the multiplicative sweep over them
+            self._set_smoother(l, which, RichardsonSmoother(sm.M, 1, 1.0))
+            abi.check(h, lib.gmg_set_smoother_patch_multiplicative(h, l, which, sm.niter, sm.omega, sm._TYPES[sm.type]))
+            if not isinstance(sm.coloring, str):
+                abi.check(h, lib.gmg_set_patch_coloring(h, l, which, abi.PATCH_COLORING_GIVEN, C.c_void_p(sm.coloring.ctypes.data),
+                                                        sm.coloring.size))
+            return
         if not isinstance(sm, RichardsonSmoother):
-            raise TypeError("smoothers must be RichardsonSmoother, GaussSeidelSmoother or ChebyshevSmoother objects")
+            raise TypeError("smoothers must be RichardsonSmoother, GaussSeidelSmoother, ChebyshevSmoother or MultiplicativePatchSmoother objects")
         if isinstance(sm.M, JacobiLinearSolver):
             abi.check(h, lib.gmg_set_smoother_jacobi(h, l, which, sm.niter, sm.omega))
         else:
@@ -1024,6 +1096,18 @@ class GMGNumericalSetup:
         abi.check(self.h, self._lib.gmg_get_chebyshev_eig(self.h, lev, abi.PRE if which == "pre" else abi.POST, C.byref(meth), C.byref(done)))
         return dict(degree=deg.value, lambda_est=v[0].value, lambda_min=v[1].value, lambda_max=v[2].value, eig_steps=steps.value,
                     eig_method=("power", "lanczos")[meth.value], eig_steps_done=done.value)
+
+    def patch_coloring(self, level=0, which="pre"):
+        """gmg_get_patch_coloring: the colouring the setup of the slot's MultiplicativePatchSmoother uses -> (ncolors, color);
+        GmgError (ERR_STATE) on a slot without one."""
+        if which not in ("pre", "post"):
+            raise ValueError('which must be "pre" or "post"')
+        w, nc = abi.PRE if which == "pre" else abi.POST, C.c_int64(0)
+        abi.check(self.h, self._lib.gmg_get_patch_coloring(self.h, level, w, C.byref(nc), None, 0))
+        sm = (self.solver.pre_smoothers if which == "pre" else self.solver.post_smoothers)[level]
+        color = np.empty(sm.M.patch_ptr.size - 1, dtype=np.int32)
+        abi.check(self.h, self._lib.gmg_get_patch_coloring(self.h, level, w, C.byref(nc), C.c_void_p(color.ctypes.data), color.size))
+        return nc.value, color
 
     def cg_set_trace(self, capacity):
         """gmg_cg_set_trace: capacity > 0 makes the outermost CG of gmg_cg_solve record alpha_k, beta_k; 0 releases the buffer."""

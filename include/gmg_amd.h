@@ -298,6 +298,61 @@ enum gmg_cheb_eig { GMG_CHEB_EIG_POWER = 0, GMG_CHEB_EIG_LANCZOS = 1 };
 GMG_API int gmg_set_chebyshev_eig_method(gmg_handle_t h, int lev, int which, int method);
 GMG_API int gmg_get_chebyshev_eig(gmg_handle_t h, int lev, int which, int *method, int *steps_done);
 
+/* MultiplicativePatchSmoother(M, niter, omega, type) over the patch blocks of a smoother slot, M = PatchSolver / BlockJacobiSolver:
+ * block Gauss-Seidel over the patches (multiplicative Schwarz, Vanka), swept colour by colour.  The reference has only the additive
+ * patch solver and names this form as a TODO (SchwarzLinearSolvers.jl:3,13); it is an addition of this library, on one GPU.
+ * Call it AFTER gmg_set_smoother_patch[_matrices] on the same slot: it turns that slot's additive Richardson iteration into the
+ * multiplicative one with this call's niter and omega.  Setting a plain smoother on the slot again clears it.
+ * One pass on (x, r):
+ *   dx = 0 ; r0 = r
+ *   repeat niter times:
+ *     forward  (types forward, symmetric): for c = 0 .. ncolors-1, for every patch p of colour c:
+ *     backward (types backward, symmetric): for c = ncolors-1 .. 0, for every patch p of colour c:
+ *       t_i = r0[rows_p[i]] - sum_k a(rows_p[i], k) dx[k]    the row in its stored order, summed from 0.0, product and sum rounded
+ *       d_i = sum_j inv(A_pp)[i, j] t_j                      j = 0 .. n_p-1, as the additive patch solve sums
+ *       dx[rows_p[i]] = dx[rows_p[i]] + omega d_i
+ *   x = x + dx ; r = r - A dx                                the level's operator application
+ * inv(A_pp) is the inverse block the patch setup builds (from the level matrix, the caller's patch matrices or the caller's factors,
+ * pivoting or not, de-duplicated or not).  A patch without dofs is skipped; a dof in no patch keeps dx = 0.
+ * COLOURING.  Two patches may share a colour only if they share no dof AND the stored pattern of A, symmetrised and with explicit
+ * zeros counting, couples no dof of one to a dof of the other.  The patches of a colour then read and write disjoint entries of dx
+ * and run in parallel; the result is bit for bit the sequential loop over the patches sorted stably by (colour, patch index).
+ * gmg_set_patch_coloring (after gmg_set_smoother_patch_multiplicative, or on any patch slot): kind 0 = greedy first-fit in patch
+ * order on that conflict graph (the default; deterministic; 2^d colours on vertex stars of a Cartesian mesh), kind 1 = the caller's
+ * color[npatch], every entry >= 0 (copied); npatch different from the slot's patch count, a negative colour, an unknown kind or a
+ * colour array with kind 0: GMG_ERR_INVALID.  gmg_setup ALWAYS validates the colouring in use on the host -- that check is what makes
+ * the launches race-free -- and a conflict is GMG_ERR_INVALID naming the level and the two patches.  gmg_get_patch_coloring (after
+ * gmg_setup; which = GMG_PRE or GMG_POST): the number of colours and, if `color` is not NULL, the colour of every patch (cap < npatch:
+ * GMG_ERR_INVALID); GMG_ERR_STATE on a slot without such a smoother.
+ * gmg_patch_multicolor is the colouring itself, without a handle and without a GPU: the 0-based CSR pattern of the square level matrix
+ * and the patch table -> color[npatch], *ncolors.  It works from a dof -> patch incidence and never forms the patch x patch graph.
+ * gmg_setup calls it.  An index out of range or a non-monotone pointer array: GMG_ERR_INVALID.
+ * KERNELS.  One launch per non-empty colour and direction: patch_mult_kernel (one wave per patch of at most 64 dofs, four patches per
+ * workgroup) and, for the patches of a colour with more than 64 dofs, patch_mult_big_kernel (one workgroup per patch); on small levels
+ * the whole pass is ONE launch of ONE workgroup, patch_mult_pass_kernel, with a workgroup barrier between colours.  No kernel waits on
+ * another workgroup.  Option pmult_one_launch (live): 1 (default) = levels of at most pmult_one_launch_max patches (default 32, from profiles/patch_mult_timing.md), 0 =
+ * never, 2 = every level; the same bits in all settings.  The sweeps read rows of A from the level's CSR, which such a level keeps on
+ * the device next to its sweep layout (counted by gmg_device_bytes).
+ * gmg_update_values[_csc] + gmg_setup keep the colouring and rebuild the blocks: the bits of a fresh setup.
+ * Errors of gmg_set_smoother_patch_multiplicative: GMG_ERR_STATE if the slot holds no patch smoother; GMG_ERR_INVALID for niter <= 0,
+ * omega <= 0 or an unknown type; GMG_ERR_UNSUPPORTED if the slot is a Chebyshev slot (and gmg_set_smoother_chebyshev on a
+ * multiplicative slot is GMG_ERR_UNSUPPORTED: Chebyshev over the multiplicative sweep is not built).
+ * Refused at gmg_setup with GMG_ERR_UNSUPPORTED, naming the level: a level whose operator was streamed (gmg_set_operator_rows) and
+ * so has no CSR to read rows from; patch_cols != patch_rows (the sweep needs one dof set per patch); a communicator of more than one
+ * rank, real or loopback (the colours of a partitioned level would have to be agreed across ranks); a patch of more than 4096 dofs
+ * (the workgroup kernel stages t_p in LDS).
+ * gmg_smooth runs one pass; gmg_precond_apply runs it with x = 0 on a copy of r, so z = dx; the slot works as the finest pre-smoother
+ * behind LinearSolverFromSmoother and inside a GMG that is a block of a block solver.  gmg_sweep_signature of such a level ends in
+ * " pmult=F+B/<ncolors>" (" pmult=F/...", " pmult=B/..." for the one-direction types).  With profiling enabled on the level,
+ * gmg_kernel_stats.launches counts the colour launches and the x update of its passes (r -= A dx is not counted).
+ * gmg_model_bytes is not extended: on a handle with such a smoother its byte model still counts Jacobi sweeps. */
+enum gmg_pmult_type { GMG_PMULT_SYMMETRIC = 0, GMG_PMULT_FORWARD = 1, GMG_PMULT_BACKWARD = 2 };
+GMG_API int gmg_set_smoother_patch_multiplicative(gmg_handle_t h, int lev, int which, int niter, double omega, int type);
+GMG_API int gmg_set_patch_coloring(gmg_handle_t h, int lev, int which, int kind, const int32_t *color, int64_t npatch);
+GMG_API int gmg_get_patch_coloring(gmg_handle_t h, int lev, int which, int64_t *ncolors, int32_t *color, int64_t cap);
+GMG_API int gmg_patch_multicolor(int64_t nrows, const int64_t *ptr, const int32_t *col, int64_t npatch, const int64_t *patch_ptr,
+                                 const int32_t *patch_dofs, int32_t *color, int64_t *ncolors);
+
 /* Patch-corrected prolongation y = P x - sum_p R_p^T A_pp^-1 R_p (A P x)  over the given patches
  * (PatchProlongationOperator, PatchBasedSmoothers/PatchTransferOperators.jl:153-172 with rhs = lhs = the
  * level operator; used by the reference for grad-div problems, test/Applications/StokesGMG.jl:125-133).
@@ -422,6 +477,9 @@ GMG_API int gmg_set_options(gmg_handle_t h, int mode, int cycle, int maxiter, do
  *   coarsest level   coarse_host_max (1500) coarse_host_fallback_max (6000) coarse_auto_cg_min (20000: a dense-inverse request on a
  *                    coarsest level of at least this many dofs is served by the device CG-Jacobi solver instead) gj_mfma (1) gj_wide_min (4096)
  *   patch smoother   patch_dedup (1) patch_source_dedup (1) patch_operator (1)
+ *                    pmult_one_launch* (1: the pass of a multiplicative patch slot runs as one launch of one workgroup,
+ *                    patch_mult_pass_kernel, on levels of at most pmult_one_launch_max* patches; 0: never, one launch per colour and
+ *                    direction; 2: on every level.  Same bits in all settings: the A/B switch of tools/patch_mult_timing.py)
  *   distributed      overlap (1) halo_fuse_pack (1) host_async (0)
  *   host round trip  host_poll* (1: the residual norm of every Krylov iteration is posted into page-locked host memory and polled; 0: copy +
  *                    hipStreamSynchronize)
