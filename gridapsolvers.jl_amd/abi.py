@@ -73,6 +73,13 @@ SYMBOLS = {
                              C.c_void_p, C.c_int, C.c_int, C.c_int],
     "gmg_set_restriction": [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                             C.c_void_p, C.c_int, C.c_int, C.c_int],
+    "gmg_set_galerkin": [C.c_void_p, C.c_int],
+    "gmg_get_galerkin_matrix": [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_int64],
+    "gmg_get_galerkin_timing": [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    "gmg_galerkin_pattern": [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int64,
+                             C.POINTER(C.c_int64)],
     "gmg_set_smoother_jacobi": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double],
     "gmg_set_smoother_patch": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int64, C.c_void_p,
                                C.c_void_p, C.c_int, C.c_int],

@@ -442,8 +442,12 @@ struct GhostFix {
 };
 
 struct GsLevel;                    // gs.inc.hpp
+struct GalerkinLevel;              // galerkin.inc.hpp
 
 struct Level {
+  // Galerkin level (gmg_set_galerkin): the matrix is R (A P) of the finer level, formed at the start of gmg_setup; holds the patterns
+  // of the symbolic phase and the product itself.  Null on a level whose matrix the caller gives
+  std::shared_ptr<GalerkinLevel> gal;
   // s = omega*(Dinv*r) already written into sbuf[0] by the kernel that produced r (restriction / r -= A dx)
   bool s0_ready = false;
   const double *s0_src = nullptr;
@@ -4440,6 +4444,9 @@ struct gmg_solver {
   void refill_values(DevCSR &A, const double *hval, double *dinv, RefillStage &st);
   void refill_release(RefillStage &st);
   void setup();
+  void galerkin_prepare();           // galerkin.inc.hpp: forms the matrices of the Galerkin levels that are out of date, before setup() / refresh_values()
+  void galerkin_invalidate(int l);   // an operator the product of level l is formed from was replaced: patterns and values are rebuilt
+  void galerkin_install(int l, bool fresh);
   void build_coarse();
   double *build_dense_inverse(const HostCSR &A, const std::string &what);
   double *build_coarse_device(const HostCSR &A, const std::string &what);
@@ -6799,6 +6806,8 @@ int gmg_set_matrix(gmg_handle_t h, int lev, int64_t nrows, int64_t ncols, int64_
     L.clear_split();                                        // (a split stream of an earlier gmg_set_operator_rows is gone with it)
     L.input_layout = layout;
     L.csc_perm.clear(); L.csc_perm.shrink_to_fit();
+    L.gal.reset();                                          // (a matrix of the caller's replaces a Galerkin mark)
+    if (slot < h->nlev) h->galerkin_invalidate(slot + 1);
     if (slot < h->nlev - 1 && h->try_eager_pattern(L.sA, 0, nrows, ncols, nnz, ptr, idx, val, layout, index_base, index_bytes)) {
       L.hA = HostCSR(); L.hA.nrows = nrows; L.hA.ncols = ncols;     // shape only
     } else
@@ -6832,6 +6841,8 @@ int gmg_set_operator_rows(gmg_handle_t h, int lev, int op, int64_t nrows_total, 
                 h->comm.nranks > 1 ? "a streamed level matrix must be square: own | ghost levels take their rows whole (gmg_set_matrix), levels in the "
                                      "overlapping layout (gmg_set_partition_overlap) and replicated levels can be streamed"
                                    : "level matrix must be square");
+      if (op == GMG_OP_A) L.gal.reset();
+      h->galerkin_invalidate(lev + 1);
       S = std::make_shared<PatStream>();
       S->mode = (op == GMG_OP_A) ? 0 : 1;
       S->nrows = nrows_total; S->ncols = split ? nrows_total : ncols;
@@ -6928,12 +6939,16 @@ int gmg_set_operator_rows_repeat(gmg_handle_t h, int lev, int op, int64_t nrows_
   });
 }
 
+static void galerkin_values_changed(gmg_handle_t h, int lev);   // galerkin.inc.hpp
+static void galerkin_refuse_update(gmg_handle_t h, int lev);    // galerkin.inc.hpp: GMG_ERR_STATE on a Galerkin level
+
 static void update_values_impl(gmg_handle_t h, int lev, const double *val)
 {
   {
     Level &L = h->lev[lev];
     REQUIRE(L.hasA, GMG_ERR_STATE, "no matrix set on this level");
     REQUIRE(val, GMG_ERR_INVALID, "null values");
+    galerkin_values_changed(h, lev);                        // a Galerkin level below is formed again by the next gmg_setup (numeric phase only)
     if (L.sA) {
       // The level is held in row-pattern form only (no CSR copy: structured operators handed over whole, or streamed).  The
       // pattern ids depend on the values, so the rows are rebuilt from the pattern form with the new values and hashed again
@@ -7026,6 +7041,7 @@ int gmg_update_values(gmg_handle_t h, int lev, const double *val)
 {
   return guarded(h, [&] {
     check_level(h, lev, false);
+    galerkin_refuse_update(h, lev);
     update_values_impl(h, lev, val);
   });
 }
@@ -7034,6 +7050,7 @@ int gmg_update_values_csc(gmg_handle_t h, int lev, const void *colptr, const voi
 {
   return guarded(h, [&] {
     check_level(h, lev, false);
+    galerkin_refuse_update(h, lev);
     Level &L = h->lev[lev];
     REQUIRE(L.hasA, GMG_ERR_STATE, "no matrix set on this level");
     REQUIRE(val, GMG_ERR_INVALID, "null values");
@@ -7064,6 +7081,7 @@ int gmg_set_prolongation(gmg_handle_t h, int lev, int64_t nrows, int64_t ncols, 
   return guarded(h, [&] {
     check_level(h, lev, true);
     Level &L = h->lev[lev];
+    h->galerkin_invalidate(lev + 1);
     L.sP.reset();
     if (h->try_eager_pattern(L.sP, 1, nrows, ncols, nnz, ptr, idx, val, layout, index_base, index_bytes)) {
       L.hP = HostCSR(); L.hP.nrows = nrows; L.hP.ncols = ncols;     // shape only (R = P^T, if needed, is formed from the pattern form)
@@ -7080,6 +7098,7 @@ int gmg_set_restriction(gmg_handle_t h, int lev, int64_t nrows, int64_t ncols, i
   return guarded(h, [&] {
     check_level(h, lev, true);
     Level &L = h->lev[lev];
+    h->galerkin_invalidate(lev + 1);
     L.sR.reset();
     if (h->try_eager_pattern(L.sR, 1, nrows, ncols, nnz, ptr, idx, val, layout, index_base, index_bytes)) {
       L.hR = HostCSR(); L.hR.nrows = nrows; L.hR.ncols = ncols;
@@ -7422,6 +7441,7 @@ int gmg_setup(gmg_handle_t h)
 {
   return guarded(h, [&] {
     REQUIRE(h, GMG_ERR_INVALID, "null handle");
+    h->galerkin_prepare();                                  // Galerkin levels: R (A P) of the current operators, set like a caller's matrix
     if (h->can_refresh()) h->refresh_values();             // numerical_setup!: only values changed and the layouts carry values
     else h->setup();
   });
@@ -8424,3 +8444,4 @@ int gmg_device_bytes(gmg_handle_t h, int64_t *bytes)
 #include "gs.inc.hpp"
 #include "cheb.inc.hpp"
 #include "pmult.inc.hpp"
+#include "galerkin.inc.hpp"

@@ -5509,4 +5509,48 @@ __global__ __launch_bounds__(kBlock) void patch_mult_pass_kernel(PmultArgs a, in
   }
 }
 
+// ----------------------------------------------------------------------------
+// Galerkin coarse matrices (galerkin.inc.hpp): the numeric phase of C = A B on a pattern the host has built, by gathering -- one lane
+// owns one stored entry C(i, J), walks row i of A in its stored (ascending) column order and looks J up in the sorted row k of B by
+// binary search:  C(i, J) = sum over k ascending of A(i, k) * B(k, J), from 0.0, every product and every sum rounded separately.
+// No lane writes anything but its own entry: no atomics, the same bits on every run.  Both stages of R (A P) are launches of this
+// kernel (T = A P, then A_coarse = R T).  The rows of A and B must be sorted and duplicate-free, every column of A a row of B (checked
+// on the host); an entry of the pattern that no term reaches stays 0.0.  Grid-stride, so any grid covers nnz_c.
+// ----------------------------------------------------------------------------
+template <typename PtrT>
+__device__ __forceinline__ int64_t galerkin_row_of(const PtrT *__restrict__ ptr, int64_t nrows, int64_t e)
+{
+  int64_t lo = 0, hi = nrows;                                // ptr[lo] <= e < ptr[hi]; rows without entries are stepped over
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if ((int64_t)ptr[mid] <= e) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+template <typename PtrT>
+__global__ __launch_bounds__(kBlock) void galerkin_gather_kernel(int64_t nrows, int64_t nnz_c, const PtrT *__restrict__ cptr,
+                                                                 const int32_t *__restrict__ ccol, const PtrT *__restrict__ aptr,
+                                                                 const int32_t *__restrict__ acol, const double *__restrict__ aval,
+                                                                 const PtrT *__restrict__ bptr, const int32_t *__restrict__ bcol,
+                                                                 const double *__restrict__ bval, double *__restrict__ cval)
+{
+  for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < nnz_c; e += (int64_t)gridDim.x * kBlock) {
+    const int64_t i = galerkin_row_of<PtrT>(cptr, nrows, e);
+    const int32_t J = ccol[e];
+    double s = 0.0;
+    for (PtrT k = aptr[i]; k < aptr[i + 1]; ++k) {
+      const int32_t row = acol[k];
+      const PtrT end = bptr[row + 1];
+      PtrT lo = bptr[row], hi = end;
+      while (lo < hi) {
+        const PtrT mid = lo + ((hi - lo) >> 1);
+        if (bcol[mid] < J) lo = mid + 1; else hi = mid;
+      }
+      if (lo < end && bcol[lo] == J) s = __dadd_rn(s, __dmul_rn(aval[k], bval[lo]));
+    }
+    cval[e] = s;
+  }
+}
+
 } // namespace gmg

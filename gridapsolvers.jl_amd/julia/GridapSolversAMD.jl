@@ -38,6 +38,7 @@ using GridapSolvers.LinearSolvers: LanczosDiagnostic, estimate!      # Krylov/Kr
 export HipGMGLinearSolver, HipCGSolver, HipFGMRESSolver, HipMINRESSolver, PatchTable, HipPatchProlongation
 export ChebyshevSmoother, chebyshev_info
 export MultiplicativePatchSmoother, patch_coloring
+export Galerkin, level_matrix, galerkin_pattern
 export LanczosDiagnostic, estimate!, cg_set_trace!, cg_trace
 export HipRichardsonLinearSolver, HipBlockTriangularSolver, HipBlockDiagonalSolver, HipBlockFGMRESSolver, block_mul!, block_cg_solve!
 export block_minres_solve!
@@ -91,6 +92,14 @@ struct HipPatchProlongation{M}
   patches :: PatchTable
 end
 
+# Galerkin(): marker for an entry of smatrices[2:end] -- the matrix of that level is R (A P) of the finer level, formed on the device at
+# the numerical setup (gmg_set_galerkin) instead of being assembled with Gridap:
+#   HipGMGLinearSolver(Any[A1, Galerkin(), Galerkin()], interp, restrict; ...)
+# The reference has the caller's matrices only (GMGLinearSolverFromMatrices, GMGLinearSolvers.jl:336-340).  level_matrix(ns, lev)
+# returns the product; numerical_setup!(ns, A) forms it again from the new values (an entry of its `smatrices` for such a level must
+# be `nothing` or Galerkin()).  One GPU, operators of the finer level handed over whole.
+struct Galerkin end
+
 struct HipGMGLinearSolver{A,B,C,D,E,F} <: Gridap.Algebra.LinearSolver
   smatrices      :: A
   interp         :: B           # explicit sparse prolongations, level l+1 -> l
@@ -114,7 +123,7 @@ end
 # once and then move over PCIe by DMA at the link rate -- 3.6 ms instead of 4.7 ms per config-2 solve; the setup keeps them alive.
 # For a top-level solve! that is called again and again with the SAME x and b; not for a preconditioner applied to rotating work vectors)
 function HipGMGLinearSolver(
-  smatrices::AbstractArray{<:AbstractMatrix}, interp::AbstractArray, restrict = nothing;
+  smatrices::AbstractArray, interp::AbstractArray, restrict = nothing;
   pre_smoothers  = fill(RichardsonSmoother(JacobiLinearSolver(),10),length(smatrices)-1),
   post_smoothers = pre_smoothers,
   coarsest_solver = Gridap.Algebra.LUSolver(),
@@ -124,6 +133,7 @@ function HipGMGLinearSolver(
 )
   nlev = length(smatrices)
   @assert nlev-1 == length(interp) == length(pre_smoothers) == length(post_smoothers)
+  @assert smatrices[1] isa AbstractMatrix && all(M -> M isa AbstractMatrix || M isa Galerkin, smatrices)
   @assert isnothing(restrict) || length(restrict) == nlev-1
   @assert mode ∈ [:preconditioner,:solver]
   @assert cycle_type ∈ [:v_cycle,:w_cycle,:f_cycle]
@@ -447,7 +457,11 @@ function Gridap.Algebra.numerical_setup(ss::HipGMGSymbolicSetup, mat::AbstractMa
     set_option!(ns, k, v)
   end
   for l in 1:nlev
-    _set_op(:matrix, h, l-1, l == 1 ? mat : s.smatrices[l])       # smatrices[1] = mat (:338)
+    if l > 1 && s.smatrices[l] isa Galerkin
+      check(h, ccall((:gmg_set_galerkin, libgmgamd), Cint, (Ptr{Cvoid},Cint), h, l-1))
+    else
+      _set_op(:matrix, h, l-1, l == 1 ? mat : s.smatrices[l])     # smatrices[1] = mat (:338)
+    end
   end
   for l in 1:nlev-1
     ip = s.interp[l]
@@ -479,9 +493,45 @@ function Gridap.Algebra.numerical_setup(ss::HipGMGSymbolicSetup, mat::AbstractMa
   if s.coarsest_solver isa Gridap.Algebra.LUSolver          # the default: one setup, dense inverse of the coarsest matrix on the device
     check(h, ccall((:gmg_setup, libgmgamd), Cint, (Ptr{Cvoid},), h))
   else                                                      # GMGLinearSolvers.jl:423-434: the caller's coarsest solver (sets up the handle itself)
-    set_coarsest_solver!(ns, s.coarsest_solver, s.smatrices[nlev])
+    set_coarsest_solver!(ns, s.coarsest_solver, _coarsest_matrix(ns, s.smatrices[nlev]))
   end
   return ns
+end
+
+# gmg_get_galerkin_matrix: the matrix of a Galerkin level as the last setup formed it (lev is 1-based)
+function level_matrix(ns::HipGMGNumericalSetup, lev::Integer)
+  n, nnz = Ref(Int64(0)), Ref(Int64(0))
+  T = (Ptr{Cvoid},Cint,Ref{Int64},Ref{Int64},Ptr{Int64},Ptr{Int32},Ptr{Float64},Int64)
+  check(ns.handle, ccall((:gmg_get_galerkin_matrix, libgmgamd), Cint, T, ns.handle, lev-1, n, nnz, C_NULL, C_NULL, C_NULL, 0))
+  ptr, col, val = Vector{Int64}(undef, n[]+1), Vector{Int32}(undef, nnz[]), Vector{Float64}(undef, nnz[])
+  GC.@preserve ptr col val begin
+    check(ns.handle, ccall((:gmg_get_galerkin_matrix, libgmgamd), Cint, T, ns.handle, lev-1, n, nnz, pointer(ptr), pointer(col), pointer(val), nnz[]))
+  end
+  # the rows of the CSR are the columns of the transpose's CSC
+  return SparseMatrixCSC{Float64,Int64}(copy(transpose(SparseMatrixCSC{Float64,Int64}(n[], n[], ptr .+ 1, Int64.(col) .+ 1, val))))
+end
+
+# the coarsest matrix a host-side coarsest solver is set up on: of a Galerkin level, the product (the handle is set up once to form it)
+_coarsest_matrix(ns::HipGMGNumericalSetup, M::AbstractMatrix) = M
+function _coarsest_matrix(ns::HipGMGNumericalSetup, ::Union{Galerkin,Nothing})
+  check(ns.handle, ccall((:gmg_setup, libgmgamd), Cint, (Ptr{Cvoid},), ns.handle))
+  return level_matrix(ns, length(ns.solver.smatrices))
+end
+
+# gmg_galerkin_pattern: the symbolic phase on the host, no handle and no GPU -> ((tptr, tcol), (cptr, ccol)), 0-based CSR patterns of
+# T = A P and of R A P with ascending columns
+function galerkin_pattern(R::SparseMatrixCSC, A::SparseMatrixCSC, P::SparseMatrixCSC)
+  csr(M) = (Mt = SparseMatrixCSC{Float64,Int64}(copy(transpose(M))); (Mt.colptr .- 1, Int32.(Mt.rowval .- 1)))
+  (rp, rc), (ap, ac), (pp, pc) = csr(R), csr(A), csr(P)
+  nc, nf = size(R,1), size(A,1)
+  @assert size(A,2) == nf == size(R,2) == size(P,1) && size(P,2) == nc
+  tn, cn = Ref(Int64(0)), Ref(Int64(0))
+  T = (Int64,Int64,Ptr{Int64},Ptr{Int32},Ptr{Int64},Ptr{Int32},Ptr{Int64},Ptr{Int32},Ptr{Int64},Ptr{Int32},Int64,Ref{Int64},Ptr{Int64},Ptr{Int32},Int64,Ref{Int64})
+  check(C_NULL, ccall((:gmg_galerkin_pattern, libgmgamd), Cint, T, nc, nf, rp, rc, ap, ac, pp, pc, C_NULL, C_NULL, 0, tn, C_NULL, C_NULL, 0, cn))
+  tptr, tcol = Vector{Int64}(undef, nf+1), Vector{Int32}(undef, tn[])
+  cptr, ccol = Vector{Int64}(undef, nc+1), Vector{Int32}(undef, cn[])
+  check(C_NULL, ccall((:gmg_galerkin_pattern, libgmgamd), Cint, T, nc, nf, rp, rc, ap, ac, pp, pc, tptr, tcol, tn[], tn, cptr, ccol, cn[], cn))
+  return (tptr, tcol), (cptr, ccol)
 end
 
 # numerical_setup!(ns,A[,smatrices]): new values on the same pattern.  The reference's FromMatrices variant only logs an @error
@@ -509,6 +559,10 @@ function Gridap.Algebra.numerical_setup!(ns::HipGMGNumericalSetup, mat::Abstract
   if !isnothing(smatrices)
     @assert length(smatrices) == length(ns.solver.smatrices)
     for l in 2:length(smatrices)
+      if ns.solver.smatrices[l] isa Galerkin              # formed again from the finer level's new values by gmg_setup
+        (isnothing(smatrices[l]) || smatrices[l] isa Galerkin) || throw(ArgumentError("smatrices[$l]: level $l is a Galerkin level"))
+        continue
+      end
       _update_values(ns.handle, l-1, smatrices[l])
     end
   end
@@ -516,7 +570,7 @@ function Gridap.Algebra.numerical_setup!(ns::HipGMGNumericalSetup, mat::Abstract
     check(ns.handle, ccall((:gmg_setup, libgmgamd), Cint, (Ptr{Cvoid},), ns.handle))
   else                                                      # the caller's coarsest solver is set up again on the new coarsest matrix (:291-294)
     nlev = length(ns.solver.smatrices)
-    set_coarsest_solver!(ns, ns.solver.coarsest_solver, isnothing(smatrices) ? ns.solver.smatrices[nlev] : smatrices[nlev])
+    set_coarsest_solver!(ns, ns.solver.coarsest_solver, _coarsest_matrix(ns, isnothing(smatrices) ? ns.solver.smatrices[nlev] : smatrices[nlev]))
   end
   return ns
 end

@@ -285,6 +285,50 @@ def patch_multicolor(A, patch_ptr, patch_dofs):
     return color, nc.value
 
 
+class Galerkin:
+    """Galerkin(): marker for an entry of smatrices[1:] -- the matrix of that level is R (A P) of the finer level, formed on the device
+    at the numerical setup (gmg_set_galerkin) instead of being assembled by the caller:
+        GMGLinearSolver([A0, Galerkin(), Galerkin()], interp, restrict, ...)
+    The reference has the caller's matrices only (GMGLinearSolverFromMatrices, GMGLinearSolvers.jl:336-340).  One GPU; the finer
+    level's operators handed over whole.  GMGNumericalSetup.level_matrix(lev) returns the product."""
+
+    def __repr__(self):
+        return "Galerkin()"
+
+
+def _level_size(smatrices, interp, l):
+    """rows of level l: of its matrix, or, for a Galerkin level, the columns of the prolongation onto the finer level"""
+    if not isinstance(smatrices[l], Galerkin):
+        return int(smatrices[l].shape[0])
+    ip = interp[l - 1]
+    return int((ip.P if isinstance(ip, PatchProlongationOperator) else ip).shape[1])
+
+
+def galerkin_pattern(R, A, P):
+    """gmg_galerkin_pattern on the stored patterns of R (nc x nf), A (nf x nf), P (nf x nc) (poisson.CSR, scipy CSR, ...; explicit zeros
+    count, rows in any order) -> ((tptr, tcol), (cptr, ccol)): the patterns of T = A P and of R A P, columns ascending, as the
+    symbolic phase of a Galerkin level builds them.  Host only: no handle, no GPU."""
+    pats = []
+    for M in (R, A, P):
+        shape, ptr, idx, _val, layout, base = _csr_fields(M)
+        if layout != abi.CSR:
+            raise ValueError("galerkin_pattern: CSR operands")
+        pats.append((shape, np.ascontiguousarray(ptr, dtype=np.int64) - base, np.ascontiguousarray(idx, dtype=np.int32) - np.int32(base)))
+    (rs, rp, rc), (as_, ap, ac), (ps, pp, pc) = pats
+    nc, nf = int(rs[0]), int(as_[0])
+    if not (as_[0] == as_[1] == rs[1] == ps[0] and ps[1] == nc):
+        raise ValueError("galerkin_pattern: the shapes of R, A and P do not chain to a square matrix")
+    lib = abi.load()
+    args = [nc, nf] + [C.c_void_p(a.ctypes.data) for a in (rp, rc, ap, ac, pp, pc)]
+    tn, cn = C.c_int64(0), C.c_int64(0)
+    abi.check(None, lib.gmg_galerkin_pattern(*args, None, None, 0, C.byref(tn), None, None, 0, C.byref(cn)))
+    tptr, tcol = np.empty(nf + 1, dtype=np.int64), np.empty(tn.value, dtype=np.int32)
+    cptr, ccol = np.empty(nc + 1, dtype=np.int64), np.empty(cn.value, dtype=np.int32)
+    abi.check(None, lib.gmg_galerkin_pattern(*args, C.c_void_p(tptr.ctypes.data), C.c_void_p(tcol.ctypes.data), tn.value, C.byref(tn),
+                                             C.c_void_p(cptr.ctypes.data), C.c_void_p(ccol.ctypes.data), cn.value, C.byref(cn)))
+    return (tptr, tcol), (cptr, ccol)
+
+
 class LinearSolverFromSmoother:
     """LinearSolverFromSmoother(smoother) -- LinearSolverFromSmoothers.jl:2-4: x = 0; r = copy(b); solve!(x,smoother,r)."""
 
@@ -326,7 +370,8 @@ class GMGLinearSolver:
     smatrices / interp / restrict are sequences of CSR-like objects with fields
     (shape, ptr, idx, val), 0-based (e.g. poisson.CSR or scipy.sparse.csr_matrix
     via `from_scipy`).  restrict=None means R = P^T (the :residual-mode transfer of
-    GridTransferOperators.jl:202-209 on nested meshes)."""
+    GridTransferOperators.jl:202-209 on nested meshes).  An entry of smatrices[1:] may be Galerkin(): that level's matrix is
+    R (A P) of the finer level, formed on the device."""
 
     def __init__(self, smatrices, interp, restrict=None, pre_smoothers=None, post_smoothers=None,
                  coarsest_solver=None, mode="preconditioner", cycle_type="v_cycle",
@@ -341,6 +386,8 @@ class GMGLinearSolver:
         # @check length(smatrices)-1 == length(interp) == ... (GMGLinearSolvers.jl:59)
         if not (nlev - 1 == len(interp) == len(restrict) == len(pre_smoothers) == len(post_smoothers)):
             raise ValueError("length(smatrices)-1 must equal the number of transfer operators and smoothers")
+        if nlev and isinstance(smatrices[0], Galerkin):
+            raise ValueError("smatrices[0]: the finest level has no finer level to form a Galerkin product from")
         if mode not in _MODES:          # :60
             raise ValueError("mode must be 'preconditioner' or 'solver'")
         if cycle_type not in _CYCLES:   # :61
@@ -352,9 +399,9 @@ class GMGLinearSolver:
             if not (coarsest_solver.constrain_matrix and isinstance(coarsest_solver.solver, LUSolver)):
                 raise NotImplementedError("coarsest_solver: NullspaceSolver(LUSolver(), N_coarse) with constrain_matrix=True "
                                           "(an iterative coarsest solver needs no constraint: CGSolver(JacobiLinearSolver()))")
-            if coarsest_solver.nullspace.size()[1] != int(smatrices[-1].shape[0]):
+            if coarsest_solver.nullspace.size()[1] != _level_size(smatrices, interp, nlev - 1):
                 raise ValueError(f"coarsest_solver: the null space has vectors of length {coarsest_solver.nullspace.size()[1]}, "
-                                 f"the coarsest matrix {int(smatrices[-1].shape[0])} rows")
+                                 f"the coarsest matrix {_level_size(smatrices, interp, nlev - 1)} rows")
         elif coarsest_solver is not None and not isinstance(coarsest_solver, (LUSolver, HostCallbackSolver)):
             if not (isinstance(coarsest_solver, CGSolver) and isinstance(coarsest_solver.Pl, JacobiLinearSolver)
                     and not coarsest_solver.flexible):
@@ -828,7 +875,10 @@ class GMGNumericalSetup:
         if mat is not None:
             mats[0] = mat  # smatrices[1] = mat, GMGLinearSolvers.jl:338
         for l, A in enumerate(mats):
-            _set_op(lib.gmg_set_matrix, h, l, A)
+            if isinstance(A, Galerkin):
+                abi.check(h, lib.gmg_set_galerkin(h, l))
+            else:
+                _set_op(lib.gmg_set_matrix, h, l, A)
         for l in range(nlev - 1):
             ip = s.interp[l]
             if isinstance(ip, PatchProlongationOperator):
@@ -874,7 +924,7 @@ class GMGNumericalSetup:
             abi.check(h, lib.gmg_set_coarse_nullspace(h, Kc.shape[0], C.c_void_p(Kc.ctypes.data), Kc.shape[1]))
         abi.check(h, lib.gmg_setup(h))
         self.n = int(mats[0].shape[0])
-        self.sizes = [int(A.shape[0]) for A in mats]
+        self.sizes = [_level_size(mats, s.interp, l) for l in range(nlev)]
 
     def _set_gs_ordering(self, l, pre, post):
         """one visiting order per level (gmg_set_gs_ordering): the one its Gauss-Seidel smoother(s) name"""
@@ -942,10 +992,14 @@ class GMGNumericalSetup:
     #    (GMGLinearSolvers.jl:249-258 logs @error); here new values on the same pattern are accepted.
     def update(self, mat, smatrices=None):
         """numerical_setup!(ns, A): new values on the same sparsity.  `smatrices` (optional) = the re-assembled matrices of ALL
-        levels, as the FromWeakform variant recomputes them (GMGLinearSolvers.jl:260-297); default: only the finest changes."""
+        levels, as the FromWeakform variant recomputes them (GMGLinearSolvers.jl:260-297); default: only the finest changes.
+        Galerkin levels follow the new values of the levels above them; their entry of `smatrices` is None or Galerkin()."""
         mats = [mat] if smatrices is None else [mat] + list(smatrices[1:])
         for l, M in enumerate(mats):
-            if M is None:
+            if M is not None and not isinstance(M, Galerkin) and isinstance(self.solver.smatrices[l], Galerkin):
+                raise ValueError(f"smatrices[{l}]: level {l} is a Galerkin level, its matrix is formed from the finer level's")
+        for l, M in enumerate(mats):
+            if M is None or isinstance(M, Galerkin):
                 continue
             shape, ptr, idx, val, layout, base = _csr_fields(M)
             if layout == abi.CSC:           # values in the caller's CSC order (the level was set in CSC layout): scattered by the library
@@ -1070,6 +1124,22 @@ class GMGNumericalSetup:
         abi.check(self.h, self._lib.gmg_level_format(self.h, lev, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(e)))
         return dict(layout=("CSR-stream", "SELL-64", "SELL-P", "SELL-O")[a.value], row_patterns=(a.value == 2),
                     value_dictionary=bool(b.value), idx16=bool(c.value), stream_bytes_per_nnz=d.value, padding=e.value)
+
+    def level_matrix(self, lev):
+        """gmg_get_galerkin_matrix: the matrix of a Galerkin level as the last setup formed it -> (shape, ptr, idx, val), 0-based CSR
+        with int64 pointers and int32 columns."""
+        n, nnz = C.c_int64(), C.c_int64()
+        abi.check(self.h, self._lib.gmg_get_galerkin_matrix(self.h, lev, C.byref(n), C.byref(nnz), None, None, None, 0))
+        ptr, idx, val = np.empty(n.value + 1, dtype=np.int64), np.empty(nnz.value, dtype=np.int32), np.empty(nnz.value)
+        abi.check(self.h, self._lib.gmg_get_galerkin_matrix(self.h, lev, C.byref(n), C.byref(nnz), C.c_void_p(ptr.ctypes.data),
+                                                            C.c_void_p(idx.ctypes.data), C.c_void_p(val.ctypes.data), nnz.value))
+        return (n.value, n.value), ptr, idx, val
+
+    def galerkin_timing(self, lev):
+        """gmg_get_galerkin_timing: what the last product of a Galerkin level cost, in ms"""
+        s, a, r = C.c_double(), C.c_double(), C.c_double()
+        abi.check(self.h, self._lib.gmg_get_galerkin_timing(self.h, lev, C.byref(s), C.byref(a), C.byref(r)))
+        return dict(symbolic_ms=s.value, ap_ms=a.value, rt_ms=r.value)
 
     def sweep_signature(self, lev=0):
         buf = C.create_string_buffer(256)

@@ -143,6 +143,42 @@ GMG_API int gmg_set_restriction(gmg_handle_t h, int lev, int64_t nrows, int64_t 
                                 const void *ptr, const void *idx, const double *val,
                                 int layout, int index_base, int index_bytes);
 
+/* Galerkin coarse matrices: level lev (1 .. nlevels-1) takes A_lev = R (A P) of level lev-1 instead of a matrix of the caller's --
+ * the algebraic alternative of hypre / AMGX / PETSc PCMG to GMGLinearSolverFromMatrices (GMGLinearSolvers.jl:336-340), which needs
+ * the assembled matrix of every level.  No reference counterpart.  In two stages, bit for bit:
+ *   T = A P        T(i, J) = sum over k ascending of A(i, k) * P(k, J)
+ *   A_lev = R T    A_lev(I, J) = sum over i ascending of R(I, i) * T(i, J)
+ * every sum from 0.0, every product and every sum rounded separately, only stored entries contribute.  The patterns are the structural
+ * products pattern(A) pattern(P) and pattern(R) pattern(T): explicit zeros of the inputs count, an entry whose terms cancel to 0.0
+ * stays stored, columns ascend in every row.  R is the restriction of level lev-1 if one was set, else P^T.  Inputs with unsorted rows
+ * are sorted in temporary copies (a column stored twice in a row: GMG_ERR_INVALID at gmg_setup).  Levels chain: level 2 from a
+ * Galerkin level 1.
+ * gmg_set_galerkin clears a matrix set earlier on the level; a later gmg_set_matrix / gmg_set_operator_rows on it clears the mark.
+ * Level 0: GMG_ERR_INVALID.  gmg_update_values[_csc] on such a level: GMG_ERR_STATE.
+ * The products are formed at the start of gmg_setup, finest first: patterns on the host, once per structure (kept until an operator
+ * the product reads is set again), values on the device by two launches of a gather kernel, one lane per stored entry, no atomics.
+ * The level is then treated exactly as if the caller had passed that matrix to gmg_set_matrix (layout choice included), the device
+ * temporaries are freed: gmg_device_bytes equals that of a handle given the same matrices.  After gmg_update_values[_csc] on a finer
+ * level the next gmg_setup forms the values again (numeric phase only) and hands them on as gmg_update_values would, so the usual
+ * rule decides between the in-place value refresh and a full setup.  The values pass through the host.
+ * Refused at gmg_setup with GMG_ERR_UNSUPPORTED, naming the level: a communicator of more than one rank, real or loopback (the local
+ * rows do not hold the off-rank terms); a matrix or transfer of the finer level that the caller streamed with gmg_set_operator_rows
+ * (no rows to take; a matrix gmg_set_matrix keeps in row-pattern form gives its rows back).  A missing prolongation: GMG_ERR_STATE. */
+GMG_API int gmg_set_galerkin(gmg_handle_t h, int lev);
+/* The matrix of a Galerkin level after gmg_setup, 0-based CSR: ptr[nrows + 1], col[nnz], val[nnz].  All three arrays NULL: size
+ * query.  cap_nnz < nnz: GMG_ERR_INVALID.  A level that is not Galerkin: GMG_ERR_STATE.  Any output may be NULL. */
+GMG_API int gmg_get_galerkin_matrix(gmg_handle_t h, int lev, int64_t *nrows, int64_t *nnz, int64_t *ptr, int32_t *col, double *val,
+                                    int64_t cap_nnz);
+/* What the last product of the level cost: host time of the symbolic phase (0 where the patterns were kept) and the HIP-event times
+ * of the two launches (T = A P, A_lev = R T), in ms.  Any output may be NULL. */
+GMG_API int gmg_get_galerkin_timing(gmg_handle_t h, int lev, double *symbolic_ms, double *ap_ms, double *rt_ms);
+/* The symbolic phase itself, without a handle and without a GPU: 0-based CSR patterns of R (nc x nf), A (nf x nf), P (nf x nc), rows in
+ * any order -> the patterns of T = A P (tptr[nf + 1], tcol) and of R A P (cptr[nc + 1], ccol), columns ascending.  *tnnz / *cnnz: the
+ * entry counts; all four arrays NULL: size query; tcap / ccap smaller than that: GMG_ERR_INVALID.  gmg_setup calls the same code. */
+GMG_API int gmg_galerkin_pattern(int64_t nc, int64_t nf, const int64_t *rptr, const int32_t *rcol, const int64_t *aptr,
+                                 const int32_t *acol, const int64_t *pptr, const int32_t *pcol, int64_t *tptr, int32_t *tcol,
+                                 int64_t tcap, int64_t *tnnz, int64_t *cptr, int32_t *ccol, int64_t ccap, int64_t *cnnz);
+
 /* ---- smoothers ------------------------------------------------------------- */
 /* RichardsonSmoother(JacobiLinearSolver(),niter,omega): RichardsonSmoothers.jl:84-98,
  * JacobiLinearSolvers.jl:20-23,43-47. */
