@@ -403,38 +403,28 @@ double *gmg_solver::cheb_pass(int l, Smoother &S, double *x, const double *r_in,
       const int grid = grid_for(vec ? (n + 1) / 2 : n);
       if (pack) {
         const HaloPlan &H = L.halo;
-#define CHEB_PACK_LAUNCH(F, D) hipLaunchKernelGGL((cheb_update_pack_kernel<F, D>), dim3(grid), dim3(256), 0, stream, n, a, b, q, z, d, x, xz, vec, \
-                                                  L.bidx, H.d_pk_ptr, H.d_pk_slot, H.d_sendbuf)
-        if (first) { if (jac) CHEB_PACK_LAUNCH(true, true); else CHEB_PACK_LAUNCH(true, false); }
-        else { if (jac) CHEB_PACK_LAUNCH(false, true); else CHEB_PACK_LAUNCH(false, false); }
-#undef CHEB_PACK_LAUNCH
+        with_bools([&](auto F, auto D) { hipLaunchKernelGGL((cheb_update_pack_kernel<F(), D()>), dim3(grid), dim3(256), 0, stream, n, a, b, q, z, d, x, xz, vec,
+                                                            L.bidx, H.d_pk_ptr, H.d_pk_slot, H.d_sendbuf); }, first, jac);
       } else {
-#define CHEB_LAUNCH(F, D) hipLaunchKernelGGL((cheb_update_kernel<F, D>), dim3(grid), dim3(256), 0, stream, n, a, b, q, z, d, x, xz, vec)
-        if (first) { if (jac) CHEB_LAUNCH(true, true); else CHEB_LAUNCH(true, false); }
-        else { if (jac) CHEB_LAUNCH(false, true); else CHEB_LAUNCH(false, false); }
-#undef CHEB_LAUNCH
+        with_bools([&](auto F, auto D) { hipLaunchKernelGGL((cheb_update_kernel<F(), D()>), dim3(grid), dim3(256), 0, stream, n, a, b, q, z, d, x, xz, vec); }, first, jac);
       }
     } else if (contrib_form) {
       patch_contrib(S, r);
       const int grid = (int)std::max<int64_t>(1, (n + 255) / 256);
       if (S.d_isoff) {
-        if (first) hipLaunchKernelGGL((patch_gather_sell_cheb_kernel<true>), dim3(grid), dim3(256), 0, stream, n, S.d_isoff, S.d_isinc, S.d_contrib, a, b, xz, d, x);
-        else hipLaunchKernelGGL((patch_gather_sell_cheb_kernel<false>), dim3(grid), dim3(256), 0, stream, n, S.d_isoff, S.d_isinc, S.d_contrib, a, b, xz, d, x);
+        with_bool(first, [&](auto F) { hipLaunchKernelGGL((patch_gather_sell_cheb_kernel<F()>), dim3(grid), dim3(256), 0, stream, n, S.d_isoff, S.d_isinc, S.d_contrib, a, b, xz, d, x); });
       } else {
-        if (first) hipLaunchKernelGGL((patch_gather_cheb_kernel<true>), dim3(grid), dim3(256), 0, stream, n, S.d_iptr, S.d_inc, S.d_contrib, a, b, xz, d, x);
-        else hipLaunchKernelGGL((patch_gather_cheb_kernel<false>), dim3(grid), dim3(256), 0, stream, n, S.d_iptr, S.d_inc, S.d_contrib, a, b, xz, d, x);
+        with_bool(first, [&](auto F) { hipLaunchKernelGGL((patch_gather_cheb_kernel<F()>), dim3(grid), dim3(256), 0, stream, n, S.d_iptr, S.d_inc, S.d_contrib, a, b, xz, d, x); });
       }
     } else if (S.kind == SM_PATCH) {
       spmv_set(S.M, r, zbuf);
       const int vec = (aligned16(zbuf) && aligned16(d) && aligned16(x)) ? 1 : 0;
       const int grid = grid_for(vec ? (n + 1) / 2 : n);
-      if (first) hipLaunchKernelGGL((cheb_update_kernel<true, false>), dim3(grid), dim3(256), 0, stream, n, a, b, (const double *)nullptr, zbuf, d, x, xz, vec);
-      else hipLaunchKernelGGL((cheb_update_kernel<false, false>), dim3(grid), dim3(256), 0, stream, n, a, b, (const double *)nullptr, zbuf, d, x, xz, vec);
+      with_bool(first, [&](auto F) { hipLaunchKernelGGL((cheb_update_kernel<F(), false>), dim3(grid), dim3(256), 0, stream, n, a, b, (const double *)nullptr, zbuf, d, x, xz, vec); });
     } else {
       const int vec = (aligned16(L.dinv) && aligned16(r) && aligned16(d) && aligned16(x)) ? 1 : 0;
       const int grid = grid_for(vec ? (n + 1) / 2 : n);
-      if (first) hipLaunchKernelGGL((cheb_update_kernel<true, true>), dim3(grid), dim3(256), 0, stream, n, a, b, L.dinv, r, d, x, xz, vec);
-      else hipLaunchKernelGGL((cheb_update_kernel<false, true>), dim3(grid), dim3(256), 0, stream, n, a, b, L.dinv, r, d, x, xz, vec);
+      with_bool(first, [&](auto F) { hipLaunchKernelGGL((cheb_update_kernel<F(), true>), dim3(grid), dim3(256), 0, stream, n, a, b, L.dinv, r, d, x, xz, vec); });
     }
     HIP_CHECK(hipGetLastError());
     apply_A_sub(l, d, r, nullptr, pack);                     // (the distributed product: exchanges d, prepacked where the update packed it)

@@ -18,6 +18,7 @@
 #include "../../include/gmg_amd.h"
 #include "kernels.hpp"
 #include "comm.hpp"
+#include "dispatch.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -1785,6 +1786,21 @@ struct gmg_solver {
     r2mv_dot_parts = nullptr;
     return r2mv_dot_n > 0 ? r2mv_dot_n : -1;                 // -1: y = M x is done, the dot is not (a grid of more than kRedBlocks workgroups)
   }
+  // the fields every SELL launcher takes over from the caller's arguments as they are
+  template <class Args>
+  static void take_stream_args(Args &a, const StreamArgs2 &a2)
+  {
+    a.x_zero = a2.x_zero; a.x = a2.x; a.dinv = a2.dinv; a.omega = a2.omega; a.y = a2.y; a.b = a2.b; a.x2 = a2.x2; a.s_out = a2.s_out;
+  }
+  // dynamic LDS beyond the 64 KB default: the limit of a kernel is raised once per instantiation and device
+  template <auto Kernel>
+  void allow_lds(int bytes)
+  {
+    static bool done[64] = {false};
+    if (done[device & 63]) return;
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    done[device & 63] = true;
+  }
   template <int EPI, bool ONEG>
   void launch_sells(const DevCSR &M, const StreamArgs2 &a2)
   {
@@ -1797,8 +1813,8 @@ struct gmg_solver {
     const int rows = 65 - M.pat_k;
     const int nsl = (int)((M.nrows + rows - 1) / rows);
     a.nrows = M.nrows; a.ncols = M.ncols; a.nslices = nsl; a.xcd_remap = xcd_remap;
-    a.x_zero = a2.x_zero; a.x = a2.x; a.dinv = a2.dinv; a.omega = a2.omega; a.y = a2.y; a.b = a2.b; a.x2 = a2.x2; a.s_out = a2.s_out;
-    const int wpb = sell_block > 0 ? sell_block / 64 : (nsl >= 256 * 32 ? 4 : pat_small_wpb);
+    take_stream_args(a, a2);
+    const int wpb = sells_wpb(nsl);
     const int nwg = std::max(1, std::min((nsl + wpb - 1) / wpb, pat_wgs));
     const int nu = M.pat_k * M.pat_nruns;
     const size_t lds = M.pat_coded ? (size_t)2048 + (((size_t)M.pat_np * nu + 7) / 8) * 8 + (size_t)M.pat_np * 12 + 8
@@ -1812,7 +1828,7 @@ struct gmg_solver {
         // (the 64-register form of the sweeps, pat_r2_occ, does not pay here: 14.8 -> 15.3 us)
         const dim3 gr(std::max(1, std::min((nsl2 + wpb - 1) / wpb, pat_r2_wgs > 0 ? pat_r2_wgs : 4 * n_cus)));
         const size_t lds2 = (size_t)M.pat_np * nu * 16 + 16;
-        const bool mk = pat_strict || !M.ptab8;
+        const bool mk = pat_strict || !M.ptab8, fm = pat_fma != 0;
         // big levels (>= pat_tile_rows rows), no fused dot asked for: one slice per wave in workgroups of eight waves, 64-register form
         // (as the sweeps of these levels: launch_rsweep)
         bool dot_here = false;
@@ -1822,46 +1838,28 @@ struct gmg_solver {
         if (pat_zwalk && pat_zwalk_mv && !dot_here && (pat_zwalk >= 2 || M.nrows >= pat_zwalk_rows) && zwalk_geo(M, zg)) {
           const dim3 gz((unsigned)((zg.nchains + 3) / 4)), bz(256);
           const size_t ldsz = (size_t)M.pat_np * 28 * 8 + 16;
-          if (mk) { if (pat_fma) hipLaunchKernelGGL((sells_zsweep_kernel<1, true, true, EPI>), gz, bz, ldsz, stream, a, zg);
-                    else hipLaunchKernelGGL((sells_zsweep_kernel<1, true, false, EPI>), gz, bz, ldsz, stream, a, zg); }
-          else { if (pat_fma) hipLaunchKernelGGL((sells_zsweep_kernel<1, false, true, EPI>), gz, bz, ldsz, stream, a, zg);
-                 else hipLaunchKernelGGL((sells_zsweep_kernel<1, false, false, EPI>), gz, bz, ldsz, stream, a, zg); }
+          with_bools([&](auto MK, auto FM) { hipLaunchKernelGGL((sells_zsweep_kernel<1, MK(), FM(), EPI>), gz, bz, ldsz, stream, a, zg); }, mk, fm);
           HIP_CHECK(hipGetLastError());
           return;
         }
         if (pat_r2_occ >= 2 && M.nrows >= pat_tile_rows && M.pat_nruns == 9 && pat_r2_wgs <= 0 && !dot_here) {
           const dim3 g8((nsl2 + 7) / 8), b8(512);
-          if (mk) { if (pat_fma) hipLaunchKernelGGL((sells_r2mv_kernel<EPI, true, true, 9, false, 2>), g8, b8, lds2, stream, a);
-                    else hipLaunchKernelGGL((sells_r2mv_kernel<EPI, true, false, 9, false, 2>), g8, b8, lds2, stream, a); }
-          else { if (pat_fma) hipLaunchKernelGGL((sells_r2mv_kernel<EPI, false, true, 9, false, 2>), g8, b8, lds2, stream, a);
-                 else hipLaunchKernelGGL((sells_r2mv_kernel<EPI, false, false, 9, false, 2>), g8, b8, lds2, stream, a); }
+          with_bools([&](auto MK, auto FM) { hipLaunchKernelGGL((sells_r2mv_kernel<EPI, MK(), FM(), 9, false, 2>), g8, b8, lds2, stream, a); }, mk, fm);
           HIP_CHECK(hipGetLastError());
           return;
         }
-#define GMG_R2MV_LAUNCH(MKV, FMV)                                                                              \
-        do {                                                                                                     \
-          if (M.pat_nruns == 9) hipLaunchKernelGGL((sells_r2mv_kernel<EPI, MKV, FMV, 9>), gr, b, lds2, stream, a);   \
-          else hipLaunchKernelGGL((sells_r2mv_kernel<EPI, MKV, FMV, 3>), gr, b, lds2, stream, a);                \
-        } while (0)
         if constexpr (EPI == EPI_SET) {
           if (r2mv_dot_parts && gr.x <= (unsigned)kRedBlocks) {   // the first stage of dot(x, A x) rides along (spmv_set_dot)
             a.s_out = r2mv_dot_parts;
             r2mv_dot_n = (int)gr.x;
-#define GMG_R2MV_DOT(MKV, FMV)                                                                                 \
-            do {                                                                                                 \
-              if (M.pat_nruns == 9) hipLaunchKernelGGL((sells_r2mv_kernel<EPI_SET, MKV, FMV, 9, true>), gr, b, lds2, stream, a);   \
-              else hipLaunchKernelGGL((sells_r2mv_kernel<EPI_SET, MKV, FMV, 3, true>), gr, b, lds2, stream, a);  \
-            } while (0)
-            if (mk) { if (pat_fma) GMG_R2MV_DOT(true, true); else GMG_R2MV_DOT(true, false); }
-            else { if (pat_fma) GMG_R2MV_DOT(false, true); else GMG_R2MV_DOT(false, false); }
-#undef GMG_R2MV_DOT
+            with_bools([&](auto MK, auto FM) { with_value<9, 3>(M.pat_nruns, [&](auto NR) {
+              hipLaunchKernelGGL((sells_r2mv_kernel<EPI_SET, MK(), FM(), NR(), true>), gr, b, lds2, stream, a); }); }, mk, fm);
             HIP_CHECK(hipGetLastError());
             return;
           }
         }
-        if (mk) { if (pat_fma) GMG_R2MV_LAUNCH(true, true); else GMG_R2MV_LAUNCH(true, false); }
-        else { if (pat_fma) GMG_R2MV_LAUNCH(false, true); else GMG_R2MV_LAUNCH(false, false); }
-#undef GMG_R2MV_LAUNCH
+        with_bools([&](auto MK, auto FM) { with_value<9, 3>(M.pat_nruns, [&](auto NR) {
+          hipLaunchKernelGGL((sells_r2mv_kernel<EPI, MK(), FM(), NR()>), gr, b, lds2, stream, a); }); }, mk, fm);
         HIP_CHECK(hipGetLastError());
         return;
       }
@@ -1875,20 +1873,9 @@ struct gmg_solver {
       const dim3 g2(wg2);
       const size_t lds2 = (size_t)M.pat_np * nu * 16 + (size_t)M.pat_np * 8 + 16;    // 16-byte {value, mask} entries
       const bool mk = pat_strict || !M.ptab8;
-#define GMG_SWEEP_LAUNCH(XMV, NBV)                                                                             \
-      do {                                                                                                       \
-        if (mk) {                                                                                                \
-          if (td) hipLaunchKernelGGL((sells_sweep_kernel<XMV, NBV, true, true>), g2, b, lds2, stream, a);        \
-          else hipLaunchKernelGGL((sells_sweep_kernel<XMV, NBV, false, true>), g2, b, lds2, stream, a);          \
-        } else {                                                                                                 \
-          if (td) hipLaunchKernelGGL((sells_sweep_kernel<XMV, NBV, true, false>), g2, b, lds2, stream, a);       \
-          else hipLaunchKernelGGL((sells_sweep_kernel<XMV, NBV, false, false>), g2, b, lds2, stream, a);         \
-        }                                                                                                        \
-      } while (0)
       M.note_sweep("sells_sweep_kernel<XM=*,NB=%d,TD=%d,MK=%d> wgs=%d wpb=%d", nb >= 2 ? 2 : 1, td ? 1 : 0, mk ? 1 : 0, wg2, wpb);
-      if (nb >= 2) { if (a.xmode == 0) GMG_SWEEP_LAUNCH(0, 2); else if (a.xmode == 1) GMG_SWEEP_LAUNCH(1, 2); else GMG_SWEEP_LAUNCH(2, 2); }
-      else { if (a.xmode == 0) GMG_SWEEP_LAUNCH(0, 1); else if (a.xmode == 1) GMG_SWEEP_LAUNCH(1, 1); else GMG_SWEEP_LAUNCH(2, 1); }
-#undef GMG_SWEEP_LAUNCH
+      with_value<2, 1>(nb >= 2 ? 2 : 1, [&](auto NB) { with_value<0, 1, 2>(a.xmode, [&](auto XM) { with_bools([&](auto MK, auto TD) {
+        hipLaunchKernelGGL((sells_sweep_kernel<XM(), NB(), TD(), MK()>), g2, b, lds2, stream, a); }, mk, td); }); });
       HIP_CHECK(hipGetLastError());
       return;
     }
@@ -1903,16 +1890,10 @@ struct gmg_solver {
           }
           a.wl_pids = M.wz_pids; a.wl_cnt = M.wz_cnt; a.wl_stride = kWideStride; a.wl_max = M.wz_max;
           const size_t ldsz = wide_z_lds(M, M.wz_max);
-          static bool attr_z[64] = {false};
-          if (!attr_z[device & 63]) {
-            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sellw_zwalk_kernel<EPI, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sellw_zwalk_kernel<EPI, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-            attr_z[device & 63] = true;
-          }
           M.note_op("sellw_zwalk_kernel<EPI=%d,FM=%d> wgs=%d", (int)EPI, pat_fma ? 1 : 0, nwz);
-          if (pat_fma) hipLaunchKernelGGL((sellw_zwalk_kernel<EPI, true>), dim3((unsigned)nwz), dim3(256), ldsz, stream, a, M.wz_geo);
-          else
-          hipLaunchKernelGGL((sellw_zwalk_kernel<EPI, false>), dim3((unsigned)nwz), dim3(256), ldsz, stream, a, M.wz_geo);
+          with_value<0, 1>(pat_fma ? 1 : 0, [&](auto FM) {          // (the plain form first: the order the code object lists the two in)
+            allow_lds<&sellw_zwalk_kernel<EPI, FM() != 0>>(96 * 1024);
+            hipLaunchKernelGGL((sellw_zwalk_kernel<EPI, FM() != 0>), dim3((unsigned)nwz), dim3(256), ldsz, stream, a, M.wz_geo); });
           HIP_CHECK(hipGetLastError());
           return;
         }
@@ -1923,20 +1904,13 @@ struct gmg_solver {
       const dim3 g(nwg_wide);
       a.wl_pids = M.wl_pids; a.wl_cnt = M.wl_cnt; a.wl_stride = kWideStride; a.wl_max = M.wl_max;
       const size_t ldsw = wide_lds(M, M.wl_max);
-      static bool attr_set[64] = {false};                   // per instantiation and device: LDS beyond the 64 KB default
-      if (!attr_set[device & 63]) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sells_kernel<EPI, ONEG, 5, 5, true, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        attr_set[device & 63] = true;
-      }
-      if (opt_int("GMG_DBG_NOGATHER", 0)) hipLaunchKernelGGL((sells_kernel<EPI, ONEG, 5, 5, true, 8, true>), g, b, ldsw, stream, a);   // timing ablation only
-      else
-      hipLaunchKernelGGL((sells_kernel<EPI, ONEG, 5, 5, true, 0, true>), g, b, ldsw, stream, a);
+      allow_lds<&sells_kernel<EPI, ONEG, 5, 5, true, 0, true>>(96 * 1024);
+      with_value<8, 0>(opt_int("GMG_DBG_NOGATHER", 0) ? 8 : 0, [&](auto DBG) {   // (8: timing ablation only)
+        hipLaunchKernelGGL((sells_kernel<EPI, ONEG, 5, 5, true, DBG(), true>), g, b, ldsw, stream, a); });
     } else
     if (M.pat_coded && M.pat_k == 5) hipLaunchKernelGGL((sells_kernel<EPI, ONEG, 5, 5, true>), g, b, lds, stream, a);
     else if (M.pat_coded) hipLaunchKernelGGL((sells_kernel<EPI, ONEG, 3, 3, true>), g, b, lds, stream, a);
-    else if (pat_rb == 9) hipLaunchKernelGGL((sells_kernel<EPI, ONEG, 9>), g, b, lds, stream, a);
-    else if (pat_rb == 1) hipLaunchKernelGGL((sells_kernel<EPI, ONEG, 1>), g, b, lds, stream, a);
-    else hipLaunchKernelGGL((sells_kernel<EPI, ONEG, 3>), g, b, lds, stream, a);
+    else with_value<9, 1, 3>(pat_rb, [&](auto RB) { hipLaunchKernelGGL((sells_kernel<EPI, ONEG, RB()>), g, b, lds, stream, a); });
     HIP_CHECK(hipGetLastError());
   }
   template <int EPI, bool ONEG>
@@ -1948,7 +1922,7 @@ struct gmg_solver {
     std::memset(&a, 0, sizeof(a));
     a.rowpid = M.rowpid; a.rowbase = M.rowbase; a.plen = M.plen; a.poff = M.ppoff; a.pval = M.ppval; a.np = M.pat_np; a.W = M.pat_w;
     a.nrows = M.nrows; a.nslices = M.nslices; a.xcd_remap = xcd_remap;
-    a.x_zero = a2.x_zero; a.x = a2.x; a.dinv = a2.dinv; a.omega = a2.omega; a.y = a2.y; a.b = a2.b; a.x2 = a2.x2; a.s_out = a2.s_out;
+    take_stream_args(a, a2);
     // persistent launch: the pattern table is staged into LDS once per workgroup
     const int wpb = sell_block > 0 ? sell_block / 64 : (M.nslices >= 256 * 32 ? 4 : pat_small_wpb2);
     const int nwg = std::max(1, std::min((M.nslices + wpb - 1) / wpb, pat_wgs));
@@ -1971,25 +1945,11 @@ struct gmg_solver {
       }
     }
     if (!M.pat_generic) {                                   // table kept in global memory / L2 (does not fit LDS)
-      switch (pat_un_eff()) {
-      case 27: hipLaunchKernelGGL((sellp_kernel<EPI, ONEG, 27, true>), g, b, 0, stream, a); break;
-      case 14: hipLaunchKernelGGL((sellp_kernel<EPI, ONEG, 14, true>), g, b, 0, stream, a); break;
-      case 9: hipLaunchKernelGGL((sellp_kernel<EPI, ONEG, 9, true>), g, b, 0, stream, a); break;
-      case 6: hipLaunchKernelGGL((sellp_kernel<EPI, ONEG, 6, true>), g, b, 0, stream, a); break;
-      default: hipLaunchKernelGGL((sellp_kernel<EPI, ONEG, 3, true>), g, b, 0, stream, a); break;
-      }
+      with_value<27, 14, 9, 6, 3>(pat_un_eff(), [&](auto UN) { hipLaunchKernelGGL((sellp_kernel<EPI, ONEG, UN(), true>), g, b, 0, stream, a); });
       HIP_CHECK(hipGetLastError());
       return;
     }
-#define GMG_SELLP_LAUNCH(UNV) hipLaunchKernelGGL((sellp_kernel<EPI, ONEG, UNV>), g, b, lds, stream, a)
-    switch (pat_un_eff()) {
-    case 27: GMG_SELLP_LAUNCH(27); break;
-    case 14: GMG_SELLP_LAUNCH(14); break;
-    case 9: GMG_SELLP_LAUNCH(9); break;
-    case 6: GMG_SELLP_LAUNCH(6); break;
-    default: GMG_SELLP_LAUNCH(3); break;
-    }
-#undef GMG_SELLP_LAUNCH
+    with_value<27, 14, 9, 6, 3>(pat_un_eff(), [&](auto UN) { hipLaunchKernelGGL((sellp_kernel<EPI, ONEG, UN()>), g, b, lds, stream, a); });
     HIP_CHECK(hipGetLastError());
   }
 
@@ -2171,17 +2131,11 @@ struct gmg_solver {
     std::memset(&a, 0, sizeof(a));
     a.soff = M.soff; a.poff = M.poff; a.scol = M.scol; a.sval = M.sval; a.pidx = M.pidx; a.pcode = M.pcode; a.pbase = M.pbase;
     a.smode = M.smode; a.dict = M.dict; a.rowlen = M.rowlen; a.nrows = M.nrows; a.nslices = M.nslices; a.xcd_remap = xcd_remap;
-    a.x_zero = a2.x_zero; a.x = a2.x; a.dinv = a2.dinv; a.omega = a2.omega; a.y = a2.y; a.b = a2.b; a.x2 = a2.x2; a.s_out = a2.s_out;
+    take_stream_args(a, a2);
     const int wpb = sell_block > 0 ? sell_block / 64 : (M.nslices >= 256 * 32 ? 4 : 1);
     const dim3 g((M.nslices + wpb - 1) / wpb), b(64 * wpb);
     const bool nt = nt_loads && (M.stream_bytes_per_nnz * (double)M.zpad > 192.0e6);
-    if (M.vdict) {
-      if (nt) hipLaunchKernelGGL((sellc_kernel<EPI, ONEG, true, true>), g, b, 0, stream, a);
-      else hipLaunchKernelGGL((sellc_kernel<EPI, ONEG, true, false>), g, b, 0, stream, a);
-    } else {
-      if (nt) hipLaunchKernelGGL((sellc_kernel<EPI, ONEG, false, true>), g, b, 0, stream, a);
-      else hipLaunchKernelGGL((sellc_kernel<EPI, ONEG, false, false>), g, b, 0, stream, a);
-    }
+    with_bools([&](auto VD, auto NT) { hipLaunchKernelGGL((sellc_kernel<EPI, ONEG, VD(), NT()>), g, b, 0, stream, a); }, M.vdict, nt);
     HIP_CHECK(hipGetLastError());
   }
   template <int EPI, bool ONEG>
@@ -2191,7 +2145,7 @@ struct gmg_solver {
     std::memset(&a, 0, sizeof(a));
     a.soff = M.soff; a.sval = M.sval; a.rowlen = M.rowlen; a.rowpid = M.orowpid; a.rowbase = M.orowbase; a.poff = M.opoff;
     a.np = M.opat_np; a.W = M.opat_w; a.nrows = M.nrows; a.nslices = M.nslices; a.xcd_remap = xcd_remap;
-    a.x_zero = a2.x_zero; a.x = a2.x; a.dinv = a2.dinv; a.omega = a2.omega; a.y = a2.y; a.b = a2.b; a.x2 = a2.x2; a.s_out = a2.s_out;
+    take_stream_args(a, a2);
     const int wpb = sell_block > 0 ? sell_block / 64 : (M.nslices >= 256 * 32 ? 4 : 1);
     const dim3 g((M.nslices + wpb - 1) / wpb), b(64 * wpb);
     const size_t lds = (size_t)M.opat_np * M.opat_w * 4;
@@ -2200,32 +2154,17 @@ struct gmg_solver {
     if (huge) a.xcd_remap = remap_for_big(M, 64 * wpb, (int)g.x);
     if constexpr (EPI == EPI_SWEEP && ONEG) {
       if (sell_un < 27 && (a2.xmode != 0 || (huge && nt && nt_rowwise))) {
-#define GMG_SELLO_SWEEP(NTV)                                                                                                        \
-        do {                                                                                                                          \
-          if (a2.xmode == 1) hipLaunchKernelGGL((sello_kernel<EPI_SWEEP, true, 9, NTV, 1>), g, b, lds, stream, a);                    \
-          else if (a2.xmode == 2) hipLaunchKernelGGL((sello_kernel<EPI_SWEEP, true, 9, NTV, 2>), g, b, lds, stream, a);               \
-          else hipLaunchKernelGGL((sello_kernel<EPI_SWEEP, true, 9, NTV, 0>), g, b, lds, stream, a);                                  \
-        } while (0)
         M.note_sweep("sello_kernel<EPI_SWEEP,ONEG,UN=9,NT=%d,XM=*> wpb=%d remap=%d", (huge && nt && nt_rowwise) ? 2 : (nt ? 1 : 0), wpb, a.xcd_remap);
-        if (huge && nt && nt_rowwise) GMG_SELLO_SWEEP(2);
-        else if (nt) GMG_SELLO_SWEEP(1);
-        else GMG_SELLO_SWEEP(0);
-#undef GMG_SELLO_SWEEP
+        with_value<2, 1, 0>((huge && nt && nt_rowwise) ? 2 : (nt ? 1 : 0), [&](auto NT) { with_value<1, 2, 0>(a2.xmode, [&](auto XM) {
+          hipLaunchKernelGGL((sello_kernel<EPI_SWEEP, true, 9, NT(), XM()>), g, b, lds, stream, a); }); });
         HIP_CHECK(hipGetLastError());
         return;
       }
     }
     REQUIRE(a2.xmode == 0 || EPI != EPI_SWEEP, GMG_ERR_STATE, "deferred x update needs the default unroll of the SELL-O sweep");
-#define GMG_SELLO_LAUNCH(UNV)                                                                         \
-    do {                                                                                                \
-      if (nt) hipLaunchKernelGGL((sello_kernel<EPI, ONEG, UNV, 1>), g, b, lds, stream, a);               \
-      else hipLaunchKernelGGL((sello_kernel<EPI, ONEG, UNV, 0>), g, b, lds, stream, a);                  \
-    } while (0)
     if (EPI == EPI_SWEEP) M.note_sweep("sello_kernel<EPI_SWEEP,%s,UN=%d,NT=%d,XM=0> wpb=%d remap=%d", ONEG ? "ONEG" : "2G", sell_un >= 27 ? 27 : sell_un >= 9 ? 9 : 3, nt ? 1 : 0, wpb, a.xcd_remap);
-    if (sell_un >= 27) GMG_SELLO_LAUNCH(27);
-    else if (sell_un >= 9) GMG_SELLO_LAUNCH(9);
-    else GMG_SELLO_LAUNCH(3);
-#undef GMG_SELLO_LAUNCH
+    with_value<27, 9, 3>(sell_un >= 27 ? 27 : sell_un >= 9 ? 9 : 3, [&](auto UN) { with_value<1, 0>(nt ? 1 : 0, [&](auto NT) {
+      hipLaunchKernelGGL((sello_kernel<EPI, ONEG, UN(), NT()>), g, b, lds, stream, a); }); });
     HIP_CHECK(hipGetLastError());
   }
   template <int EPI, bool ONEG>
@@ -2237,7 +2176,7 @@ struct gmg_solver {
     SellArgs a;
     std::memset(&a, 0, sizeof(a));
     a.soff = M.soff; a.scol = M.scol; a.sval = M.sval; a.rowlen = M.rowlen; a.nrows = M.nrows; a.nslices = M.nslices; a.xcd_remap = xcd_remap;
-    a.x_zero = a2.x_zero; a.x = a2.x; a.dinv = a2.dinv; a.omega = a2.omega; a.y = a2.y; a.b = a2.b; a.x2 = a2.x2; a.s_out = a2.s_out;
+    take_stream_args(a, a2);
     // one wave per slice; small levels get single-wave workgroups so that they spread over all CUs
     const int wpb = sell_block > 0 ? sell_block / 64 : (M.nslices >= 256 * 32 ? 4 : 1);
     const dim3 g((M.nslices + wpb - 1) / wpb), b(64 * wpb);
@@ -2250,35 +2189,18 @@ struct gmg_solver {
     if constexpr (EPI == EPI_SWEEP && ONEG) {
       if (sell_un >= 6 && sell_un < 9 && (a2.xmode != 0 || (huge && nt && nt_rowwise))) {
         // default unroll: the variants with the deferred x update (a2.xmode) and non-temporal row-wise operands
-#define GMG_SELL_SWEEP(NTV)                                                                                                         \
-        do {                                                                                                                          \
-          if (a2.xmode == 1) hipLaunchKernelGGL((sell_kernel<EPI_SWEEP, true, 6, NTV, 1>), g, b, 0, stream, a);                       \
-          else if (a2.xmode == 2) hipLaunchKernelGGL((sell_kernel<EPI_SWEEP, true, 6, NTV, 2>), g, b, 0, stream, a);                  \
-          else hipLaunchKernelGGL((sell_kernel<EPI_SWEEP, true, 6, NTV, 0>), g, b, 0, stream, a);                                     \
-        } while (0)
         M.note_sweep("sell_kernel<EPI_SWEEP,ONEG,UN=6,NT=%d,XM=*> wpb=%d remap=%d", (huge && nt && nt_rowwise) ? 2 : (nt ? 1 : 0), wpb, a.xcd_remap);
-        if (huge && nt && nt_rowwise) GMG_SELL_SWEEP(2);
-        else if (nt) GMG_SELL_SWEEP(1);
-        else GMG_SELL_SWEEP(0);
-#undef GMG_SELL_SWEEP
+        with_value<2, 1, 0>((huge && nt && nt_rowwise) ? 2 : (nt ? 1 : 0), [&](auto NT) { with_value<1, 2, 0>(a2.xmode, [&](auto XM) {
+          hipLaunchKernelGGL((sell_kernel<EPI_SWEEP, true, 6, NT(), XM()>), g, b, 0, stream, a); }); });
         HIP_CHECK(hipGetLastError());
         return;
       }
     }
     REQUIRE(a2.xmode == 0 || EPI != EPI_SWEEP, GMG_ERR_STATE, "deferred x update needs the default unroll of the SELL-64 sweep");
-#define GMG_SELL_LAUNCH(UNV)                                                                          \
-    do {                                                                                                \
-      if (nt) hipLaunchKernelGGL((sell_kernel<EPI, ONEG, UNV, 1>), g, b, 0, stream, a);                  \
-      else hipLaunchKernelGGL((sell_kernel<EPI, ONEG, UNV, 0>), g, b, 0, stream, a);                     \
-    } while (0)
     if (EPI == EPI_SWEEP) M.note_sweep("sell_kernel<EPI_SWEEP,%s,UN=%d,NT=%d,XM=0> wpb=%d remap=%d", ONEG ? "ONEG" : "2G", sell_un, nt ? 1 : 0, wpb, a.xcd_remap);
-    if (sell_un >= 27) GMG_SELL_LAUNCH(27);
-    else if (sell_un >= 9) GMG_SELL_LAUNCH(9);
-    else if (sell_un >= 6) GMG_SELL_LAUNCH(6);
-    else if (sell_un >= 4) GMG_SELL_LAUNCH(4);
-    else if (sell_un >= 3) GMG_SELL_LAUNCH(3);
-    else GMG_SELL_LAUNCH(2);
-#undef GMG_SELL_LAUNCH
+    const int un = sell_un >= 27 ? 27 : sell_un >= 9 ? 9 : sell_un >= 6 ? 6 : sell_un >= 4 ? 4 : sell_un >= 3 ? 3 : 2;
+    with_value<27, 9, 6, 4, 3, 2>(un, [&](auto UN) { with_value<1, 0>(nt ? 1 : 0, [&](auto NT) {
+      hipLaunchKernelGGL((sell_kernel<EPI, ONEG, UN(), NT()>), g, b, 0, stream, a); }); });
     HIP_CHECK(hipGetLastError());
   }
 
@@ -2414,23 +2336,9 @@ struct gmg_solver {
     // that also update x have no registers to spare under the 64 the two resident workgroups allow (252.8 -> 282 us with it)
     const bool bc = pat_bcast && M.pat_nruns == 9 && M.pat_k == 3 && a.xmode == 1;
     M.note_sweep("sells_tsweep_kernel<XM=*,MK=%d,WPB=%d,FM=%d,BC=%d> T=%d tiles=%d wgs=%d segs=%d", mk ? 1 : 0, WPB, pat_fma ? 1 : 0, bc ? 1 : 0, T, ntiles, nwg, tl.nseg);
-#define GMG_TSWEEP_LAUNCH3(XMV, MKV, FMV, BCV)                                                                      \
-    do {                                                                                                              \
-      static bool attr[64] = {false};                                                                                 \
-      if (!attr[device & 63]) { HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sells_tsweep_kernel<XMV, MKV, WPB, FMV, BCV>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)); attr[device & 63] = true; } \
-      hipLaunchKernelGGL((sells_tsweep_kernel<XMV, MKV, WPB, FMV, BCV>), g, b, lds, stream, a, tl);                   \
-    } while (0)
-#define GMG_TSWEEP_LAUNCH2(XMV, MKV, FMV) do { if (bc) GMG_TSWEEP_LAUNCH3(XMV, MKV, FMV, true); else GMG_TSWEEP_LAUNCH3(XMV, MKV, FMV, false); } while (0)
-#define GMG_TSWEEP_LAUNCH(XMV)                                                                                      \
-    do {                                                                                                              \
-      if (mk) { if (pat_fma) GMG_TSWEEP_LAUNCH2(XMV, true, true); else GMG_TSWEEP_LAUNCH2(XMV, true, false); }        \
-      else { if (pat_fma) GMG_TSWEEP_LAUNCH2(XMV, false, true); else GMG_TSWEEP_LAUNCH2(XMV, false, false); }         \
-    } while (0)
-    if (a.xmode == 0) GMG_TSWEEP_LAUNCH(0); else if (a.xmode == 1) GMG_TSWEEP_LAUNCH(1); else GMG_TSWEEP_LAUNCH(2);
-#undef GMG_TSWEEP_LAUNCH
-#undef GMG_TSWEEP_LAUNCH3
-#undef GMG_TSWEEP_LAUNCH2
-#undef GMG_TSWEEP_LAUNCH2
+    with_value<0, 1, 2>(a.xmode, [&](auto XM) { with_bools([&](auto MK, auto FM, auto BC) {
+      allow_lds<&sells_tsweep_kernel<XM(), MK(), WPB, FM(), BC()>>(96 * 1024);
+      hipLaunchKernelGGL((sells_tsweep_kernel<XM(), MK(), WPB, FM(), BC()>), g, b, lds, stream, a, tl); }, mk, pat_fma != 0, bc); });
     HIP_CHECK(hipGetLastError());
     return true;
   }
@@ -2554,23 +2462,9 @@ struct gmg_solver {
     const dim3 gr((unsigned)(g.nzb * g.nyt * g.nxs)), b(64 * g.W);
     M.note_sweep("sells_z2sweep_kernel<MK=%d,FM=%d,BC=%d> (two sweeps per launch) wgs=%u W=%d T=%d tiles=%dx%dx%d L=%d", mk ? 1 : 0, pat_fma ? 1 : 0, bc ? 1 : 0, gr.x, g.W, g.T, g.nxs, g.nyt, g.nzb, g.L);
     REQUIRE(lds <= (size_t)150 * 1024, GMG_ERR_UNSUPPORTED, "sells_z2sweep_kernel: pattern table + ring exceed the LDS of a CU");
-    static bool attr[64] = {false};
-    if (!attr[device & 63]) {
-#define GMG_Z2_ATTR(MKV, FMV, BCV) HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sells_z2sweep_kernel<MKV, FMV, BCV>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024))
-      GMG_Z2_ATTR(true, true, true); GMG_Z2_ATTR(true, false, true); GMG_Z2_ATTR(false, true, true); GMG_Z2_ATTR(false, false, true);
-      GMG_Z2_ATTR(true, true, false); GMG_Z2_ATTR(true, false, false); GMG_Z2_ATTR(false, true, false); GMG_Z2_ATTR(false, false, false);
-#undef GMG_Z2_ATTR
-      attr[device & 63] = true;
-    }
-#define GMG_Z2_LAUNCH(BCV)                                                                                                   \
-    do {                                                                                                                     \
-      if (mk) { if (pat_fma) hipLaunchKernelGGL((sells_z2sweep_kernel<true, true, BCV>), gr, b, lds, stream, a, g);          \
-                else hipLaunchKernelGGL((sells_z2sweep_kernel<true, false, BCV>), gr, b, lds, stream, a, g); }               \
-      else { if (pat_fma) hipLaunchKernelGGL((sells_z2sweep_kernel<false, true, BCV>), gr, b, lds, stream, a, g);            \
-             else hipLaunchKernelGGL((sells_z2sweep_kernel<false, false, BCV>), gr, b, lds, stream, a, g); }                 \
-    } while (0)
-    if (bc) GMG_Z2_LAUNCH(true); else GMG_Z2_LAUNCH(false);
-#undef GMG_Z2_LAUNCH
+    with_bools([&](auto BC, auto MK, auto FM) {
+      allow_lds<&sells_z2sweep_kernel<MK(), FM(), BC()>>(150 * 1024);
+      hipLaunchKernelGGL((sells_z2sweep_kernel<MK(), FM(), BC()>), gr, b, lds, stream, a, g); }, bc, mk, pat_fma != 0);
     HIP_CHECK(hipGetLastError());
   }
   void ensure_z2(const DevCSR &M)
@@ -2601,16 +2495,29 @@ struct gmg_solver {
     ensure_z2(M);
     return M.z2_ok > 0 && M.z2.box != 0;
   }
+  int sells_wpb(int nsl) const { return sell_block > 0 ? sell_block / 64 : (nsl >= 256 * 32 ? 4 : pat_small_wpb); }
+  // The form of the r-gather sweep of an operator -- the ONE place that decides it, in this order: tile (by option and size; the tile
+  // sweep may still decline), constant-coefficient box, z-walk (fills zg), pair sweep at one slice per wave or at resident workgroups,
+  // single-row sweep.  `from`: where the decisions start -- what follows a tile sweep that declined, or an x mode that tile and box lack.
+  enum class RSweepForm { Tile, Box, ZWalk, Pair8, Pair, Row };
+  RSweepForm rsweep_form(const DevCSR &M, ZWalkGeo &zg, RSweepForm from = RSweepForm::Tile)
+  {
+    if (from == RSweepForm::Tile && (pat_tile >= 2 || (pat_tile == 1 && M.nrows >= pat_tile_rows))) return RSweepForm::Tile;
+    if (from <= RSweepForm::Box && box_level(M)) return RSweepForm::Box;
+    if (pat_r2 && pat_zwalk && (pat_zwalk >= 2 || M.nrows >= pat_zwalk_rows) && zwalk_geo(M, zg)) return RSweepForm::ZWalk;
+    if (!(pat_r2 && (M.pat_nruns == 9 || M.pat_nruns == 3))) return RSweepForm::Row;
+    // one slice per wave: workgroups of eight waves stage the coefficient table once per eight slices (pat_r2_occ = 2)
+    const int rows = 65 - M.pat_k;
+    const bool occ8 = pat_r2_occ >= 2 && sells_wpb((int)((M.nrows + rows - 1) / rows)) == 4 && M.pat_nruns == 9 && M.nrows >= pat_tile_rows && pat_r2_wgs <= 0;
+    return occ8 ? RSweepForm::Pair8 : RSweepForm::Pair;
+  }
   // Does launch_rsweep() end in a kernel that has x mode 3 (x = (x + s_k) + s_{k+1}, the latter from the row's own r_{k+1} in
-  // registers) for this operator?  Same order of decisions as launch_rsweep(): tile, box, z-walk, pair sweep, single-row sweep --
-  // only the z-walk and the pair sweep have it.
+  // registers) for this operator?  Only the z-walk and the pair sweep have it.  (Tile by option: no, whether or not the tile sweep then applies.)
   bool xnext_kernel(const DevCSR &M)
   {
-    if (pat_tile >= 2 || (pat_tile == 1 && M.nrows >= pat_tile_rows)) return false;   // (whether or not the tile sweep then applies)
-    if (box_level(M)) return false;
     ZWalkGeo zg;
-    if (pat_r2 && pat_zwalk && (pat_zwalk >= 2 || M.nrows >= pat_zwalk_rows) && zwalk_geo(M, zg)) return true;
-    return pat_r2 && (M.pat_nruns == 9 || M.pat_nruns == 3);
+    const RSweepForm form = rsweep_form(M, zg);
+    return form == RSweepForm::ZWalk || form == RSweepForm::Pair8 || form == RSweepForm::Pair;
   }
   void launch_rsweep(const DevCSR &M, const double *r_cur, double *r_next, const double *r_prev, double *x, bool x_zero, double omega, int xmode)
   {
@@ -2622,53 +2529,43 @@ struct gmg_solver {
     const int nsl = (int)((M.nrows + rows - 1) / rows);
     a.nrows = M.nrows; a.ncols = M.ncols; a.nslices = nsl; a.xcd_remap = xcd_remap;
     a.x_zero = x_zero ? 1 : 0; a.x = r_cur; a.omega = omega; a.y = r_next; a.b = r_cur; a.x2 = x; a.s_out = const_cast<double *>(r_prev);
-    if ((pat_tile >= 2 || (pat_tile == 1 && M.nrows >= pat_tile_rows)) && xmode != 3 && launch_tsweep(M, a, nsl)) return;
-    const int wpb = sell_block > 0 ? sell_block / 64 : (nsl >= 256 * 32 ? 4 : pat_small_wpb);
+    ZWalkGeo zg;
+    // (xmode 3 is only asked for where xnext_kernel() has ruled the tile and the box out: the decisions then start after them)
+    RSweepForm form = rsweep_form(M, zg, xmode == 3 ? RSweepForm::ZWalk : RSweepForm::Tile);
+    if (form == RSweepForm::Tile) {
+      if (launch_tsweep(M, a, nsl)) return;
+      form = rsweep_form(M, zg, RSweepForm::Box);
+    }
+    const int wpb = sells_wpb(nsl);
     const int nu = M.pat_k * M.pat_nruns;
-    const int nb = pat_nb > 0 ? pat_nb : (nsl >= 200000 ? 2 : 1);
-    const int wg2 = std::max(1, std::min((nsl + wpb - 1) / wpb, nb >= 2 && pat_wgs == 2048 ? 1024 : pat_wgs));
-    const dim3 g2(wg2), b(64 * wpb);
+    const dim3 b(64 * wpb);
     const size_t lds2 = (size_t)M.pat_np * nu * 16 + 16;
-    const bool mk = pat_strict || !M.ptab8;
-    // constant-coefficient box: one coefficient set per wave from the kernel arguments, no pattern ids, no LDS
-    if (xmode != 3 && box_level(M)) {                        // (xmode 3 is only asked for where xnext_kernel() has ruled these forms out)
+    const bool mk = pat_strict || !M.ptab8, fm = pat_fma != 0;
+    switch (form) {
+    case RSweepForm::Tile: break;                            // (not reached)
+    case RSweepForm::Box: {
+      // constant-coefficient box: one coefficient set per wave from the kernel arguments, no pattern ids, no LDS
       const Z2Geo &gb = M.zbx;
       const int nch = gb.nzb * gb.ny * gb.nxs;
       const dim3 gx((unsigned)((nch + 3) / 4)), bx(256);
       M.note_sweep("sells_boxsweep_kernel<XM=*,MK=%d,FM=%d> chains=%d T=%d segs=%d L=%d", mk ? 1 : 0, pat_fma ? 1 : 0, nch, gb.T, gb.nxs, gb.L);
-#define GMG_BOX_LAUNCH(XMV)                                                                                      \
-      do {                                                                                                       \
-        if (mk) { if (pat_fma) hipLaunchKernelGGL((sells_boxsweep_kernel<XMV, true, true>), gx, bx, 0, stream, a, gb);      \
-                  else hipLaunchKernelGGL((sells_boxsweep_kernel<XMV, true, false>), gx, bx, 0, stream, a, gb); }           \
-        else { if (pat_fma) hipLaunchKernelGGL((sells_boxsweep_kernel<XMV, false, true>), gx, bx, 0, stream, a, gb);        \
-               else hipLaunchKernelGGL((sells_boxsweep_kernel<XMV, false, false>), gx, bx, 0, stream, a, gb); }             \
-      } while (0)
-      if (xmode == 0) GMG_BOX_LAUNCH(0); else if (xmode == 1) GMG_BOX_LAUNCH(1); else GMG_BOX_LAUNCH(2);
-#undef GMG_BOX_LAUNCH
-      HIP_CHECK(hipGetLastError());
-      return;
+      with_value<0, 1, 2>(xmode, [&](auto XM) { with_bools([&](auto MK, auto FM) {
+        hipLaunchKernelGGL((sells_boxsweep_kernel<XM(), MK(), FM()>), gx, bx, 0, stream, a, gb); }, mk, fm); });
+      break;
     }
-    // the pair sweep as a walk along the slowest grid direction: three new windows per step instead of nine, one step of requests in flight
-    ZWalkGeo zg;
-    if (pat_r2 && pat_zwalk && (pat_zwalk >= 2 || M.nrows >= pat_zwalk_rows) && zwalk_geo(M, zg)) {
+    case RSweepForm::ZWalk: {
+      // the pair sweep as a walk along the slowest grid direction: three new windows per step instead of nine, one step of requests in flight
       const int wz = 4;
       const dim3 gz((unsigned)((zg.nchains + wz - 1) / wz)), bz(64 * wz);
       const size_t ldsz = (size_t)M.pat_np * 28 * 8 + 16;       // patterns padded to 28 doubles (16-byte aligned coefficient pairs)
       M.note_sweep("sells_zsweep_kernel<XM=*,MK=%d,FM=%d> chains=%d P=%d m=%d T=%d", mk ? 1 : 0, pat_fma ? 1 : 0, zg.nchains, zg.P, zg.m, zg.T);
-#define GMG_ZW_LAUNCH(XMV)                                                                                       \
-      do {                                                                                                       \
-        if (mk) { if (pat_fma) hipLaunchKernelGGL((sells_zsweep_kernel<XMV, true, true>), gz, bz, ldsz, stream, a, zg);     \
-                  else hipLaunchKernelGGL((sells_zsweep_kernel<XMV, true, false>), gz, bz, ldsz, stream, a, zg); }          \
-        else { if (pat_fma) hipLaunchKernelGGL((sells_zsweep_kernel<XMV, false, true>), gz, bz, ldsz, stream, a, zg);       \
-               else hipLaunchKernelGGL((sells_zsweep_kernel<XMV, false, false>), gz, bz, ldsz, stream, a, zg); }            \
-      } while (0)
-      if (xmode == 0) GMG_ZW_LAUNCH(0); else if (xmode == 1) GMG_ZW_LAUNCH(1); else if (xmode == 3) GMG_ZW_LAUNCH(3); else GMG_ZW_LAUNCH(2);
-#undef GMG_ZW_LAUNCH
-      HIP_CHECK(hipGetLastError());
-      return;
+      with_value<0, 1, 3, 2>(xmode, [&](auto XM) { with_bools([&](auto MK, auto FM) {
+        hipLaunchKernelGGL((sells_zsweep_kernel<XM(), MK(), FM()>), gz, bz, ldsz, stream, a, zg); }, mk, fm); });
+      break;
     }
-    // two rows per lane (kernels.hpp: sells_r2sweep_kernel): slices of 126 rows, 16-byte loads / stores, half the conversions and shifts per row
-    if (pat_r2 && (M.pat_nruns == 9 || M.pat_nruns == 3)) {
+    case RSweepForm::Pair8:
+    case RSweepForm::Pair: {
+      // two rows per lane (kernels.hpp: sells_r2sweep_kernel): slices of 126 rows, 16-byte loads / stores, half the conversions and shifts per row
       const int nsl2 = (int)((M.nrows + 125) / 126);
       a.nslices = nsl2;
       // one round of workgroups: four per CU at 105 registers (128^3: 17.4 us per sweep; 768: 19.2, 1280: 20.8, 2048: 19.1 --
@@ -2676,57 +2573,35 @@ struct gmg_solver {
       // Levels of >= pat_tile_rows rows (256^3 and up): the 64-register form with ONE slice per wave -- workgroups are dealt to the CUs
       // as they retire, neighbouring slices run at the same time on the same XCD and meet in its L2 -- beats the tile sweep that
       // these levels took before: 256^3 134 / 185 -> 123 / 166 us per sweep by variant, 288^3 184 / 271 -> 173 / 253 (section 14)
-      const bool occ = pat_r2_occ && wpb == 4 && M.pat_nruns == 9;
-      // one slice per wave: workgroups of eight waves stage the coefficient table once per eight slices (pat_r2_occ = 2)
-      const bool occ8 = occ && pat_r2_occ >= 2 && M.nrows >= pat_tile_rows && pat_r2_wgs <= 0;
-      if (occ8) {
+      if (form == RSweepForm::Pair8) {
         const dim3 g8((nsl2 + 7) / 8), b8(512);
         M.note_sweep("sells_r2sweep_kernel<XM=*,MK=%d,FM=%d,NR=%d,OCC=2> wgs=%d wpb=8", mk ? 1 : 0, pat_fma ? 1 : 0, M.pat_nruns, (int)g8.x);
-#define GMG_R2_LAUNCH8(XMV)                                                                                      \
-        do {                                                                                                     \
-          if (mk) { if (pat_fma) hipLaunchKernelGGL((sells_r2sweep_kernel<XMV, true, true, 9, 2>), g8, b8, lds2, stream, a);   \
-                    else hipLaunchKernelGGL((sells_r2sweep_kernel<XMV, true, false, 9, 2>), g8, b8, lds2, stream, a); }        \
-          else { if (pat_fma) hipLaunchKernelGGL((sells_r2sweep_kernel<XMV, false, true, 9, 2>), g8, b8, lds2, stream, a);     \
-                 else hipLaunchKernelGGL((sells_r2sweep_kernel<XMV, false, false, 9, 2>), g8, b8, lds2, stream, a); }          \
-        } while (0)
-        if (xmode == 0) GMG_R2_LAUNCH8(0); else if (xmode == 1) GMG_R2_LAUNCH8(1); else if (xmode == 3) GMG_R2_LAUNCH8(3); else GMG_R2_LAUNCH8(2);
-#undef GMG_R2_LAUNCH8
-        HIP_CHECK(hipGetLastError());
-        return;
+        with_value<0, 1, 3, 2>(xmode, [&](auto XM) { with_bools([&](auto MK, auto FM) {
+          hipLaunchKernelGGL((sells_r2sweep_kernel<XM(), MK(), FM(), 9, 2>), g8, b8, lds2, stream, a); }, mk, fm); });
+        break;
       }
+      const bool occ = pat_r2_occ && wpb == 4 && M.pat_nruns == 9;
       const int full = (nsl2 + wpb - 1) / wpb;
       const int wgr = std::max(1, std::min(full, pat_r2_wgs > 0 ? pat_r2_wgs : (occ && M.nrows >= pat_tile_rows ? full : (occ ? 8 : 4) * n_cus)));
       const dim3 gr(wgr);
       M.note_sweep("sells_r2sweep_kernel<XM=*,MK=%d,FM=%d,NR=%d,OCC=%d> wgs=%d wpb=%d", mk ? 1 : 0, pat_fma ? 1 : 0, M.pat_nruns, occ ? 1 : 0, wgr, wpb);
-#define GMG_R2_LAUNCH2(XMV, MKV, FMV)                                                                            \
-      do {                                                                                                       \
-        if (occ) hipLaunchKernelGGL((sells_r2sweep_kernel<XMV, MKV, FMV, 9, 1>), gr, b, lds2, stream, a);        \
-        else if (M.pat_nruns == 9) hipLaunchKernelGGL((sells_r2sweep_kernel<XMV, MKV, FMV, 9>), gr, b, lds2, stream, a);   \
-        else hipLaunchKernelGGL((sells_r2sweep_kernel<XMV, MKV, FMV, 3>), gr, b, lds2, stream, a);               \
-      } while (0)
-#define GMG_R2_LAUNCH(XMV)                                                                                       \
-      do {                                                                                                       \
-        if (mk) { if (pat_fma) GMG_R2_LAUNCH2(XMV, true, true); else GMG_R2_LAUNCH2(XMV, true, false); }         \
-        else { if (pat_fma) GMG_R2_LAUNCH2(XMV, false, true); else GMG_R2_LAUNCH2(XMV, false, false); }          \
-      } while (0)
-      if (xmode == 0) GMG_R2_LAUNCH(0); else if (xmode == 1) GMG_R2_LAUNCH(1); else if (xmode == 3) GMG_R2_LAUNCH(3); else GMG_R2_LAUNCH(2);
-#undef GMG_R2_LAUNCH2
-#undef GMG_R2_LAUNCH
-      HIP_CHECK(hipGetLastError());
-      return;
+      with_value<0, 1, 3, 2>(xmode, [&](auto XM) { with_bools([&](auto MK, auto FM) {
+        with_value<1, 0>(occ ? 1 : 0, [&](auto OCC) { with_value<9, 3>(M.pat_nruns, [&](auto NR) {
+          if constexpr (OCC() == 0 || NR() == 9)             // (the 64-register form is the nine-run one: occ says so)
+            hipLaunchKernelGGL((sells_r2sweep_kernel<XM(), MK(), FM(), NR(), OCC()>), gr, b, lds2, stream, a); }); }); }, mk, fm); });
+      break;
     }
-    REQUIRE(xmode != 3, GMG_ERR_STATE, "sells_rsweep_kernel has no x mode 3 (xnext_kernel() and launch_rsweep() disagree)");
-    M.note_sweep("sells_rsweep_kernel<XM=*,NB=%d,MK=%d,FM=%d> wgs=%d wpb=%d", nb >= 2 ? 2 : 1, mk ? 1 : 0, pat_fma ? 1 : 0, wg2, wpb);
-#define GMG_RSWEEP_LAUNCH(XMV, NBV)                                                                            \
-    do {                                                                                                         \
-      if (mk) { if (pat_fma) hipLaunchKernelGGL((sells_rsweep_kernel<XMV, NBV, true, 0, true>), g2, b, lds2, stream, a);   \
-                else hipLaunchKernelGGL((sells_rsweep_kernel<XMV, NBV, true>), g2, b, lds2, stream, a); }        \
-      else { if (pat_fma) hipLaunchKernelGGL((sells_rsweep_kernel<XMV, NBV, false, 0, true>), g2, b, lds2, stream, a);     \
-             else hipLaunchKernelGGL((sells_rsweep_kernel<XMV, NBV, false>), g2, b, lds2, stream, a); }          \
-    } while (0)
-    if (nb >= 2) { if (xmode == 0) GMG_RSWEEP_LAUNCH(0, 2); else if (xmode == 1) GMG_RSWEEP_LAUNCH(1, 2); else GMG_RSWEEP_LAUNCH(2, 2); }
-    else { if (xmode == 0) GMG_RSWEEP_LAUNCH(0, 1); else if (xmode == 1) GMG_RSWEEP_LAUNCH(1, 1); else GMG_RSWEEP_LAUNCH(2, 1); }
-#undef GMG_RSWEEP_LAUNCH
+    case RSweepForm::Row: {
+      REQUIRE(xmode != 3, GMG_ERR_STATE, "sells_rsweep_kernel has no x mode 3 (xnext_kernel() and launch_rsweep() disagree)");
+      const int nb = pat_nb > 0 ? pat_nb : (nsl >= 200000 ? 2 : 1);
+      const int wg2 = std::max(1, std::min((nsl + wpb - 1) / wpb, nb >= 2 && pat_wgs == 2048 ? 1024 : pat_wgs));
+      const dim3 g2(wg2);
+      M.note_sweep("sells_rsweep_kernel<XM=*,NB=%d,MK=%d,FM=%d> wgs=%d wpb=%d", nb >= 2 ? 2 : 1, mk ? 1 : 0, pat_fma ? 1 : 0, wg2, wpb);
+      with_value<2, 1>(nb >= 2 ? 2 : 1, [&](auto NB) { with_value<0, 1, 2>(xmode, [&](auto XM) { with_bools([&](auto MK, auto FM) {
+        hipLaunchKernelGGL((sells_rsweep_kernel<XM(), NB(), MK(), 0, FM()>), g2, b, lds2, stream, a); }, mk, fm); }); });
+      break;
+    }
+    }
     HIP_CHECK(hipGetLastError());
   }
   // one sweep of that form: x (+)= s_k ; r_{k+1} = r_k - A s_k with s_k = omega*(d*r_k) formed from the gathered r_k
@@ -3361,24 +3236,9 @@ struct gmg_solver {
     // (NS, MK, NR) exist is smooth_nr_form's answer (kernels.hpp), everything else keeps the runtime run count body
     const int nr = persist_regs && smooth_nr_form(ns, mk, M.pat_nruns) ? M.pat_nruns : 0;
     M.note_smooth("sells_smooth_kernel<NS=%d,TD=%d,MK=%d,NR=%d> wgs=%d wpb=%d", ns, td ? 1 : 0, mk ? 1 : 0, nr, nwg, wpb);
-#define GMG_SMOOTH_LAUNCH_MK(NSV, TDV, MKV, NRV)                                                               \
-    do {                                                                                                         \
-      if constexpr (NRV == 0 || smooth_nr_form(NSV, MKV, NRV))                                                   \
-        hipLaunchKernelGGL((sells_smooth_kernel<NSV, TDV, MKV, 0, NRV>), g, b, lds, stream, a);                  \
-    } while (0)
-#define GMG_SMOOTH_LAUNCH_NR(NSV, TDV, NRV)                                                                    \
-    do { if (mk) GMG_SMOOTH_LAUNCH_MK(NSV, TDV, true, NRV); else GMG_SMOOTH_LAUNCH_MK(NSV, TDV, false, NRV); } while (0)
-#define GMG_SMOOTH_LAUNCH(NSV, TDV)                                                                            \
-    do {                                                                                                         \
-      if (nr == 9) GMG_SMOOTH_LAUNCH_NR(NSV, TDV, 9);                                                            \
-      else if (nr == 3) GMG_SMOOTH_LAUNCH_NR(NSV, TDV, 3);                                                       \
-      else GMG_SMOOTH_LAUNCH_NR(NSV, TDV, 0);                                                                    \
-    } while (0)
-    if (ns == 2) { if (td) GMG_SMOOTH_LAUNCH(2, true); else GMG_SMOOTH_LAUNCH(2, false); }
-    else { if (td) GMG_SMOOTH_LAUNCH(1, true); else GMG_SMOOTH_LAUNCH(1, false); }
-#undef GMG_SMOOTH_LAUNCH
-#undef GMG_SMOOTH_LAUNCH_NR
-#undef GMG_SMOOTH_LAUNCH_MK
+    with_value<2, 1>(ns, [&](auto NS) { with_bool(td, [&](auto TD) { with_value<9, 3, 0>(nr, [&](auto NR) { with_bool(mk, [&](auto MK) {
+      if constexpr (NR() == 0 || smooth_nr_form(NS(), MK(), NR()))
+        hipLaunchKernelGGL((sells_smooth_kernel<NS(), TD(), MK(), 0, NR()>), g, b, lds, stream, a); }); }); }); });
     HIP_CHECK(hipGetLastError());
     if (prof) {
       HIP_CHECK(hipEventRecord(prof_ev[prof_used + 1], stream));
