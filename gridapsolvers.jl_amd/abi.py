@@ -178,6 +178,7 @@ SYMBOLS = {
     "gmg_sweep_signature": [C.c_void_p, C.c_int, C.c_char_p, C.c_int],
     "gmg_level_format": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                          C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    "gmg_level_values": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)],
     "gmg_device_bytes": [C.c_void_p, C.POINTER(C.c_int64)],
     "gmg_stream_probe": [C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_double)],
     "gmg_stream_probe_read": [C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_double)],

@@ -316,7 +316,10 @@ struct DevCSR {
   // numerical_setup!: the layout stores every value explicitly (CSR-stream, or SELL-64 / SELL-O with its own value stream), so new
   // values on the same pattern can be written in place.  Dictionary / row-pattern / packed layouts were chosen FROM the values.
   // The one rule of gmg_solver::can_refresh (levels) and gmg_block_solver::can_refresh (blocks).
-  bool explicit_values() const { return rowptr && (sell ? (sval && !pat && !vdict && !comp_idx) : val != nullptr); }
+  bool explicit_values() const { return rowptr && (sell ? ((sval || sval32) && !pat && !vdict && !comp_idx) : val != nullptr); }
+  // cycle_values = float32 (f32.inc.hpp): the value stream rounded to float32 in the slice geometry of sval -- what the cycle's
+  // launches on this level matrix stream.  Level 0 keeps sval next to it (the Krylov side), levels >= 1 release sval.
+  float *sval32 = nullptr;
   // kernel + template arguments of the fused sweep last launched on this operator (x-update variant excluded): bench.py only
   // attaches committed PMC traffic to a kernel whose signature matches the profiled one (gmg_sweep_signature)
   mutable char sweep_sig[112] = {0};
@@ -1000,6 +1003,7 @@ struct gmg_solver {
     }
     d_Ainv = d_partials = d_scalars = nullptr;
     d_partials2 = nullptr;
+    d_f32_flags = nullptr;
     cc_w = cc_p = cc_z = cc_r = nullptr;
     d_rep_gid = nullptr; d_rep_tmp = nullptr; cg_x = nullptr; d_own2loc = nullptr; d_vr = nullptr;
     redist.glue_r = redist.glue_x = nullptr;
@@ -2139,8 +2143,9 @@ struct gmg_solver {
     HIP_CHECK(hipGetLastError());
   }
   template <int EPI, bool ONEG>
-  void launch_sello(const DevCSR &M, const StreamArgs2 &a2)
+  void launch_sello(const DevCSR &M, const StreamArgs2 &a2, bool cyc = false)
   {
+    if (f32_stream(M, cyc)) { launch_sello_f32<EPI, ONEG>(M, a2); return; }
     SellOArgs a;
     std::memset(&a, 0, sizeof(a));
     a.soff = M.soff; a.sval = M.sval; a.rowlen = M.rowlen; a.rowpid = M.orowpid; a.rowbase = M.orowbase; a.poff = M.opoff;
@@ -2167,12 +2172,15 @@ struct gmg_solver {
       hipLaunchKernelGGL((sello_kernel<EPI, ONEG, UN(), NT()>), g, b, lds, stream, a); }); });
     HIP_CHECK(hipGetLastError());
   }
+  // cyc: the launch belongs to the multigrid cycle (sweeps, r -= A dx) -- on a level with a float32 value stream (cycle_values =
+  // float32, f32.inc.hpp) those stream it; everything else (the Krylov side, op_apply) streams the fp64 values
   template <int EPI, bool ONEG>
-  void launch_sell(const DevCSR &M, const StreamArgs2 &a2)
+  void launch_sell(const DevCSR &M, const StreamArgs2 &a2, bool cyc = false)
   {
     if (M.pat) { launch_sellp<EPI, ONEG>(M, a2); return; }
     if (M.comp_idx || M.vdict) { launch_sellc<EPI, ONEG>(M, a2); return; }
-    if (M.opat) { launch_sello<EPI, ONEG>(M, a2); return; }
+    if (M.opat) { launch_sello<EPI, ONEG>(M, a2, cyc); return; }
+    if (f32_stream(M, cyc)) { launch_sell_f32<EPI, ONEG>(M, a2); return; }
     SellArgs a;
     std::memset(&a, 0, sizeof(a));
     a.soff = M.soff; a.scol = M.scol; a.sval = M.sval; a.rowlen = M.rowlen; a.nrows = M.nrows; a.nslices = M.nslices; a.xcd_remap = xcd_remap;
@@ -2238,11 +2246,12 @@ struct gmg_solver {
     launch_stream1<EPI_SET, false, false>(M, a);
   }
   // y -= M x
-  void spmv_sub(const DevCSR &M, const double *x, double *y, double *emit_s = nullptr, const double *emit_dinv = nullptr, double emit_omega = 0.0)
+  void spmv_sub(const DevCSR &M, const double *x, double *y, double *emit_s = nullptr, const double *emit_dinv = nullptr, double emit_omega = 0.0,
+                bool cyc = false)
   {
     StreamArgs2 a = base_args1(M); a.x = x; a.y = y;
     if (emit_s && M.pat) { a.s_out = emit_s; a.dinv = emit_dinv; a.omega = emit_omega; }
-    if (M.sell) { launch_sell<EPI_SUB, false>(M, a); return; }
+    if (M.sell) { launch_sell<EPI_SUB, false>(M, a, cyc); return; }
     launch_stream1<EPI_SUB, false, false>(M, a);
   }
   // y = b - M x
@@ -2657,8 +2666,8 @@ struct gmg_solver {
       a.b = r_old; a.dinv = L.dinv; a.omega = S.omega; a.y = r_new; a.x2 = x; a.x_zero = x_zero ? 1 : 0;
       a.xmode = xmode; a.dinv_from_table = pat_dinv;      // L.dinv is 1 ./ diag(L.A): the pattern table holds the same numbers
       if (L.A.sell) {
-        if (s_old) { a.x = s_old; a.s_out = s_new; launch_sell<EPI_SWEEP, true>(L.A, a); }
-        else { a.x = r_old; launch_sell<EPI_SWEEP, false>(L.A, a); }
+        if (s_old) { a.x = s_old; a.s_out = s_new; launch_sell<EPI_SWEEP, true>(L.A, a, true); }
+        else { a.x = r_old; launch_sell<EPI_SWEEP, false>(L.A, a, true); }
       } else
       if (s_old) { a.x = s_old; a.s_out = s_new; launch_stream1<EPI_SWEEP, true, false>(L.A, a); }
       else { a.x = r_old; launch_stream1<EPI_SWEEP, false, false>(L.A, a); }
@@ -3033,7 +3042,7 @@ struct gmg_solver {
       spmv_sub(L.A, x, y, L.sbuf[0], L.dinv, next->omega);
       L.s0_ready = true; L.s0_src = y; L.s0_omega = next->omega;
     } else
-    spmv_sub(L.A, x, y);
+    spmv_sub(L.A, x, y, nullptr, nullptr, 0.0, true);       // (a launch of the cycle: the float32 stream where the level has one)
     finish_ghost<1>(l, x, y);
   }
   bool emits_s0(const Level &L, const Smoother &S, const DevCSR &producer)
@@ -3129,6 +3138,16 @@ struct gmg_solver {
   void build_gs(int l, bool values_only = false);
   void gs_solve(Level &L, int dir, const double *r, double *dx, int xmode = 0, double *x = nullptr);
   void gs_pass(int l, Smoother &S, double *x, double *r, bool x_zero);
+  // cycle_values = float32 (f32.inc.hpp): float twins of the SELL-64 / SELL-O value streams, streamed by the cycle's launches
+  int values_f32 = 0;                        // GMG_VALUES_F32
+  int f32_nt = -1;                           // GMG_VALUES_F32_NT: -1 by the bytes of the float stream, 0 never, 1 always (2: the row-wise operands too)
+  unsigned long long *d_f32_flags = nullptr; // {first row with a value outside float32's normal range, zero diagonals} of the last fill
+  bool f32_stream(const DevCSR &M, bool cyc) const;
+  void f32_check() const;
+  void f32_prepare(int l, int &nzero);
+  void f32_fill(DevCSR &A, const double *dval, double *dinv, int l, int &nzero);
+  template <int EPI, bool ONEG> void launch_sell_f32(const DevCSR &M, const StreamArgs2 &a2);
+  template <int EPI, bool ONEG> void launch_sello_f32(const DevCSR &M, const StreamArgs2 &a2);
   // Chebyshev smoother (cheb.inc.hpp)
   void cheb_precond(int l, Smoother &S, double *r, double *z);
   void cheb_setup(int l, Smoother &S, const Smoother *same_M);
@@ -4211,6 +4230,8 @@ struct gmg_solver {
     pat_rb = opt_int("GMG_PAT_RB", 3); pat_rb = pat_rb >= 9 ? 9 : (pat_rb <= 1 ? 1 : 3);
     pat_batched = opt_int("GMG_PAT_BATCHED", 1);
     use_opattern = opt_int("GMG_OPATTERN", 1);
+    values_f32 = opt_int("GMG_VALUES_F32", 0) != 0 ? 1 : 0;
+    f32_nt = std::min(2, std::max(-1, opt_int("GMG_VALUES_F32_NT", -1)));
     pat_nb = std::min(2, std::max(0, opt_int("GMG_PAT_NB", 0)));
     tile = kTile;
   }
@@ -4268,9 +4289,9 @@ struct gmg_solver {
       if (fuse2_level(L)) vec = 16.0 * N;                  // sells_z2sweep_kernel, per sweep of the pair: (r_k in + r_{k+2} out + x in + x out) / 2
       if (box_active(A)) mat = 0.0;                        // sells_boxsweep_kernel: no pattern ids either -- the coefficients are kernel arguments
     } else if (A.pat) mat = (A.rowbase ? 6.0 : 2.0) * N;
-    else if (A.sell && A.opat) { mat = 8.0 * (double)A.zpad + (A.orowbase ? 6.0 : 2.0) * N + 4.0 * N + 8.0 * (double)A.nslices; if (sell_defer && sell_un < 27) vec -= 4.0 * N; }
+    else if (A.sell && A.opat) { mat = (A.sval32 ? 4.0 : 8.0) * (double)A.zpad + (A.orowbase ? 6.0 : 2.0) * N + 4.0 * N + 8.0 * (double)A.nslices; if (sell_defer && sell_un < 27) vec -= 4.0 * N; }
     else if (A.sell && (A.comp_idx || A.vdict)) mat = A.stream_bytes_per_nnz * (double)A.zpack + 4.0 * N + 4.0 * (double)(A.zpack / 64);
-    else if (A.sell) { mat = 12.0 * (double)A.zpad + 4.0 * N + 8.0 * (double)A.nslices; if (sell_defer && sell_un >= 6 && sell_un < 9) vec -= 4.0 * N; }
+    else if (A.sell) { mat = (A.sval32 ? 8.0 : 12.0) * (double)A.zpad + 4.0 * N + 8.0 * (double)A.nslices; if (sell_defer && sell_un >= 6 && sell_un < 9) vec -= 4.0 * N; }
     else mat = 12.0 * (double)A.nnz + (A.ptr64 ? 8.0 : 4.0) * N;
     return mat + vec;
   }
@@ -5927,6 +5948,7 @@ void gmg_solver::setup()
             "(gmg_set_redistribution) is not supported, its reductions would need a communicator of the subset");
   }
   for (int l = 0; l < nlev - 1; ++l) pmult_check(l);         // multiplicative patch slots: what is refused, before anything is built
+  f32_check();                                               // cycle_values = float32: the same
   // patch smoothers / patch corrections with patches of more than 64 dofs take their blocks from the level's CSR (one thread block
   // per patch): a level kept in row-pattern form only gets its rows back
   for (int l = 0; l < nlev - 1; ++l) {
@@ -6165,6 +6187,7 @@ void gmg_solver::setup()
       // :189-190 smoother caches: inv_diag = 1 ./ diag(A) (JacobiLinearSolvers.jl:20-23)
       int nzero = 0;
       L.dinv = build_inv_diag(L.A, nzero);
+      f32_prepare(l, nzero);                                 // cycle_values = float32: the float value stream, 1/diag of the rounded matrix
       const bool need_diag = (L.pre.kind == SM_JACOBI) || ((L.post_shares_pre ? L.pre : L.post).kind == SM_JACOBI);   // (a shared post is copied from pre below)
       REQUIRE(!(need_diag && nzero > 0), GMG_ERR_SINGULAR, "zero diagonal entry on level " + std::to_string(l));
       if (L.has_pcorr) {
@@ -6310,9 +6333,13 @@ void gmg_solver::refill_values(DevCSR &A, const double *hval, double *dinv, Refi
     }
     HIP_CHECK(hipMemcpyAsync(st.d_val, hval, sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, stream));
     lap(st.copy_ms);
-    if (A.ptr64) hipLaunchKernelGGL((sell_refill_kernel<int64_t>), dim3(grid), dim3(256), 0, stream, n, (const int64_t *)A.rowptr, A.soff, A.scol, st.d_val, A.sval, dinv, st.d_nzero);
-    else hipLaunchKernelGGL((sell_refill_kernel<int32_t>), dim3(grid), dim3(256), 0, stream, n, (const int32_t *)A.rowptr, A.soff, A.scol, st.d_val, A.sval, dinv, st.d_nzero);
+    // (a level with a float32 value stream takes its 1/diag from the rounded values: refresh_values, f32_fill)
+    double *dinv64 = A.sval32 ? nullptr : dinv;
+    if (A.sval) {
+    if (A.ptr64) hipLaunchKernelGGL((sell_refill_kernel<int64_t>), dim3(grid), dim3(256), 0, stream, n, (const int64_t *)A.rowptr, A.soff, A.scol, st.d_val, A.sval, dinv64, st.d_nzero);
+    else hipLaunchKernelGGL((sell_refill_kernel<int32_t>), dim3(grid), dim3(256), 0, stream, n, (const int32_t *)A.rowptr, A.soff, A.scol, st.d_val, A.sval, dinv64, st.d_nzero);
     HIP_CHECK(hipGetLastError());
+    }
     // a level that kept its CSR rows next to the slices (multiplicative patch sweeps, pmult.inc.hpp) gets the new values there too
     if (A.val) HIP_CHECK(hipMemcpyAsync(A.val, st.d_val, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToDevice, stream));
   }
@@ -6344,6 +6371,7 @@ void gmg_solver::refresh_values()
       int nzero = 0;
       HIP_CHECK(hipMemcpyAsync(&nzero, st.d_nzero, sizeof(int), hipMemcpyDeviceToHost, stream));
       HIP_CHECK(hipStreamSynchronize(stream));
+      if (L.A.sval32) f32_fill(L.A, st.d_val, L.dinv, l, nzero);   // the float stream and 1/diag of the rounded matrix, from the staged values
       const bool need_diag = l < nlev - 1 ? (L.pre.kind == SM_JACOBI || L.post.kind == SM_JACOBI) : coarse_eff == GMG_COARSE_CG_JACOBI;
       REQUIRE(!(want_dinv && need_diag && nzero > 0), GMG_ERR_SINGULAR, "zero diagonal entry on level " + std::to_string(l));
       L.s0_ready = false;
@@ -7139,6 +7167,7 @@ const OptionKey kOptionKeys[] = {
   {"GMG_XCD_REMAP", false}, {"GMG_XCD_REMAP_BIG", false}, {"GMG_X0_ZERO", true}, {"GMG_HOST_POLL", true}, {"GMG_HOST_CHUNK_BYTES", true}, {"GMG_PAT_FMA", false}, {"GMG_PAT_R2", false}, {"GMG_RED_FUSED", false}, {"GMG_GMRES_FUSED", true}, {"GMG_FGMRES_FUSED", true}, {"GMG_NULLSPACE_FUSED", true}, {"GMG_PAT_R2MV", false}, {"GMG_PAT_R2_OCC", false}, {"GMG_PAT_PAIR_P", false}, {"GMG_PAT_R2MV_DOT", false}, {"GMG_PERSIST_WPB", false}, {"GMG_HOST_TIMELINE", true}, {"GMG_PAT_R2MV_MIN", false}, {"GMG_PAT_BCAST", false}, {"GMG_PAT_R2_WGS", false}, {"GMG_PAT_ZWALK", false}, {"GMG_PAT_ZWALK_T", false}, {"GMG_PAT_ZWALK_ROWS", false}, {"GMG_PAT_ZWALK_MV", false}, {"GMG_PAT_ZWALK_WIDE", false}, {"GMG_PAT_ZWALK_WIDE_ROWS", false}, {"GMG_PAT_FUSE2", false}, {"GMG_PAT_FUSE2_W", false}, {"GMG_PAT_FUSE2_T", false}, {"GMG_PAT_FUSE2_ROWS", false}, {"GMG_PAT_FUSE2_BOX", false}, {"GMG_PAT_BOX", false}, {"GMG_PAT_WIDE_GRID", false}, {"GMG_PAT_BOX_T", false}, {"GMG_PAT_BOX_MIN_ROWS", false}, {"GMG_PAT_BOX_MAX_ROWS", false},
   {"GMG_PERSIST_FORCE_TIMEOUT", true}, {"GMG_PAT_XNEXT", false}, {"GMG_PAT_CLOSE", false}, {"GMG_CG_SPLIT", true}, {"GMG_GS_WIDE", true}, {"GMG_GS_PACK_FUSED", true}, {"GMG_CHEB_PACK_FUSED", true},
   {"GMG_PMULT_ONE_LAUNCH", true}, {"GMG_PMULT_ONE_LAUNCH_MAX", true},
+  {"GMG_VALUES_F32", false}, {"GMG_VALUES_F32_NT", false},
 };
 // "pat_tile", "PAT_TILE" and "GMG_PAT_TILE" name the same option
 const OptionKey *find_option(const char *key)
@@ -8182,7 +8211,8 @@ int gmg_model_bytes(gmg_handle_t h, double *vcycle_bytes, double *cg_iter_bytes)
       const Level &L = h->lev[l];
       const double Z = (double)L.A.nnz, N = (double)L.n, ZP = (double)L.P.nnz, NH = (double)h->lev[l + 1].n;
       const double nu2 = (double)(L.pre.niter + L.post.niter);
-      BV += nu2 * (12.0 * Z + 68.0 * N) + (12.0 * Z + 28.0 * N) + 24.0 * ZP + 36.0 * N + 28.0 * NH;
+      const double bz = L.A.sval32 ? 8.0 : 12.0;             // cycle_values = float32: the cycle's launches stream 4-byte values
+      BV += nu2 * (bz * Z + 68.0 * N) + (bz * Z + 28.0 * N) + 24.0 * ZP + 36.0 * N + 28.0 * NH;
     }
     const double NL = (double)h->lev[h->nlev - 1].n;
     BV += 8.0 * NL * NL + 16.0 * NL;
@@ -8301,6 +8331,7 @@ int gmg_device_bytes(gmg_handle_t h, int64_t *bytes)
 } // extern "C"
 
 #include "block.inc.hpp"
+#include "f32.inc.hpp"
 #include "gs.inc.hpp"
 #include "cheb.inc.hpp"
 #include "pmult.inc.hpp"

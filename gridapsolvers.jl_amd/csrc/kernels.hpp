@@ -252,14 +252,25 @@ struct SellArgs {
   const double *b;         // RESID: b ; sweep: r_old
   double *x2;              // sweep / ADDTO: x
   double *s_out;           // ONEG sweep: s_new
+  const float *sval32;     // VT = float: the value stream rounded to float32, same slice geometry as sval (cycle_values = float32)
 };
+
+// the value stream a kernel instantiated for VT reads (SellArgs / SellOArgs)
+template <typename VT, typename Args>
+__device__ __forceinline__ const VT *stream_values(const Args &a)
+{
+  if constexpr (sizeof(VT) == 4) return a.sval32;
+  else return a.sval;
+}
 
 // NT: 0 cached matrix stream ; 1 non-temporal matrix stream ; 2 also the row-wise operands that are touched once per sweep
 // (r, x, 1/diag in; r, x out: non-temporal; s stays cacheable -- the next sweep gathers it)
 // XM (fused one-gather sweeps only): how x is updated, as in the row-pattern kernels -- 0: x += s_k ; 1: x untouched (the
 // increment is applied by the next sweep) ; 2: x = (x + s_{k-1}) + s_k with s_{k-1} read from s_out before it is overwritten:
 // the same two roundings, one read + one write of x less per pair of sweeps (writes are what this kernel pays most for).
-template <int EPI, bool ONEG, int UN, int NT, int XM = 0>
+// VT: type of the stored values.  float: each value is widened to double in a register (exact) and enters the same v * g, s + pr in
+// the same order -- bit for bit this kernel on the matrix whose values were rounded to float32.
+template <int EPI, bool ONEG, int UN, int NT, int XM = 0, typename VT = double>
 __global__ __launch_bounds__(kBlock) void sell_kernel(SellArgs a)
 {
   const int lane = threadIdx.x & 63;
@@ -295,17 +306,20 @@ __global__ __launch_bounds__(kBlock) void sell_kernel(SellArgs a)
     }
   }
   const int32_t *cp = a.scol + base + lane;
-  const double *vp = a.sval + base + lane;
+  const VT *vp = stream_values<VT>(a) + base + lane;
   double s = 0.0;
   int j = 0;
   for (; j + UN <= w; j += UN) {
     int32_t c[UN];
+    VT vs[UN];
     double v[UN], g[UN];
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
-      if (NT) { c[u] = __builtin_nontemporal_load(cp + (int64_t)(j + u) * 64); v[u] = __builtin_nontemporal_load(vp + (int64_t)(j + u) * 64); }
-      else { c[u] = cp[(int64_t)(j + u) * 64]; v[u] = vp[(int64_t)(j + u) * 64]; }
+      if (NT) { c[u] = __builtin_nontemporal_load(cp + (int64_t)(j + u) * 64); vs[u] = __builtin_nontemporal_load(vp + (int64_t)(j + u) * 64); }
+      else { c[u] = cp[(int64_t)(j + u) * 64]; vs[u] = vp[(int64_t)(j + u) * 64]; }
     }
+#pragma unroll
+    for (int u = 0; u < UN; ++u) v[u] = (double)vs[u];
 #pragma unroll
     for (int u = 0; u < UN; ++u) {    // unconditional gathers: padding points at a valid column
       if (EPI == EPI_SWEEP && !ONEG) g[u] = omega * (dinv[c[u]] * xg[c[u]]);
@@ -319,7 +333,7 @@ __global__ __launch_bounds__(kBlock) void sell_kernel(SellArgs a)
   }
   for (; j < w; ++j) {
     const int32_t c = cp[(int64_t)j * 64];
-    const double v = vp[(int64_t)j * 64];
+    const double v = (double)vp[(int64_t)j * 64];
     double g;
     if (EPI == EPI_SWEEP && !ONEG) g = omega * (dinv[c] * xg[c]);
     else g = xg[c];
@@ -565,9 +579,10 @@ struct SellOArgs {
   const double *b;
   double *x2;
   double *s_out;
+  const float *sval32;      // VT = float: see SellArgs
 };
 
-template <int EPI, bool ONEG, int UN, int NT, int XM = 0>
+template <int EPI, bool ONEG, int UN, int NT, int XM = 0, typename VT = double>
 __global__ __launch_bounds__(kBlock) void sello_kernel(SellOArgs a)
 {
   extern __shared__ double sp_smem[];
@@ -609,14 +624,17 @@ __global__ __launch_bounds__(kBlock) void sello_kernel(SellOArgs a)
     if (XM == 2) sp = a.s_out[rc];
   }
   __syncthreads();
-  const double *vp = a.sval + base + lane;
+  const VT *vp = stream_values<VT>(a) + base + lane;
   const int32_t *to = s_off + pid * a.W;
   double s = 0.0;
   int j = 0;
   for (; j + UN <= w; j += UN) {
+    VT vs[UN];
     double v[UN], g[UN];
 #pragma unroll
-    for (int u = 0; u < UN; ++u) v[u] = NT ? __builtin_nontemporal_load(vp + (int64_t)(j + u) * 64) : vp[(int64_t)(j + u) * 64];
+    for (int u = 0; u < UN; ++u) vs[u] = NT ? __builtin_nontemporal_load(vp + (int64_t)(j + u) * 64) : vp[(int64_t)(j + u) * 64];
+#pragma unroll
+    for (int u = 0; u < UN; ++u) v[u] = (double)vs[u];
 #pragma unroll
     for (int u = 0; u < UN; ++u) {    // entries past the end of the row have offset 0: they gather the row's base column (valid)
       const uint32_t c8 = base8 + (uint32_t)((j + u < a.W) ? to[j + u] : 0);
@@ -630,7 +648,7 @@ __global__ __launch_bounds__(kBlock) void sello_kernel(SellOArgs a)
     }
   }
   for (; j < w; ++j) {
-    const double v = vp[(int64_t)j * 64];
+    const double v = (double)vp[(int64_t)j * 64];
     const uint32_t c8 = base8 + (uint32_t)((j < a.W) ? to[j] : 0);
     double g;
     if (EPI == EPI_SWEEP && !ONEG) g = omega * (ld_off(dinv, c8) * ld_off(xg, c8));
@@ -5114,6 +5132,36 @@ __global__ void sell_refill_kernel(int64_t nrows, const PtrT *__restrict__ rowpt
     sval[q] = v;
     if (scol[q] == (int32_t)i) d += v;
   }
+  if (dinv) {
+    if (d == 0.0) atomicAdd(nzero, 1);
+    dinv[i] = 1.0 / d;
+  }
+}
+
+// cycle_values = float32: the float twin of a SELL-64 / SELL-O value stream from the CSR-ordered fp64 values (setup: the CSR copy on
+// the device; numerical_setup!: the staged new values), rounded to nearest even, and the Jacobi inverse diagonal of the ROUNDED
+// matrix (1 / sum of the rounded diagonal entries, the sum inv_diag_kernel forms).  Padding entries were zeroed when the stream was
+// allocated and are never written.  A nonzero value outside float32's normal range posts its row to *bad_row (smallest row wins).
+template <typename PtrT>
+__global__ void sell_fill_f32_kernel(int64_t nrows, const PtrT *__restrict__ rowptr, const int64_t *__restrict__ soff,
+                                     const int32_t *__restrict__ scol, const double *__restrict__ val, float *__restrict__ sval32,
+                                     double *__restrict__ dinv, int *__restrict__ nzero, unsigned long long *__restrict__ bad_row)
+{
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nrows) return;
+  const int64_t base = soff[i >> 6] + (i & 63);
+  const PtrT k0 = rowptr[i], k1 = rowptr[i + 1];
+  double d = 0.0;
+  bool bad = false;
+  for (PtrT k = k0; k < k1; ++k) {
+    const int64_t q = base + (int64_t)(k - k0) * 64;
+    const double v = val[k];
+    const float f = (float)v;
+    if (v != 0.0 && (!(fabs(v) >= 0x1p-126) || isinf(f))) bad = true;   // (a NaN fails the first test)
+    sval32[q] = f;
+    if (scol[q] == (int32_t)i) d += (double)f;
+  }
+  if (bad) atomicMin(bad_row, (unsigned long long)i);
   if (dinv) {
     if (d == 0.0) atomicAdd(nzero, 1);
     dinv[i] = 1.0 / d;

@@ -117,8 +117,8 @@ struct HipGMGLinearSolver{A,B,C,D,E,F} <: Gridap.Algebra.LinearSolver
   gs_ordering    :: Vector{Any}            # per smoothed level: :natural, :multicolor or a 1-based permutation (gmg_set_gs_ordering)
 end
 
-# Same keyword surface as GMGLinearSolver(smatrices,interp,restrict;...) GMGLinearSolvers.jl:48-69, plus three keywords the
-# reference has no use for: `device`, `options` (layout / schedule policy of THIS solver: e.g. Dict("pat_tile"=>2, "persist"=>0,
+# Same keyword surface as GMGLinearSolver(smatrices,interp,restrict;...) GMGLinearSolvers.jl:48-69, plus keywords the
+# reference has no use for: `cycle_values` (:float64 / :float32, below), `device`, `options` (layout / schedule policy of THIS solver: e.g. Dict("pat_tile"=>2, "persist"=>0,
 # "x0_zero"=>1); unknown keys are rejected by the library) and `pin_vectors` (default false; true: the vectors solve! sees are page-locked
 # once and then move over PCIe by DMA at the link rate -- 3.6 ms instead of 4.7 ms per config-2 solve; the setup keeps them alive.
 # For a top-level solve! that is called again and again with the SAME x and b; not for a preconditioner applied to rotating work vectors)
@@ -130,6 +130,7 @@ function HipGMGLinearSolver(
   mode = :preconditioner, cycle_type = :v_cycle,
   maxiter = 100, atol = 1.0e-14, rtol = 1.0e-08, verbose = false, device = 0,
   options = Dict{String,Float64}(), pin_vectors = false, gs_ordering = :natural,
+  cycle_values = :float64,
 )
   nlev = length(smatrices)
   @assert nlev-1 == length(interp) == length(pre_smoothers) == length(post_smoothers)
@@ -140,6 +141,15 @@ function HipGMGLinearSolver(
   tols = SolverTolerances{Float64}(;maxiter=maxiter,atol=atol,rtol=rtol)
   log  = ConvergenceLog("GMG-MI355X",tols;verbose=verbose)
   opts = Dict{String,Float64}(string(k) => Float64(v) for (k,v) in pairs(options))
+  # cycle_values = :float32 (no reference counterpart): inside the cycle the matrices of the levels stored as SELL-64 / SELL-O are
+  # streamed from float32 copies -- the preconditioner is exactly the fp64 cycle on the rounded matrices, the Krylov solver around it
+  # keeps A in fp64 (include/gmg_amd.h, gmg_level_values).  Passed through as option values_f32; gmg_setup refuses what does not go
+  # with it (Galerkin levels, HipPatchProlongation, other smoothers than Richardson-Jacobi on such a level, values outside float32's range)
+  @assert cycle_values ∈ [:float64,:float32]
+  if cycle_values == :float32
+    @assert mode == :preconditioner "cycle_values = :float32 needs mode = :preconditioner"
+    opts["values_f32"] = 1.0
+  end
   # the visiting order of the levels' Gauss-Seidel sweeps (the reference's GaussSeidelSmoother has no field for it): one entry for
   # every smoothed level, or one entry per level -- :natural, :multicolor or a 1-based permutation of the level's rows
   gso = (gs_ordering isa Symbol || gs_ordering isa AbstractVector{<:Integer}) ? Any[gs_ordering for _ in 1:nlev-1] : Any[gs_ordering...]

@@ -361,6 +361,7 @@ class ConvergenceLog:
 
 _MODES = {"preconditioner": abi.MODE_PRECONDITIONER, "solver": abi.MODE_SOLVER}
 _CYCLES = {"v_cycle": abi.V_CYCLE, "w_cycle": abi.W_CYCLE, "f_cycle": abi.F_CYCLE}
+_CYCLE_VALUES = ("float64", "float32")
 
 
 class GMGLinearSolver:
@@ -371,11 +372,15 @@ class GMGLinearSolver:
     (shape, ptr, idx, val), 0-based (e.g. poisson.CSR or scipy.sparse.csr_matrix
     via `from_scipy`).  restrict=None means R = P^T (the :residual-mode transfer of
     GridTransferOperators.jl:202-209 on nested meshes).  An entry of smatrices[1:] may be Galerkin(): that level's matrix is
-    R (A P) of the finer level, formed on the device."""
+    R (A P) of the finer level, formed on the device.
+
+    cycle_values (no reference counterpart): "float64" (default) or "float32".  With "float32" the cycle streams the matrices of the
+    levels stored as SELL-64 / SELL-O from float32 copies: the preconditioner is exactly the fp64 cycle on the matrices rounded to
+    float32, while the Krylov solver around it keeps A in fp64 (include/gmg_amd.h, gmg_level_values).  Preconditioner mode only."""
 
     def __init__(self, smatrices, interp, restrict=None, pre_smoothers=None, post_smoothers=None,
                  coarsest_solver=None, mode="preconditioner", cycle_type="v_cycle",
-                 maxiter=100, atol=1.0e-14, rtol=1.0e-8, verbose=False, options=None, pin_vectors=False):
+                 maxiter=100, atol=1.0e-14, rtol=1.0e-8, verbose=False, options=None, pin_vectors=False, cycle_values="float64"):
         nlev = len(smatrices)
         if pre_smoothers is None:  # Fill(RichardsonSmoother(JacobiLinearSolver(),10),nlev-1)
             pre_smoothers = [RichardsonSmoother(JacobiLinearSolver(), 10) for _ in range(nlev - 1)]
@@ -392,6 +397,17 @@ class GMGLinearSolver:
             raise ValueError("mode must be 'preconditioner' or 'solver'")
         if cycle_type not in _CYCLES:   # :61
             raise ValueError("cycle_type must be 'v_cycle', 'w_cycle' or 'f_cycle'")
+        if cycle_values not in _CYCLE_VALUES:
+            raise ValueError("cycle_values must be 'float64' or 'float32'")
+        if cycle_values == "float32":
+            # what gmg_setup refuses and this constructor can already see
+            if mode != "preconditioner":
+                raise ValueError("cycle_values='float32' needs mode='preconditioner': as a solver the cycle would converge to the solution "
+                                 "of the rounded system")
+            if any(isinstance(A, Galerkin) for A in smatrices):
+                raise ValueError("cycle_values='float32' does not take a Galerkin() level")
+            if any(isinstance(ip, PatchProlongationOperator) for ip in interp):
+                raise ValueError("cycle_values='float32' does not take a PatchProlongationOperator")
         # coarsest_solver: LUSolver() (default, GMGLinearSolvers.jl:54), CGSolver(JacobiLinearSolver();...) on the device, or any
         # host-side solver wrapped in HostCallbackSolver (the analogue of passing PETSc / UMFPACK objects in Julia)
         if isinstance(coarsest_solver, NullspaceSolver):
@@ -410,6 +426,7 @@ class GMGLinearSolver:
         self.smatrices, self.interp, self.restrict = list(smatrices), list(interp), list(restrict)
         self.pre_smoothers, self.post_smoothers = list(pre_smoothers), list(post_smoothers)
         self.mode, self.cycle_type = mode, cycle_type
+        self.cycle_values = cycle_values
         self.verbose = int(verbose)
         self.log = ConvergenceLog("GMG", maxiter, atol, rtol)
         # device-side policy (no reference counterpart): `options` = {key: number} handed to gmg_set_option before the operators are
@@ -803,6 +820,8 @@ class GMGNumericalSetup:
         try:
             for k, v in solver.options.items():
                 self.set_option(k, v)
+            if getattr(solver, "cycle_values", "float64") == "float32":
+                self.set_option("values_f32", 1)
             self._upload(mat)
         except Exception:
             self.close()
@@ -1124,6 +1143,13 @@ class GMGNumericalSetup:
         abi.check(self.h, self._lib.gmg_level_format(self.h, lev, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(e)))
         return dict(layout=("CSR-stream", "SELL-64", "SELL-P", "SELL-O")[a.value], row_patterns=(a.value == 2),
                     value_dictionary=bool(b.value), idx16=bool(c.value), stream_bytes_per_nnz=d.value, padding=e.value)
+
+    def level_values(self, lev=0):
+        """gmg_level_values: what the cycle streams of this level's matrix -> dict(dtype ("float64" / "float32"),
+        cycle_stream_bytes_per_nnz)"""
+        f, d = C.c_int(0), C.c_double(0.0)
+        abi.check(self.h, self._lib.gmg_level_values(self.h, lev, C.byref(f), C.byref(d)))
+        return dict(dtype="float32" if f.value else "float64", cycle_stream_bytes_per_nnz=d.value)
 
     def level_matrix(self, lev):
         """gmg_get_galerkin_matrix: the matrix of a Galerkin level as the last setup formed it -> (shape, ptr, idx, val), 0-based CSR

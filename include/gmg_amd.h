@@ -446,6 +446,9 @@ GMG_API int gmg_set_options(gmg_handle_t h, int mode, int cycle, int maxiter, do
  * value -- a debugging / A-B device, not the configuration interface.  Keys (default):
  *   storage layout   pattern (1) pat_shared (1) opattern (1) sell (1) sell_maxpad (1.25) vdict (1) idx16 (1) force_ptr64 (0)
  *                    pat_coded_min_rows (500000) eager* (1) eager_min_rows* (20000) refresh* (1)
+ *   cycle precision  values_f32 (0; 1: the cycle streams float32 level values, see gmg_level_values) values_f32_nt (-1: non-temporal
+ *                    loads of the float stream by its size, with the thresholds of the fp64 stream; 0 never; 1 always; 2 always, the
+ *                    row-wise operands too -- float32 launches only, same bits in every setting)
  *   measurement      prof_stride (7: HIP events on every n-th sweep launch of the profiled level)
  *   sweep kernels    pat_rsweep (1) pat_r2 (1: two rows per lane in the r-gather sweep) pat_r2_occ (2: its 64-register form, eight waves per SIMD, in workgroups of eight waves on big levels; 1: four waves; 0: off) pat_r2_wgs (0 = one round of workgroups) pat_tile (0: never -- levels >= pat_tile_rows (3500000) take the pair sweep with one slice per wave; 1: tile sweep on those levels; 2: wherever it applies) pat_tile_min (512)
  *                    pat_tile_t (48) pat_tile_lds (79872) pat_strict (1) pat_fma (0: products and sums rounded separately, as the
@@ -861,6 +864,20 @@ GMG_API int gmg_model_bytes(gmg_handle_t h, double *vcycle_bytes, double *cg_ite
  * padding factor. */
 GMG_API int gmg_level_format(gmg_handle_t h, int lev, int *sell, int *vdict, int *idx16,
                              double *stream_bytes_per_nnz, double *padding);
+/* cycle_values = "float32" (no counterpart in the reference, whose level matrices are the caller's SparseMatrixCSC{Float64};
+ * GMGLinearSolvers.jl:468-500 is the cycle it applies to).  Option values_f32 = 1: inside the cycle of a preconditioner-mode handle
+ * every level but the coarsest that gmg_setup lays out as SELL-64 or SELL-O with an explicit value stream is streamed from a float
+ * copy of that stream.  The preconditioner is then exactly the fp64 cycle on the matrices whose stored values were rounded to float32
+ * (nearest even) and read back as fp64: vectors, transfers, the coarsest solve and all arithmetic stay fp64, 1/diag of such a level
+ * is that of the rounded matrix, and nothing outside the cycle reads the rounded values -- the Krylov drivers and gmg_op_apply stream
+ * the fp64 ones.  Level 0 holds both streams; levels >= 1 release their fp64 values (gmg_op_apply(GMG_OP_A) is GMG_ERR_STATE there).
+ * Levels on SELL-P / SELL-C / CSR-stream tiles and the coarsest level are untouched.  gmg_update_values[_csc] + gmg_setup refill both
+ * streams in place.  gmg_setup refuses with GMG_ERR_INVALID: mode = solver, a partitioned handle, a Galerkin level, a patch-corrected
+ * prolongation, a smoother other than Richardson-Jacobi on a level that would be float32, and a nonzero stored value outside
+ * float32's normal range (magnitude below 2^-126 or rounding to infinity; the message names level and row, nothing is scaled).
+ * gmg_level_values: *is_f32 = 1 on a float32 level, whose cycle stream is 8.0 (SELL-64: 4 B column + 4 B value) or 4.0 (SELL-O)
+ * bytes per stored nonzero; elsewhere 0 and the figure of gmg_level_format, which itself is unchanged. */
+GMG_API int gmg_level_values(gmg_handle_t h, int lev, int *is_f32, double *cycle_stream_bytes_per_nnz);
 /* Kernel + template arguments + launch geometry of the fused sweep last launched on level lev ("" before the first sweep):
  * committed counter measurements (profiles/traffic_latest.json) are only attached to a bench line whose sweep has this signature.
  * A level that has run no row sweep (patch-smoothed wide-row levels) reports the wide-row operator kernel its matrix first ran
