@@ -478,6 +478,22 @@ struct gmg_block_solver {
     if (use_precond) o.precond = [this](double *z, const double *r, double) { precond_apply(z, r); };
     return o;
   }
+  // gmg_solver::krylov_entry for the block system (vectors of length N(), one rank): the handle's own staging vectors, no retry
+  template <typename F>
+  void krylov_entry(const double *b, double *x, int memspace, int maxiter, double atol, double rtol, gmg_result *res, double *hist,
+                    int hist_cap, F &&body)
+  {
+    const int64_t n = N();
+    const double *db = eng.in_vec(b, n, memspace, st_b);
+    double *dx = (memspace == GMG_MEM_DEVICE) ? x : st_x;
+    if (memspace == GMG_MEM_HOST) eng.h2d(dx, x, n);       // x = initial guess on entry
+    if (eng.ns.project_guess) eng.ns_project_guess(dx, n, false);   // NullspaceSolvers.jl:115-116
+    ConvLog log;
+    log.configure(maxiter, atol, rtol);
+    const double last = body(n, db, dx, log);
+    eng.out_vec(x, dx, n, memspace);
+    log.export_to(res, hist, hist_cap, last);
+  }
 };
 
 // gmg_destroy on a handle that a block solver still borrows: drop the pointer, the block solver must be set up again
@@ -866,17 +882,10 @@ int gmg_block_fgmres_solve(gmg_block_handle_t h, const double *b, double *x, int
     check_block_ready(h);
     REQUIRE(b && x, GMG_ERR_INVALID, "null vector");
     REQUIRE(m0 >= 1 && m_add >= 1 && maxiter >= 0, GMG_ERR_INVALID, "bad FGMRES sizes");
-    const int64_t n = h->N();
-    const double *db = h->eng.in_vec(b, n, memspace, h->st_b);
-    double *dx = (memspace == GMG_MEM_DEVICE) ? x : h->st_x;
-    if (memspace == GMG_MEM_HOST) h->eng.h2d(dx, x, n);
-    if (h->eng.ns.project_guess) h->eng.ns_project_guess(dx, n, false);   // NullspaceSolvers.jl:115-116
-    ConvLog log;
-    log.configure(maxiter, atol, rtol);
-    KrylovOps ops = h->ops(use_precond != 0);
-    const double beta = fgmres_core(h->eng, n, n, db, dx, h->fg_V, h->fg_Z, ops, m0, restart != 0, m_add, log);
-    h->eng.out_vec(x, dx, n, memspace);
-    log.export_to(res, hist, hist_cap, beta);
+    h->krylov_entry(b, x, memspace, maxiter, atol, rtol, res, hist, hist_cap, [&](int64_t n, const double *db, double *dx, ConvLog &log) {
+      KrylovOps ops = h->ops(use_precond != 0);
+      return fgmres_core(h->eng, n, n, db, dx, h->fg_V, h->fg_Z, ops, m0, restart != 0, m_add, log);
+    });
   });
 }
 
@@ -887,17 +896,10 @@ int gmg_block_cg_solve(gmg_block_handle_t h, const double *b, double *x, int mem
     check_block_ready(h);
     REQUIRE(b && x, GMG_ERR_INVALID, "null vector");
     REQUIRE(maxiter >= 0, GMG_ERR_INVALID, "maxiter < 0");
-    const int64_t n = h->N();
-    const double *db = h->eng.in_vec(b, n, memspace, h->st_b);
-    double *dx = (memspace == GMG_MEM_DEVICE) ? x : h->st_x;
-    if (memspace == GMG_MEM_HOST) h->eng.h2d(dx, x, n);
-    if (h->eng.ns.project_guess) h->eng.ns_project_guess(dx, n, false);   // NullspaceSolvers.jl:115-116
-    ConvLog log;
-    log.configure(maxiter, atol, rtol);
-    KrylovOps ops = h->ops(use_precond != 0);
-    const double resn = cg_core(h->eng, n, db, dx, h->kw, h->kp, h->kz, h->kr, ops, flexible != 0, log);
-    h->eng.out_vec(x, dx, n, memspace);
-    log.export_to(res, hist, hist_cap, resn);
+    h->krylov_entry(b, x, memspace, maxiter, atol, rtol, res, hist, hist_cap, [&](int64_t n, const double *db, double *dx, ConvLog &log) {
+      KrylovOps ops = h->ops(use_precond != 0);
+      return cg_core(h->eng, n, db, dx, h->kw, h->kp, h->kz, h->kr, ops, flexible != 0, log);
+    });
   });
 }
 
@@ -908,17 +910,10 @@ int gmg_block_minres_solve(gmg_block_handle_t h, const double *b, double *x, int
     check_block_ready(h);
     REQUIRE(b && x, GMG_ERR_INVALID, "null vector");
     REQUIRE(maxiter >= 0, GMG_ERR_INVALID, "maxiter < 0");
-    const int64_t n = h->N();
-    const double *db = h->eng.in_vec(b, n, memspace, h->st_b);
-    double *dx = (memspace == GMG_MEM_DEVICE) ? x : h->st_x;
-    if (memspace == GMG_MEM_HOST) h->eng.h2d(dx, x, n);
-    if (h->eng.ns.project_guess) h->eng.ns_project_guess(dx, n, false);   // NullspaceSolvers.jl:115-116
-    ConvLog log;
-    log.configure(maxiter, atol, rtol);
-    KrylovOps ops = h->ops(use_precond != 0);
-    const double beta_r = minres_core(h->eng, n, n, db, dx, h->eng.minres_work(n), h->eng.mr_parts, ops, log);
-    h->eng.out_vec(x, dx, n, memspace);
-    log.export_to(res, hist, hist_cap, beta_r);
+    h->krylov_entry(b, x, memspace, maxiter, atol, rtol, res, hist, hist_cap, [&](int64_t n, const double *db, double *dx, ConvLog &log) {
+      KrylovOps ops = h->ops(use_precond != 0);
+      return minres_core(h->eng, n, n, db, dx, h->eng.minres_work(n), h->eng.mr_parts, ops, log);
+    });
   });
 }
 
@@ -934,18 +929,11 @@ int gmg_block_gmres_solve(gmg_block_handle_t h, const double *b, double *x, int 
     check_block_ready(h);
     REQUIRE(b && x, GMG_ERR_INVALID, "null vector");
     REQUIRE(m0 >= 1 && m_add >= 1 && maxiter >= 0, GMG_ERR_INVALID, "bad GMRES sizes");
-    const int64_t n = h->N();
-    const double *db = h->eng.in_vec(b, n, memspace, h->st_b);
-    double *dx = (memspace == GMG_MEM_DEVICE) ? x : h->st_x;
-    if (memspace == GMG_MEM_HOST) h->eng.h2d(dx, x, n);
-    if (h->eng.ns.project_guess) h->eng.ns_project_guess(dx, n, false);   // NullspaceSolvers.jl:115-116
-    ConvLog log;
-    log.configure(maxiter, atol, rtol);
-    KrylovOps ops = h->ops(use_precond_right != 0);
-    if (use_precond_left) ops.precond_left = [h](double *z, const double *r) { h->precond_apply(z, r); };
-    const double beta = gmres_core(h->eng, n, n, db, dx, ops, m0, restart != 0, m_add, log);
-    h->eng.out_vec(x, dx, n, memspace);
-    log.export_to(res, hist, hist_cap, beta);
+    h->krylov_entry(b, x, memspace, maxiter, atol, rtol, res, hist, hist_cap, [&](int64_t n, const double *db, double *dx, ConvLog &log) {
+      KrylovOps ops = h->ops(use_precond_right != 0);
+      if (use_precond_left) ops.precond_left = [h](double *z, const double *r) { h->precond_apply(z, r); };
+      return gmres_core(h->eng, n, n, db, dx, ops, m0, restart != 0, m_add, log);
+    });
   });
 }
 

@@ -30,6 +30,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "krylov_small.hpp"
 
 namespace gmg {
 
@@ -4024,30 +4025,7 @@ __global__ void div_dev_kernel(int64_t n, const double *__restrict__ s, double *
 // K11: MINRES (Krylov/MINRESSolvers.jl:75-148).  The solver state lives in device memory, so an iteration needs one host
 // round trip (the residual norm of the stopping rule); the Givens rotation is formed by every workgroup from that state.
 // ---------------------------------------------------------------------------
-// LinearAlgebra.givensAlgorithm(f, g) -> (c, s, r): the LAPACK dlartg form Julia ships (safmn2 rescaling, r scaled back, the sign
-// rule flipping c, s and r together).  jl_max is Julia's max (NaN if either is NaN), not fmax.
-__host__ __device__ inline double jl_max(double a, double b) { return (a != a || b != b) ? a + b : (a > b ? a : b); }
-__host__ __device__ inline void givens_lapack(double f, double g, double &cs, double &sn, double &r)
-{
-  const double safmn2 = 0x1p-485, safmx2 = 1.0 / safmn2;        // floatmin2(Float64) = reinterpret(Float64, 0x21a0000000000000)
-  if (g == 0.0) { cs = 1.0; sn = 0.0; r = f; return; }
-  if (f == 0.0) { cs = 0.0; sn = 1.0; r = g; return; }
-  double f1 = f, g1 = g, scale = jl_max(fabs(f1), fabs(g1));
-  if (scale >= safmx2) {
-    int count = 0;
-    do { ++count; f1 *= safmn2; g1 *= safmn2; scale = jl_max(fabs(f1), fabs(g1)); } while (!(scale < safmx2 || count >= 20));
-    r = sqrt(f1 * f1 + g1 * g1); cs = f1 / r; sn = g1 / r;
-    for (int i = 0; i < count; ++i) r *= safmx2;
-  } else if (scale <= safmn2) {
-    int count = 0;
-    do { ++count; f1 *= safmx2; g1 *= safmx2; scale = jl_max(fabs(f1), fabs(g1)); } while (!(scale > safmn2));
-    r = sqrt(f1 * f1 + g1 * g1); cs = f1 / r; sn = g1 / r;
-    for (int i = 0; i < count; ++i) r *= safmn2;
-  } else {
-    r = sqrt(f1 * f1 + g1 * g1); cs = f1 / r; sn = g1 / r;
-  }
-  if (fabs(f) > fabs(g) && cs < 0.0) { cs = -cs; sn = -sn; r = -r; }
-}
+// The Givens rotation of minres_update_kernel is givens_lapack (krylov_small.hpp): the function the host side of (F)GMRES calls.
 
 // The MINRES state block: two halves of kMinresState doubles, the kernels read half `cur` and minres_update_kernel writes the other
 // (its other workgroups are still reading `cur`).  beta_r < 0 marks a breakdown (sqrt of a negative beta_p: DomainError in Julia).
