@@ -80,6 +80,13 @@ SYMBOLS = {
     "gmg_galerkin_pattern": [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                              C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_int64,
                              C.POINTER(C.c_int64)],
+    "gmg_set_aggregation": [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int64],
+    "gmg_get_aggregates": [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_int64],
+    "gmg_get_prolongation": [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
+                             C.c_void_p, C.c_int64, C.c_int64],
+    "gmg_get_aggregation_info": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                 C.POINTER(C.c_int64), C.POINTER(C.c_double)],
+    "gmg_get_level_size": [C.c_void_p, C.c_int, C.POINTER(C.c_int64)],
     "gmg_set_smoother_jacobi": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double],
     "gmg_set_smoother_patch": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int64, C.c_void_p,
                                C.c_void_p, C.c_int, C.c_int],

@@ -194,15 +194,18 @@ void gmg_solver::galerkin_install(int l, bool fresh)
   else L.hA = G.C;
   L.hasA = true;
   galerkin_invalidate(l + 1);
+  aggregation_invalidate(l);
   touch();
   G.installed = true;
 }
 
 void gmg_solver::galerkin_prepare()
 {
+  aggregation_check();
   for (int l = 1; l < nlev; ++l) {
     Level &L = lev[l];
     if (!L.gal) continue;
+    aggregation_prepare(l - 1);                              // an aggregated finer level: its prolongation first (aggregation.inc.hpp)
     GalerkinLevel &G = *L.gal;
     const std::string where = "Galerkin matrix of level " + std::to_string(l) + ": ";
     REQUIRE(comm.nranks == 1, GMG_ERR_UNSUPPORTED, where + "the handle has a communicator of more than one rank; the local rows of R, A and P "
@@ -246,6 +249,7 @@ extern "C" {
 static void galerkin_values_changed(gmg_handle_t h, int lev)
 {
   if (lev + 1 < h->nlev && h->lev[lev + 1].gal) h->lev[lev + 1].gal->computed = false;
+  h->aggregation_values_changed(lev);
 }
 
 static void galerkin_refuse_update(gmg_handle_t h, int lev)
@@ -268,6 +272,7 @@ int gmg_set_galerkin(gmg_handle_t h, int lev)
     L.csc_perm.clear(); L.csc_perm.shrink_to_fit();
     L.gal = std::make_shared<GalerkinLevel>();
     h->galerkin_invalidate(lev + 1);
+    h->aggregation_invalidate(lev);
     h->touch();
   });
 }

@@ -447,11 +447,16 @@ struct GhostFix {
 
 struct GsLevel;                    // gs.inc.hpp
 struct GalerkinLevel;              // galerkin.inc.hpp
+struct AggLevel;                   // aggregation.inc.hpp
 
 struct Level {
   // Galerkin level (gmg_set_galerkin): the matrix is R (A P) of the finer level, formed at the start of gmg_setup; holds the patterns
   // of the symbolic phase and the product itself.  Null on a level whose matrix the caller gives
   std::shared_ptr<GalerkinLevel> gal;
+  // aggregated level (gmg_set_aggregation): the prolongation is built from this level's matrix by smoothed aggregation at the start of
+  // gmg_setup; holds the aggregates and P.  p_dirty: P got new values on its kept pattern since the last setup (value refresh)
+  std::shared_ptr<AggLevel> agg;
+  bool p_dirty = false;
   // s = omega*(Dinv*r) already written into sbuf[0] by the kernel that produced r (restriction / r -= A dx)
   bool s0_ready = false;
   const double *s0_src = nullptr;
@@ -4347,6 +4352,10 @@ struct gmg_solver {
   void galerkin_prepare();           // galerkin.inc.hpp: forms the matrices of the Galerkin levels that are out of date, before setup() / refresh_values()
   void galerkin_invalidate(int l);   // an operator the product of level l is formed from was replaced: patterns and values are rebuilt
   void galerkin_install(int l, bool fresh);
+  void aggregation_check() const;      // aggregation.inc.hpp: what gmg_setup refuses on a handle with aggregated levels
+  void aggregation_prepare(int l);     // builds / refreshes the prolongation of an aggregated level that is out of date
+  void aggregation_invalidate(int l);  // the matrix of level l was replaced: aggregates and P are built again
+  void aggregation_values_changed(int l);
   void build_coarse();
   double *build_dense_inverse(const HostCSR &A, const std::string &what);
   double *build_coarse_device(const HostCSR &A, const std::string &what);
@@ -5806,7 +5815,7 @@ void gmg_solver::setup()
   setup_done = true;
   was_setup = true;
   structure_dirty = false;
-  for (auto &L : lev) L.values_dirty = false;
+  for (auto &L : lev) { L.values_dirty = false; L.p_dirty = false; }
 }
 
 // numerical_setup!(ns, A): same sparsity, new values (GMGLinearSolvers.jl:260-297, JacobiLinearSolvers.jl:25-27).  Keeps every
@@ -5819,6 +5828,8 @@ bool gmg_solver::can_refresh() const
   if (!was_setup || structure_dirty || comm.nranks != 1 || !opt_int("GMG_REFRESH", 1)) return false;
   for (int l = 0; l < nlev; ++l) {
     const Level &L = lev[l];
+    // (an aggregated prolongation with new values: P and R = P^T take them in place where both layouts store explicit values)
+    if (L.p_dirty && (L.sP || L.hasR || !L.P.explicit_values() || !L.R.explicit_values())) return false;
     if (!L.values_dirty) continue;
     if (L.sA) return false;
     if (!L.A.explicit_values()) return false;
@@ -5893,6 +5904,13 @@ void gmg_solver::refresh_values()
   try {
     for (int l = 0; l < nlev; ++l) {
       Level &L = lev[l];
+      if (L.p_dirty) {                                       // aggregated prolongation: new values of P and of R = P^T on the kept patterns
+        const HostCSR Rt = transpose(L.hP);
+        refill_values(L.P, L.hP.val.data(), nullptr, st);
+        refill_values(L.R, Rt.val.data(), nullptr, st);
+        HIP_CHECK(hipStreamSynchronize(stream));
+        L.p_dirty = false;
+      }
       if (!L.values_dirty) continue;
       const int64_t n = L.n;
       const bool want_dinv = L.dinv != nullptr;
@@ -6225,7 +6243,7 @@ int gmg_set_matrix(gmg_handle_t h, int lev, int64_t nrows, int64_t ncols, int64_
     L.input_layout = layout;
     L.csc_perm.clear(); L.csc_perm.shrink_to_fit();
     L.gal.reset();                                          // (a matrix of the caller's replaces a Galerkin mark)
-    if (slot < h->nlev) h->galerkin_invalidate(slot + 1);
+    if (slot < h->nlev) { h->galerkin_invalidate(slot + 1); h->aggregation_invalidate(slot); }
     if (slot < h->nlev - 1 && h->try_eager_pattern(L.sA, 0, nrows, ncols, nnz, ptr, idx, val, layout, index_base, index_bytes)) {
       L.hA = HostCSR(); L.hA.nrows = nrows; L.hA.ncols = ncols;     // shape only
     } else
@@ -6259,7 +6277,8 @@ int gmg_set_operator_rows(gmg_handle_t h, int lev, int op, int64_t nrows_total, 
                 h->comm.nranks > 1 ? "a streamed level matrix must be square: own | ghost levels take their rows whole (gmg_set_matrix), levels in the "
                                      "overlapping layout (gmg_set_partition_overlap) and replicated levels can be streamed"
                                    : "level matrix must be square");
-      if (op == GMG_OP_A) L.gal.reset();
+      if (op == GMG_OP_A) { L.gal.reset(); h->aggregation_invalidate(lev); }
+      if (op == GMG_OP_P) { L.agg.reset(); L.p_dirty = false; }   // (a prolongation of the caller's replaces an aggregation mark)
       h->galerkin_invalidate(lev + 1);
       S = std::make_shared<PatStream>();
       S->mode = (op == GMG_OP_A) ? 0 : 1;
@@ -6500,6 +6519,7 @@ int gmg_set_prolongation(gmg_handle_t h, int lev, int64_t nrows, int64_t ncols, 
     check_level(h, lev, true);
     Level &L = h->lev[lev];
     h->galerkin_invalidate(lev + 1);
+    L.agg.reset(); L.p_dirty = false;                       // (a prolongation of the caller's replaces an aggregation mark)
     L.sP.reset();
     if (h->try_eager_pattern(L.sP, 1, nrows, ncols, nnz, ptr, idx, val, layout, index_base, index_bytes)) {
       L.hP = HostCSR(); L.hP.nrows = nrows; L.hP.ncols = ncols;     // shape only (R = P^T, if needed, is formed from the pattern form)
@@ -7803,3 +7823,4 @@ int gmg_device_bytes(gmg_handle_t h, int64_t *bytes)
 #include "cheb.inc.hpp"
 #include "pmult.inc.hpp"
 #include "galerkin.inc.hpp"
+#include "aggregation.inc.hpp"

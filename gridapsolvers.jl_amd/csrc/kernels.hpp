@@ -5579,4 +5579,326 @@ __global__ __launch_bounds__(kBlock) void galerkin_gather_kernel(int64_t nrows, 
   }
 }
 
+// ----------------------------------------------------------------------------
+// Smoothed aggregation (aggregation.inc.hpp): P_l from A_l.  Setup kernels, bandwidth-bound streams over the CSR pattern; one lane per
+// row (rows of 9 .. 125 entries) or one lane per stored entry, 64-bit row pointers, no floating-point atomics.  Every kernel writes
+// arrays that no kernel of the same step reads, so the result does not depend on the launch order.  The rows of A ascend (host check).
+// ----------------------------------------------------------------------------
+// key_i = splitmix64(i + 0x9E3779B97F4A7C15 (seed + 1)), wrapping; salt is the second term
+__device__ __forceinline__ uint64_t agg_key(int64_t i, uint64_t salt)
+{
+  uint64_t z = (uint64_t)i + salt;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+// priorities are the pairs (key, index); "none" is (0, -1), below every priority
+__device__ __forceinline__ bool agg_prio_less(uint64_t ka, int32_t ia, uint64_t kb, int32_t ib)
+{
+  if (ia < 0 || ib < 0) return ia < ib;
+  return ka < kb || (ka == kb && ia < ib);
+}
+
+// per row: the diagonal a_ii, m_i = max |a_ik| over stored k != i, and rho = max_i (sum_k |a_ik|, stored order, from 0.0) / |a_ii| as
+// an integer maximum over the bit patterns (non-negative doubles order like their bits).  A row without a stored nonzero diagonal
+// posts its index to *bad_row (the smallest wins).
+__global__ __launch_bounds__(kBlock) void agg_rowstat_kernel(int64_t n, const int64_t *__restrict__ ptr, const int32_t *__restrict__ col,
+                                                             const double *__restrict__ val, double *__restrict__ diag,
+                                                             double *__restrict__ rmax, unsigned long long *__restrict__ rho_bits,
+                                                             unsigned long long *__restrict__ bad_row)
+{
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  double d = 0.0, m = 0.0, s = 0.0;
+  for (int64_t k = ptr[i]; k < ptr[i + 1]; ++k) {
+    const double a = fabs(val[k]);
+    s = __dadd_rn(s, a);
+    if (col[k] == (int32_t)i) d = val[k];
+    else m = fmax(m, a);
+  }
+  diag[i] = d;
+  if (rmax) rmax[i] = m;
+  if (d == 0.0) { atomicMin(bad_row, (unsigned long long)i); return; }
+  atomicMax(rho_bits, (unsigned long long)__double_as_longlong(s / fabs(d)));
+}
+
+// per stored entry (i, j): the transposed entry by binary search in row j, ecol = j where {i, j} is an edge of the strength graph
+// (either direction row-strong: a != 0 and |a| >= theta m_row), else -1; w = max(|a_ij|, |a_ji|).  A missing transposed entry posts
+// (i << 32 | j) to *bad_pair (the smallest wins).  *nstrong counts the flagged entries (both directions of every edge).
+__global__ __launch_bounds__(kBlock) void agg_strong_kernel(int64_t n, int64_t nnz, const int64_t *__restrict__ ptr,
+                                                            const int32_t *__restrict__ col, const double *__restrict__ val,
+                                                            const double *__restrict__ rmax, double theta, int32_t *__restrict__ ecol,
+                                                            double *__restrict__ w, unsigned long long *__restrict__ bad_pair,
+                                                            unsigned long long *__restrict__ nstrong)
+{
+  unsigned long long cnt = 0;
+  for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < nnz; e += (int64_t)gridDim.x * kBlock) {
+    const int64_t i = galerkin_row_of<int64_t>(ptr, n, e);
+    const int32_t j = col[e];
+    int32_t out = -1;
+    double wij = 0.0;
+    if (j != (int32_t)i) {
+      const int64_t end = ptr[j + 1];
+      int64_t lo = ptr[j], hi = end;
+      while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (col[mid] < (int32_t)i) lo = mid + 1; else hi = mid;
+      }
+      const double a = fabs(val[e]);
+      double at = 0.0;
+      if (lo < end && col[lo] == (int32_t)i) at = fabs(val[lo]);
+      else atomicMin(bad_pair, ((unsigned long long)i << 32) | (unsigned long long)(uint32_t)j);
+      const bool strong = (a != 0.0 && a >= __dmul_rn(theta, rmax[i])) || (at != 0.0 && at >= __dmul_rn(theta, rmax[j]));
+      if (strong) { out = j; ++cnt; }
+      wij = fmax(a, at);
+    }
+    ecol[e] = out;
+    w[e] = wij;
+  }
+  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
+  if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(nstrong, cnt);
+}
+
+// round, step 1: t1_i = max(v_i, max over neighbours v_j), v = the priority of an undecided node (state 0), else none
+__global__ __launch_bounds__(kBlock) void agg_mis_t1_kernel(int64_t n, const int64_t *__restrict__ ptr, const int32_t *__restrict__ ecol,
+                                                            const uint8_t *__restrict__ state, uint64_t salt, uint64_t *__restrict__ tk,
+                                                            int32_t *__restrict__ ti)
+{
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  uint64_t bk = 0;
+  int32_t bi = -1;
+  if (state[i] == 0) { bk = agg_key(i, salt); bi = (int32_t)i; }
+  for (int64_t k = ptr[i]; k < ptr[i + 1]; ++k) {
+    const int32_t j = ecol[k];
+    if (j < 0 || state[j] != 0) continue;
+    const uint64_t kj = agg_key(j, salt);
+    if (agg_prio_less(bk, bi, kj, j)) { bk = kj; bi = j; }
+  }
+  tk[i] = bk; ti[i] = bi;
+}
+
+// round, step 2: t2_i = max(t1_i, max over neighbours t1_j); an undecided i whose t2 is its own priority becomes a root
+__global__ __launch_bounds__(kBlock) void agg_mis_t2_kernel(int64_t n, const int64_t *__restrict__ ptr, const int32_t *__restrict__ ecol,
+                                                            const uint8_t *__restrict__ state, const uint64_t *__restrict__ tk,
+                                                            const int32_t *__restrict__ ti, uint8_t *__restrict__ root)
+{
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  uint8_t r = 0;
+  if (state[i] == 0) {
+    uint64_t bk = tk[i];
+    int32_t bi = ti[i];
+    for (int64_t k = ptr[i]; k < ptr[i + 1]; ++k) {
+      const int32_t j = ecol[k];
+      if (j < 0) continue;
+      const uint64_t kj = tk[j];
+      const int32_t ij = ti[j];
+      if (agg_prio_less(bk, bi, kj, ij)) { bk = kj; bi = ij; }
+    }
+    r = bi == (int32_t)i ? 1 : 0;
+  }
+  root[i] = r;
+}
+
+// round, step 3: f1_i = i or a neighbour is a root of this round
+__global__ __launch_bounds__(kBlock) void agg_mis_f1_kernel(int64_t n, const int64_t *__restrict__ ptr, const int32_t *__restrict__ ecol,
+                                                            const uint8_t *__restrict__ root, uint8_t *__restrict__ f1)
+{
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  uint8_t f = root[i];
+  for (int64_t k = ptr[i]; k < ptr[i + 1] && !f; ++k) {
+    const int32_t j = ecol[k];
+    if (j >= 0 && root[j]) f = 1;
+  }
+  f1[i] = f;
+}
+
+// round, step 4: f2_i = f1_i or f1_j of a neighbour; an undecided node becomes a root (1), covered (2, when f2_i) or stays undecided,
+// and the nodes that stay undecided are counted (one integer atomic per wave)
+__global__ __launch_bounds__(kBlock) void agg_mis_f2_kernel(int64_t n, const int64_t *__restrict__ ptr, const int32_t *__restrict__ ecol,
+                                                            const uint8_t *__restrict__ root, const uint8_t *__restrict__ f1,
+                                                            uint8_t *__restrict__ state, unsigned long long *__restrict__ undecided)
+{
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  unsigned long long left = 0;
+  if (i < n && state[i] == 0) {
+    if (root[i]) state[i] = 1;
+    else {
+      uint8_t f = f1[i];
+      for (int64_t k = ptr[i]; k < ptr[i + 1] && !f; ++k) {
+        const int32_t j = ecol[k];
+        if (j >= 0 && f1[j]) f = 1;
+      }
+      if (f) state[i] = 2;
+      else left = 1;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) left += __shfl_down(left, off, 64);
+  if ((threadIdx.x & 63) == 0 && left) atomicAdd(undecided, left);
+}
+
+// exclusive prefix sum of int32 counts into int64, three launches: per block of kAggScanTile items the local scan and the block total,
+// one workgroup over the block totals, then the block offsets added (out[n] = the grand total)
+constexpr int kAggScanItems = 4, kAggScanTile = kBlock * kAggScanItems;
+__device__ __forceinline__ int64_t agg_block_exscan(int64_t v, int64_t *sh, int64_t &total)
+{
+  const int t = threadIdx.x;
+  sh[t] = v;
+  __syncthreads();
+  for (int off = 1; off < kBlock; off <<= 1) {
+    const int64_t add = t >= off ? sh[t - off] : 0;
+    __syncthreads();
+    sh[t] += add;
+    __syncthreads();
+  }
+  total = sh[kBlock - 1];
+  const int64_t ex = sh[t] - v;
+  __syncthreads();
+  return ex;
+}
+__global__ __launch_bounds__(kBlock) void agg_scan_local_kernel(int64_t n, const int32_t *__restrict__ in, int64_t *__restrict__ out,
+                                                                int64_t *__restrict__ bsum)
+{
+  __shared__ int64_t sh[kBlock];
+  const int64_t base = (int64_t)blockIdx.x * kAggScanTile + (int64_t)threadIdx.x * kAggScanItems;
+  int64_t v[kAggScanItems], s = 0;
+#pragma unroll
+  for (int q = 0; q < kAggScanItems; ++q) { v[q] = base + q < n ? (int64_t)in[base + q] : 0; s += v[q]; }
+  int64_t total;
+  int64_t ex = agg_block_exscan(s, sh, total);
+#pragma unroll
+  for (int q = 0; q < kAggScanItems; ++q) { if (base + q < n) out[base + q] = ex; ex += v[q]; }
+  if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+__global__ __launch_bounds__(kBlock) void agg_scan_top_kernel(int64_t nb, int64_t *__restrict__ bsum, int64_t *__restrict__ total_out)
+{
+  __shared__ int64_t sh[kBlock];
+  int64_t carry = 0;
+  for (int64_t b0 = 0; b0 < nb; b0 += kBlock) {
+    const int64_t b = b0 + threadIdx.x;
+    const int64_t v = b < nb ? bsum[b] : 0;
+    int64_t total;
+    const int64_t ex = agg_block_exscan(v, sh, total);
+    if (b < nb) bsum[b] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0) *total_out = carry;
+}
+__global__ __launch_bounds__(kBlock) void agg_scan_add_kernel(int64_t n, int64_t *__restrict__ out, const int64_t *__restrict__ bsum)
+{
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) out[i] += bsum[i / kAggScanTile];
+}
+
+__global__ __launch_bounds__(kBlock) void agg_rootflag_kernel(int64_t n, const uint8_t *__restrict__ state, int32_t *__restrict__ flag)
+{
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) flag[i] = state[i] == 1 ? 1 : 0;
+}
+
+// pass 1: a root takes its number (roots are numbered in ascending row index), a non-root with a root neighbour that root's; else -1
+__global__ __launch_bounds__(kBlock) void agg_pass1_kernel(int64_t n, const int64_t *__restrict__ ptr, const int32_t *__restrict__ ecol,
+                                                           const uint8_t *__restrict__ state, const int64_t *__restrict__ rootid,
+                                                           int32_t *__restrict__ agg1)
+{
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  int32_t a = -1;
+  if (state[i] == 1) a = (int32_t)rootid[i];
+  else
+    for (int64_t k = ptr[i]; k < ptr[i + 1]; ++k) {
+      const int32_t j = ecol[k];
+      if (j >= 0 && state[j] == 1) { a = (int32_t)rootid[j]; break; }
+    }
+  agg1[i] = a;
+}
+
+// pass 2: a node pass 1 left out takes the aggregate of the neighbour pass 1 assigned with the largest w_ij, ties to the smallest j
+// (the row ascends, the comparison is strict).  A node that finds none is counted in *unassigned (cannot happen: a covered node is
+// within distance 2 of a root).
+__global__ __launch_bounds__(kBlock) void agg_pass2_kernel(int64_t n, const int64_t *__restrict__ ptr, const int32_t *__restrict__ ecol,
+                                                           const double *__restrict__ w, const int32_t *__restrict__ agg1,
+                                                           int32_t *__restrict__ agg, unsigned long long *__restrict__ unassigned)
+{
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  int32_t a = agg1[i];
+  if (a < 0) {
+    double best = -1.0;
+    for (int64_t k = ptr[i]; k < ptr[i + 1]; ++k) {
+      const int32_t j = ecol[k];
+      if (j < 0) continue;
+      const int32_t aj = agg1[j];
+      if (aj >= 0 && w[k] > best) { best = w[k]; a = aj; }
+    }
+    if (a < 0) { atomicAdd(unassigned, 1ull); a = 0; }
+  }
+  agg[i] = a;
+}
+
+// per stored entry: the aggregate of its column
+__global__ __launch_bounds__(kBlock) void agg_entry_kernel(int64_t nnz, const int32_t *__restrict__ col, const int32_t *__restrict__ agg,
+                                                           int32_t *__restrict__ ac)
+{
+  for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < nnz; e += (int64_t)gridDim.x * kBlock) ac[e] = agg[col[e]];
+}
+
+// per row: the distinct aggregates among its stored entries in ascending order (the next one is the smallest above the last one);
+// pcol == nullptr: the count only
+__global__ __launch_bounds__(kBlock) void agg_prow_kernel(int64_t n, const int64_t *__restrict__ ptr, const int32_t *__restrict__ ac,
+                                                          int32_t *__restrict__ cnt, const int64_t *__restrict__ pptr,
+                                                          int32_t *__restrict__ pcol)
+{
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const int64_t k0 = ptr[i], k1 = ptr[i + 1];
+  int64_t q = pcol ? pptr[i] : 0;
+  int32_t last = -1, c = 0;
+  for (;;) {
+    int32_t next = INT32_MAX;
+    for (int64_t k = k0; k < k1; ++k) {
+      const int32_t J = ac[k];
+      if (J > last && J < next) next = J;
+    }
+    if (next == INT32_MAX) break;
+    if (pcol) pcol[q++] = next;
+    last = next;
+    ++c;
+  }
+  if (cnt) cnt[i] = c;
+}
+
+// per row: P(i, J) = t - w_i s_J, t = 1 for J = agg(i) else 0, s_J = sum over stored k ascending with agg(k) = J of a_ik from 0.0,
+// w_i = omega (1 / a_ii); every product and sum rounded separately
+__global__ __launch_bounds__(kBlock) void agg_pval_kernel(int64_t n, const int64_t *__restrict__ ptr, const double *__restrict__ val,
+                                                          const int32_t *__restrict__ ac, const int32_t *__restrict__ agg,
+                                                          const double *__restrict__ diag, double omega, const int64_t *__restrict__ pptr,
+                                                          const int32_t *__restrict__ pcol, double *__restrict__ pval)
+{
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const int64_t k0 = ptr[i], k1 = ptr[i + 1];
+  const double wi = __dmul_rn(omega, 1.0 / diag[i]);
+  const int32_t mine = agg[i];
+  for (int64_t q = pptr[i]; q < pptr[i + 1]; ++q) {
+    const int32_t J = pcol[q];
+    double s = 0.0;
+    for (int64_t k = k0; k < k1; ++k)
+      if (ac[k] == J) s = __dadd_rn(s, val[k]);
+    pval[q] = __dsub_rn(J == mine ? 1.0 : 0.0, __dmul_rn(wi, s));
+  }
+}
+
+// the tentative prolongation T (smooth = 0): one stored 1.0 per row at column agg(i)
+__global__ __launch_bounds__(kBlock) void agg_tentative_kernel(int64_t n, const int32_t *__restrict__ agg, int64_t *__restrict__ pptr,
+                                                               int32_t *__restrict__ pcol, double *__restrict__ pval)
+{
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i > n) return;
+  pptr[i] = i;
+  if (i < n) { pcol[i] = agg[i]; pval[i] = 1.0; }
+}
+
 } // namespace gmg

@@ -39,6 +39,7 @@ export HipGMGLinearSolver, HipCGSolver, HipFGMRESSolver, HipMINRESSolver, PatchT
 export ChebyshevSmoother, chebyshev_info
 export MultiplicativePatchSmoother, patch_coloring
 export Galerkin, level_matrix, galerkin_pattern
+export Aggregation, aggregates, aggregated_prolongation, aggregation_info, level_size
 export LanczosDiagnostic, estimate!, cg_set_trace!, cg_trace
 export HipRichardsonLinearSolver, HipBlockTriangularSolver, HipBlockDiagonalSolver, HipBlockFGMRESSolver, block_mul!, block_cg_solve!
 export block_minres_solve!
@@ -100,6 +101,26 @@ end
 # be `nothing` or Galerkin()).  One GPU, operators of the finer level handed over whole.
 struct Galerkin end
 
+# Aggregation(; theta, smooth, omega, seed): marker for an entry of interp -- the prolongation of that level is built on the device from the
+# level's matrix by smoothed aggregation at the numerical setup (gmg_set_aggregation); the next entry of smatrices must be Galerkin():
+#   HipGMGLinearSolver(Any[A1, Galerkin(), Galerkin()], Any[Aggregation(), Aggregation()]; ...)
+# theta: strength threshold against the largest off-diagonal entry of the row; smooth = false: the tentative prolongation; omega = nothing:
+# (4/3) / the infinity-norm bound of D^-1 A; seed: of the priorities of the independent set.  The reference has the caller's transfers
+# only (it leaves for PETSc GAMG where there is no mesh hierarchy).  One GPU, constant near-null space, no explicit restriction on the
+# level.  aggregates / aggregated_prolongation / aggregation_info / level_size return what was built.
+struct Aggregation
+  theta  :: Float64
+  smooth :: Bool
+  omega  :: Union{Nothing,Float64}
+  seed   :: Int64
+  function Aggregation(; theta = 0.25, smooth = true, omega = nothing, seed = 0)
+    @assert 0.0 <= theta <= 1.0
+    @assert isnothing(omega) || omega > 0.0
+    @assert seed >= 0
+    new(Float64(theta), smooth, isnothing(omega) ? nothing : Float64(omega), Int64(seed))
+  end
+end
+
 struct HipGMGLinearSolver{A,B,C,D,E,F} <: Gridap.Algebra.LinearSolver
   smatrices      :: A
   interp         :: B           # explicit sparse prolongations, level l+1 -> l
@@ -136,6 +157,12 @@ function HipGMGLinearSolver(
   @assert nlev-1 == length(interp) == length(pre_smoothers) == length(post_smoothers)
   @assert smatrices[1] isa AbstractMatrix && all(M -> M isa AbstractMatrix || M isa Galerkin, smatrices)
   @assert isnothing(restrict) || length(restrict) == nlev-1
+  for l in 1:nlev-1                                          # Aggregation() entries: what gmg_setup refuses and is visible here
+    interp[l] isa Aggregation || continue
+    @assert smatrices[l+1] isa Galerkin "interp[$l] is Aggregation(): smatrices[$(l+1)] must be Galerkin()"
+    @assert isnothing(restrict) || isnothing(restrict[l]) "interp[$l] is Aggregation(): level $l takes no explicit restriction"
+    @assert l+1 > nlev-1 || !(interp[l+1] isa HipPatchProlongation) "level $(l+1) takes its size from the aggregation of level $l"
+  end
   @assert mode ∈ [:preconditioner,:solver]
   @assert cycle_type ∈ [:v_cycle,:w_cycle,:f_cycle]
   tols = SolverTolerances{Float64}(;maxiter=maxiter,atol=atol,rtol=rtol)
@@ -475,7 +502,10 @@ function Gridap.Algebra.numerical_setup(ss::HipGMGSymbolicSetup, mat::AbstractMa
   end
   for l in 1:nlev-1
     ip = s.interp[l]
-    if ip isa HipPatchProlongation
+    if ip isa Aggregation
+      check(h, ccall((:gmg_set_aggregation, libgmgamd), Cint, (Ptr{Cvoid},Cint,Float64,Cint,Float64,Int64),
+                     h, l-1, ip.theta, ip.smooth ? 1 : 0, isnothing(ip.omega) ? 0.0 : ip.omega, ip.seed))
+    elseif ip isa HipPatchProlongation
       _set_op(:prolongation, h, l-1, ip.P)
       T = ip.patches
       GC.@preserve T begin
@@ -486,7 +516,7 @@ function Gridap.Algebra.numerical_setup(ss::HipGMGSymbolicSetup, mat::AbstractMa
     else
       _set_op(:prolongation, h, l-1, ip)
     end
-    !isnothing(s.restrict) && _set_op(:restriction, h, l-1, s.restrict[l])
+    !isnothing(s.restrict) && !isnothing(s.restrict[l]) && _set_op(:restriction, h, l-1, s.restrict[l])
     if s.post_smoothers[l] === s.pre_smoothers[l]
       _set_smoother(h, l-1, GMG_PRE_AND_POST, s.pre_smoothers[l])
     else
@@ -519,6 +549,49 @@ function level_matrix(ns::HipGMGNumericalSetup, lev::Integer)
   end
   # the rows of the CSR are the columns of the transpose's CSC
   return SparseMatrixCSC{Float64,Int64}(copy(transpose(SparseMatrixCSC{Float64,Int64}(n[], n[], ptr .+ 1, Int64.(col) .+ 1, val))))
+end
+
+# gmg_get_level_size: rows of a level after the setup (lev is 1-based; levels below an Aggregation() have no size before)
+function level_size(ns::HipGMGNumericalSetup, lev::Integer)
+  n = Ref(Int64(0))
+  check(ns.handle, ccall((:gmg_get_level_size, libgmgamd), Cint, (Ptr{Cvoid},Cint,Ref{Int64}), ns.handle, lev-1, n))
+  return Int(n[])
+end
+
+# gmg_get_aggregates: the aggregate (1-based) of every row of an Aggregation() level and their number
+function aggregates(ns::HipGMGNumericalSetup, lev::Integer)
+  nagg = Ref(Int64(0))
+  agg = Vector{Int32}(undef, level_size(ns, lev))
+  GC.@preserve agg begin
+    check(ns.handle, ccall((:gmg_get_aggregates, libgmgamd), Cint, (Ptr{Cvoid},Cint,Ref{Int64},Ptr{Int32},Int64),
+                           ns.handle, lev-1, nagg, pointer(agg), length(agg)))
+  end
+  return agg .+ Int32(1), Int(nagg[])
+end
+
+# gmg_get_prolongation: the prolongation of an Aggregation() level as the last setup formed it
+function aggregated_prolongation(ns::HipGMGNumericalSetup, lev::Integer)
+  nr, nc, nnz = Ref(Int64(0)), Ref(Int64(0)), Ref(Int64(0))
+  T = (Ptr{Cvoid},Cint,Ref{Int64},Ref{Int64},Ref{Int64},Ptr{Int64},Ptr{Int32},Ptr{Float64},Int64,Int64)
+  check(ns.handle, ccall((:gmg_get_prolongation, libgmgamd), Cint, T, ns.handle, lev-1, nr, nc, nnz, C_NULL, C_NULL, C_NULL, 0, 0))
+  ptr, col, val = Vector{Int64}(undef, nr[]+1), Vector{Int32}(undef, nnz[]), Vector{Float64}(undef, nnz[])
+  GC.@preserve ptr col val begin
+    check(ns.handle, ccall((:gmg_get_prolongation, libgmgamd), Cint, T, ns.handle, lev-1, nr, nc, nnz, pointer(ptr), pointer(col), pointer(val),
+                           length(ptr), nnz[]))
+  end
+  # the rows of the CSR are the columns of the transpose's CSC
+  return SparseMatrixCSC{Float64,Int64}(copy(transpose(SparseMatrixCSC{Float64,Int64}(nc[], nr[], ptr .+ 1, Int64.(col) .+ 1, val))))
+end
+
+# gmg_get_aggregation_info: what the last aggregation of the level did (times in ms: strength, independent set, assignment, P)
+function aggregation_info(ns::HipGMGNumericalSetup, lev::Integer)
+  rounds, omega, rho, edges, ms = Ref(Cint(0)), Ref(0.0), Ref(0.0), Ref(Int64(0)), zeros(Float64, 4)
+  GC.@preserve ms begin
+    check(ns.handle, ccall((:gmg_get_aggregation_info, libgmgamd), Cint, (Ptr{Cvoid},Cint,Ref{Cint},Ref{Float64},Ref{Float64},Ref{Int64},Ptr{Float64}),
+                           ns.handle, lev-1, rounds, omega, rho, edges, pointer(ms)))
+  end
+  return (rounds = Int(rounds[]), omega = omega[], rho = rho[], strong_edges = Int(edges[]), strength_ms = ms[1], mis_ms = ms[2],
+          assign_ms = ms[3], p_ms = ms[4])
 end
 
 # the coarsest matrix a host-side coarsest solver is set up on: of a Galerkin level, the product (the handle is set up once to form it)

@@ -296,12 +296,44 @@ class Galerkin:
         return "Galerkin()"
 
 
+class Aggregation:
+    """Aggregation(theta=0.25, smooth=True, omega=None, seed=0): marker for an entry of interp -- the prolongation of that level is built
+    on the device from the level's matrix by smoothed aggregation at the numerical setup (gmg_set_aggregation); the next entry of
+    smatrices must be Galerkin():
+        GMGLinearSolver([A0, Galerkin(), Galerkin()], [Aggregation(), Aggregation()])
+    theta: strength threshold against the largest off-diagonal entry of the row; smooth=False: the tentative (piecewise constant)
+    prolongation; omega=None: (4/3) / the infinity-norm bound of D^-1 A; seed: of the priorities of the independent set.  The reference
+    has the caller's transfers only.  One GPU; constant near-null space.  GMGNumericalSetup.aggregates / prolongation / aggregation_info
+    return what was built."""
+
+    def __init__(self, theta=0.25, smooth=True, omega=None, seed=0):
+        if not 0.0 <= float(theta) <= 1.0:
+            raise ValueError("theta must lie in [0, 1]")
+        if omega is not None and not float(omega) > 0.0:
+            raise ValueError("omega must be positive (None: automatic)")
+        if int(seed) < 0:
+            raise ValueError("seed must not be negative")
+        self.theta, self.smooth, self.omega, self.seed = float(theta), bool(smooth), None if omega is None else float(omega), int(seed)
+
+    def __repr__(self):
+        return f"Aggregation(theta={self.theta}, smooth={self.smooth}, omega={self.omega}, seed={self.seed})"
+
+
 def _level_size(smatrices, interp, l):
-    """rows of level l: of its matrix, or, for a Galerkin level, the columns of the prolongation onto the finer level"""
+    """rows of level l: of its matrix, or, for a Galerkin level, the columns of the prolongation onto the finer level; None (unknown
+    until the setup) where that prolongation is an Aggregation()"""
     if not isinstance(smatrices[l], Galerkin):
         return int(smatrices[l].shape[0])
     ip = interp[l - 1]
+    if isinstance(ip, Aggregation):
+        return None
     return int((ip.P if isinstance(ip, PatchProlongationOperator) else ip).shape[1])
+
+
+def _is_patch_smoother(sm):
+    if isinstance(sm, (ChebyshevSmoother, MultiplicativePatchSmoother)):
+        return not isinstance(sm.M, JacobiLinearSolver)
+    return isinstance(sm, RichardsonSmoother) and not isinstance(sm.M, JacobiLinearSolver)
 
 
 def galerkin_pattern(R, A, P):
@@ -408,6 +440,24 @@ class GMGLinearSolver:
                 raise ValueError("cycle_values='float32' does not take a Galerkin() level")
             if any(isinstance(ip, PatchProlongationOperator) for ip in interp):
                 raise ValueError("cycle_values='float32' does not take a PatchProlongationOperator")
+        # Aggregation() entries of interp: what gmg_setup refuses and this constructor can already see
+        for l, ip in enumerate(interp):
+            if not isinstance(ip, Aggregation):
+                continue
+            if not isinstance(smatrices[l + 1], Galerkin):
+                raise ValueError(f"interp[{l}] is Aggregation(): smatrices[{l + 1}] must be Galerkin(), a matrix of the caller's cannot "
+                                 f"match the aggregates of level {l}")
+            if restrict[l] is not None:
+                raise ValueError(f"interp[{l}] is Aggregation(): level {l} takes no explicit restriction (restrict[{l}]), R = P^T")
+            if hasattr(smatrices[l], "row_blocks"):
+                raise ValueError(f"interp[{l}] is Aggregation(): the matrix of level {l} is streamed, the aggregation needs its rows")
+            if l + 1 < nlev - 1:
+                if _is_patch_smoother(pre_smoothers[l + 1]) or _is_patch_smoother(post_smoothers[l + 1]):
+                    raise ValueError(f"level {l + 1} takes its size from the aggregation of level {l}: a patch-based smoother there is "
+                                     f"refused, its tables cannot match")
+                if isinstance(interp[l + 1], PatchProlongationOperator):
+                    raise ValueError(f"level {l + 1} takes its size from the aggregation of level {l}: a PatchProlongationOperator there "
+                                     f"is refused, its tables cannot match")
         # coarsest_solver: LUSolver() (default, GMGLinearSolvers.jl:54), CGSolver(JacobiLinearSolver();...) on the device, or any
         # host-side solver wrapped in HostCallbackSolver (the analogue of passing PETSc / UMFPACK objects in Julia)
         if isinstance(coarsest_solver, NullspaceSolver):
@@ -415,6 +465,8 @@ class GMGLinearSolver:
             if not (coarsest_solver.constrain_matrix and isinstance(coarsest_solver.solver, LUSolver)):
                 raise NotImplementedError("coarsest_solver: NullspaceSolver(LUSolver(), N_coarse) with constrain_matrix=True "
                                           "(an iterative coarsest solver needs no constraint: CGSolver(JacobiLinearSolver()))")
+            if _level_size(smatrices, interp, nlev - 1) is None:
+                raise ValueError(f"coarsest_solver: a null space cannot be given for level {nlev - 1}, whose size comes from an Aggregation()")
             if coarsest_solver.nullspace.size()[1] != _level_size(smatrices, interp, nlev - 1):
                 raise ValueError(f"coarsest_solver: the null space has vectors of length {coarsest_solver.nullspace.size()[1]}, "
                                  f"the coarsest matrix {_level_size(smatrices, interp, nlev - 1)} rows")
@@ -900,7 +952,9 @@ class GMGNumericalSetup:
                 _set_op(lib.gmg_set_matrix, h, l, A)
         for l in range(nlev - 1):
             ip = s.interp[l]
-            if isinstance(ip, PatchProlongationOperator):
+            if isinstance(ip, Aggregation):
+                abi.check(h, lib.gmg_set_aggregation(h, l, ip.theta, 1 if ip.smooth else 0, 0.0 if ip.omega is None else ip.omega, ip.seed))
+            elif isinstance(ip, PatchProlongationOperator):
                 _set_op(lib.gmg_set_prolongation, h, l, ip.P)
                 abi.check(h, lib.gmg_set_prolongation_patch_correction(
                     h, l, ip.kind, ip.patch_ptr.size - 1, C.c_void_p(ip.patch_ptr.ctypes.data),
@@ -941,9 +995,10 @@ class GMGNumericalSetup:
         elif isinstance(cs, NullspaceSolver):
             Kc = np.ascontiguousarray(cs.nullspace.matrix_representation().T)      # vector q at Kc + q*n_L
             abi.check(h, lib.gmg_set_coarse_nullspace(h, Kc.shape[0], C.c_void_p(Kc.ctypes.data), Kc.shape[1]))
-        abi.check(h, lib.gmg_setup(h))
         self.n = int(mats[0].shape[0])
         self.sizes = [_level_size(mats, s.interp, l) for l in range(nlev)]
+        abi.check(h, lib.gmg_setup(h))
+        self.sizes = [self.level_size(l) if n is None else n for l, n in enumerate(self.sizes)]
 
     def _set_gs_ordering(self, l, pre, post):
         """one visiting order per level (gmg_set_gs_ordering): the one its Gauss-Seidel smoother(s) name"""
@@ -1160,6 +1215,39 @@ class GMGNumericalSetup:
         abi.check(self.h, self._lib.gmg_get_galerkin_matrix(self.h, lev, C.byref(n), C.byref(nnz), C.c_void_p(ptr.ctypes.data),
                                                             C.c_void_p(idx.ctypes.data), C.c_void_p(val.ctypes.data), nnz.value))
         return (n.value, n.value), ptr, idx, val
+
+    def level_size(self, lev):
+        """gmg_get_level_size: rows of a level after the setup (levels below an Aggregation() have no size before)"""
+        n = C.c_int64()
+        abi.check(self.h, self._lib.gmg_get_level_size(self.h, lev, C.byref(n)))
+        return n.value
+
+    def aggregates(self, lev):
+        """gmg_get_aggregates: -> (agg, nagg): the aggregate 0 .. nagg-1 of every row of an Aggregation() level (int32)"""
+        nagg, n = C.c_int64(), self.sizes[lev]
+        if n is None:
+            n = self.level_size(lev)
+        agg = np.empty(n, dtype=np.int32)
+        abi.check(self.h, self._lib.gmg_get_aggregates(self.h, lev, C.byref(nagg), C.c_void_p(agg.ctypes.data), agg.size))
+        return agg, nagg.value
+
+    def prolongation(self, lev):
+        """gmg_get_prolongation: the prolongation of an Aggregation() level as the last setup formed it -> (shape, ptr, idx, val),
+        0-based CSR with int64 pointers and int32 columns"""
+        nr, nc, nnz = C.c_int64(), C.c_int64(), C.c_int64()
+        abi.check(self.h, self._lib.gmg_get_prolongation(self.h, lev, C.byref(nr), C.byref(nc), C.byref(nnz), None, None, None, 0, 0))
+        ptr, idx, val = np.empty(nr.value + 1, dtype=np.int64), np.empty(nnz.value, dtype=np.int32), np.empty(nnz.value)
+        abi.check(self.h, self._lib.gmg_get_prolongation(self.h, lev, C.byref(nr), C.byref(nc), C.byref(nnz), C.c_void_p(ptr.ctypes.data),
+                                                         C.c_void_p(idx.ctypes.data), C.c_void_p(val.ctypes.data), ptr.size, nnz.value))
+        return (nr.value, nc.value), ptr, idx, val
+
+    def aggregation_info(self, lev):
+        """gmg_get_aggregation_info: what the last aggregation of the level did -> dict(rounds, omega, rho, strong_edges, strength_ms,
+        mis_ms, assign_ms, p_ms)"""
+        r, om, rho, se, ms = C.c_int(), C.c_double(), C.c_double(), C.c_int64(), (C.c_double * 4)()
+        abi.check(self.h, self._lib.gmg_get_aggregation_info(self.h, lev, C.byref(r), C.byref(om), C.byref(rho), C.byref(se), ms))
+        return dict(rounds=r.value, omega=om.value, rho=rho.value, strong_edges=se.value, strength_ms=ms[0], mis_ms=ms[1], assign_ms=ms[2],
+                    p_ms=ms[3])
 
     def galerkin_timing(self, lev):
         """gmg_get_galerkin_timing: what the last product of a Galerkin level cost, in ms"""

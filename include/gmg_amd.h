@@ -179,6 +179,48 @@ GMG_API int gmg_galerkin_pattern(int64_t nc, int64_t nf, const int64_t *rptr, co
                                  const int32_t *acol, const int64_t *pptr, const int32_t *pcol, int64_t *tptr, int32_t *tcol,
                                  int64_t tcap, int64_t *tnnz, int64_t *cptr, int32_t *ccol, int64_t ccap, int64_t *cnnz);
 
+/* Smoothed-aggregation prolongations: level lev (0 .. nlevels-2) takes P_lev built from A_lev on the device at gmg_setup instead of a
+ * prolongation of the caller's -- with gmg_set_galerkin on the levels below, a hierarchy without any mesh hierarchy (what the reference
+ * leaves to PETSc GAMG).  No reference counterpart.  The construction is fixed, bit for bit (tests/aggregation_reference.py):
+ *   strength    m_i = max over stored k != i of |a_ik|; (i, j), j != i, a_ij != 0, is row-strong iff |a_ij| >= theta * m_i; {i, j} is an
+ *               edge iff (i, j) or (j, i) is row-strong; w_ij = max(|a_ij|, |a_ji|).  Explicit zeros are legal and never strong.
+ *   MIS-2       priorities (key_i, i), key_i = the splitmix64 finaliser of i + 0x9E3779B97F4A7C15 (seed + 1); synchronous rounds
+ *               until no node is undecided: the undecided node that is the maximum of its distance-2 neighbourhood becomes a root,
+ *               undecided nodes within distance 2 of a root become covered
+ *   aggregates  roots numbered in ascending row index; a root's neighbours join it; every other node joins the aggregate of the
+ *               neighbour assigned so far with the largest w_ij, ties to the smallest index
+ *   P           smooth = 0: one 1.0 per row at column agg(i).  smooth != 0: (I - omega D^-1 A) T, row i over {agg(k) : (i, k) stored}
+ *               ascending, P(i, J) = [J == agg(i)] - (omega (1 / a_ii)) * (sum over stored k ascending with agg(k) = J of a_ik),
+ *               every product and sum rounded separately
+ *   omega       the argument if > 0, else (4/3) / rho with rho = max_i (sum_k |a_ik|) / |a_ii|, the infinity-norm bound of D^-1 A: the
+ *               same bits on every run, and an under-smoothing against the true largest eigenvalue
+ * theta in [0, 1] (0.25 is the usual choice), seed >= 0.  The near-null space is the constant vector; vector-valued candidates
+ * (rigid-body modes), filtered matrices and partitioned handles are not built.
+ * A_lev needs a stored nonzero diagonal in every row (GMG_ERR_SINGULAR at gmg_setup, naming the row) and a structurally symmetric
+ * stored pattern (checked on the device; GMG_ERR_INVALID naming the first offending (i, j)).
+ * At gmg_setup, finest level first: A_lev (the caller's, or the Galerkin product just formed) is aggregated, P_lev is installed exactly
+ * as gmg_set_prolongation installs a caller's matrix, the product of level lev+1 follows; every size below is taken from the result.
+ * The device temporaries are freed and never part of gmg_device_bytes.  After gmg_update_values on a finer level the next gmg_setup
+ * keeps the aggregates, the pattern of P and the Galerkin patterns and forms rho, omega, the values of P and the products again -- the
+ * strength of connection is NOT evaluated again; gmg_set_matrix aggregates afresh.  A later gmg_set_prolongation clears the mark.
+ * Refused at gmg_setup with GMG_ERR_UNSUPPORTED or GMG_ERR_INVALID, naming the level: a communicator of more than one rank, real or
+ * loopback; a level matrix streamed with gmg_set_operator_rows; a patch-corrected prolongation or an explicit restriction on the
+ * level; level lev+1 not marked with gmg_set_galerkin; values_f32 (refuses the Galerkin level); a level that does not coarsen
+ * (as many aggregates as rows); a patch-based smoother or prolongation on level lev+1, whose tables cannot match. */
+GMG_API int gmg_set_aggregation(gmg_handle_t h, int lev, double theta, int smooth, double omega, int64_t seed);
+/* The aggregate of every row of the level, 0 .. *nagg-1, as the last gmg_setup formed them (also after a gmg_setup that refused the
+ * level because it does not coarsen).  agg NULL: size query; cap < rows: GMG_ERR_INVALID.  No aggregates yet: GMG_ERR_STATE. */
+GMG_API int gmg_get_aggregates(gmg_handle_t h, int lev, int64_t *nagg, int32_t *agg, int64_t cap);
+/* The prolongation of an aggregated level after gmg_setup, 0-based CSR: ptr[nrows + 1], col[nnz], val[nnz].  All three arrays NULL:
+ * size query.  ptr_cap < nrows + 1 or nnz_cap < nnz: GMG_ERR_INVALID.  A level without aggregation: GMG_ERR_STATE. */
+GMG_API int gmg_get_prolongation(gmg_handle_t h, int lev, int64_t *nrows, int64_t *ncols, int64_t *nnz, int64_t *ptr, int32_t *col,
+                                 double *val, int64_t ptr_cap, int64_t nnz_cap);
+/* What the last aggregation of the level did: rounds of the independent set, omega and rho in use, edges of the strength graph, and
+ * the HIP-event times in ms of ms[0] strength (+ rho), ms[1] independent set, ms[2] assignment, ms[3] P.  Any output may be NULL. */
+GMG_API int gmg_get_aggregation_info(gmg_handle_t h, int lev, int *rounds, double *omega, double *rho, int64_t *strong_edges, double *ms);
+/* Rows of a level after gmg_setup (levels below an aggregated one have no size before). */
+GMG_API int gmg_get_level_size(gmg_handle_t h, int lev, int64_t *n);
+
 /* ---- smoothers ------------------------------------------------------------- */
 /* RichardsonSmoother(JacobiLinearSolver(),niter,omega): RichardsonSmoothers.jl:84-98,
  * JacobiLinearSolvers.jl:20-23,43-47. */
