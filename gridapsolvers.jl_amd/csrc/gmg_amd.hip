@@ -232,9 +232,6 @@ struct PatStream {
 // device containers
 // ----------------------------------------------------------------------------
 struct DevCSR {
-  mutable Z2Geo z2;                 // fused pair of sweeps (sells_z2sweep_kernel): geometry, valid when z2_ok > 0
-  mutable Z2Geo zbx;                // single sweep of a constant-coefficient box (sells_boxsweep_kernel): the same grid, its own chains
-  mutable int z2_ok = -1;           // -1 not examined yet, 0 no, 1 yes
   mutable bool xnext_used = false;  // the last per-sweep pass of this operator ran the x-from-the-next-residual schedule (byte counts)
   int64_t nrows = 0, ncols = 0, nnz = 0;
   bool ptr64 = false;
@@ -288,8 +285,8 @@ struct DevCSR {
   uint8_t *pcodes = nullptr;
   double *pdict = nullptr;
   uint32_t *prunmask = nullptr;
+  mutable std::vector<int32_t> h_run_off;   // host copy of prun (z-walk geometry), fetched on first use
   // per-workgroup value tables of the coded form (sells_kernel<..., WL>): pattern lists of the launch geometry they were built for
-  mutable std::vector<int32_t> h_run_off;   // host copy of prun (tile sweep geometry), fetched on first use
   mutable int wl_state = 0;     // 0 not looked at, 1 in use, 2 not applicable (too many patterns in one chunk / switched off)
   mutable int wl_req = 0, wl_nwg = 0, wl_wpb = 0, wl_max = 0;   // requested / launched workgroups
   mutable uint16_t *wl_pids = nullptr;
@@ -858,8 +855,7 @@ struct gmg_solver {
   int pat_emit = 1;     // GMG_PAT_EMIT: restriction / r -= A dx kernels also write the next smoothing pass' s_0
   int64_t pat_coded_min_rows = 500000;   // GMG_PAT_CODED_MIN_ROWS
   int gj_mfma = 1;      // GMG_GJ_MFMA: trailing update of the device coarse inversion on the FP64 matrix cores
-  int pat_tile = 0;     // GMG_PAT_TILE: r-gather sweeps share their gathers through LDS (sells_tsweep_kernel): 0 never (default since the 64-register pair sweep beats it), 1 on levels of >= GMG_PAT_TILE_ROWS rows, 2 wherever it applies
-  int64_t pat_tile_rows = 3500000;   // "big" row-pattern levels: pair sweep / mat-vecs at one slice per wave in eight-wave workgroups (and the tile sweep with pat_tile = 1)
+  int64_t pat_tile_rows = 3500000;   // GMG_PAT_TILE_ROWS: the size from which the pair sweep (and the pair mat-vec) takes its eight-wave form, one slice per wave (the name is older than that form)
   int pat_wide = 1;     // GMG_PAT_WIDE: coded (wide-row) operators decode the patterns of each workgroup's chunk into a plain LDS value table
   int pat_strict = 1;   // GMG_PAT_STRICT: fused sweeps keep the per-entry mask (exact zero products even for non-finite vectors); 0 = 8-byte table entries, 2-3 % faster
   int persist_wpb_min = 1;   // GMG_PERSIST_WPB: smallest workgroup (in waves) of a one-launch pass
@@ -871,29 +867,12 @@ struct gmg_solver {
   int n_cus = 0;
   uint32_t *d_perr_dev = nullptr;                  // device-memory twin (the kernel's end-of-pass check)
   uint32_t *h_perr = nullptr, *d_perr = nullptr;   // pinned + mapped: a bounded wait of the persistent kernel timed out
-  int pat_bcast = 1;    // GMG_PAT_BCAST: tile sweep: slices whose DPP rows are single-pattern take their coefficients by row broadcast (no LDS read per tap)
   int pat_r2 = 1;       // GMG_PAT_R2: r-gather sweeps with two rows per lane (sells_r2sweep_kernel)
   int pat_zwalk = 1;    // GMG_PAT_ZWALK: the pair sweep as a walk along the slowest grid direction (kernels.hpp: sells_zsweep_kernel); 1: levels of >= pat_zwalk_rows rows, 2: every level
   int64_t pat_zwalk_wide_rows = 1000000;   // GMG_PAT_ZWALK_WIDE_ROWS: smallest wide-row level that takes the walk -- it wins wherever there are enough chains (it removes gathers,
                                            // not bytes): Q2 64^3 (2.05e6 rows) 18.6 -> 16.0 ms per solve, 96^3 (7.0e6) 40.3 -> 30.0, 128^3 89 -> 70
   int pat_zwalk_wide = 1; // GMG_PAT_ZWALK_WIDE: the wide-row (Q2) operator applications of those levels (sellw_zwalk_kernel)
   int pat_zwalk_mv = 1; // GMG_PAT_ZWALK_MV: also the operator mat-vecs of those levels
-  // GMG_PAT_FUSE2 (opt-in): two sweeps per pass over the data (kernels.hpp: sells_z2sweep_kernel) on grid levels of one GPU: 1 = levels of >=
-  // pat_fuse2_rows rows, 2 = every level that qualifies, 0 = off (default).  Bit-identical to the single sweeps and 32 instead of 56 bytes
-  // per row and pair -- but measured SLOWER on MI355X (profiles/r06_ab_fuse2.txt): 128^3 21.9 against 18.5 us per sweep, 288^3 185 against
-  // 156: the rim rows (W / (W - 2) x (T + 2) / T more sweep-k rows), 77 % lane use on 287-row lines and one workgroup barrier per plane
-  // cost more issue slots than the saved bytes buy; the single sweeps already run at their memory bound at 288^3.
-  // pat_fuse2_w = waves (grid lines) per workgroup, pat_fuse2_t = planes per block (0: chosen from the level's size); pat_fuse2_box = 0
-  // keeps the per-row patterns in LDS even on constant-coefficient boxes (the BC form reads one coefficient set per wave from the arguments)
-  int pat_fuse2 = 0, pat_fuse2_w = 0, pat_fuse2_t = 0;
-  // GMG_PAT_BOX (opt-in): constant-coefficient box levels (verified row by row at setup) sweep with one coefficient set per wave from the kernel
-  // arguments -- no pattern ids, no LDS (kernels.hpp: sells_boxsweep_kernel): 1 = levels of pat_box_min_rows .. pat_box_max_rows rows, 2 = every
-  // level that qualifies, 0 = off (default).  Measured on MI355X (profiles/r06_ab_box.txt): 128^3 20.1-21.0 us per sweep against 18.8 for
-  // sells_r2sweep_kernel, 288^3 208 against 165 for sells_zsweep_kernel -- the per-row LDS coefficient reads it removes are not what bounds the
-  // single sweeps.  pat_box_t = planes per chain (0: from the level's size)
-  int pat_box = 0, pat_box_t = 0;
-  int64_t pat_box_min_rows = 1000000, pat_box_max_rows = 9000000;
-  int64_t pat_fuse2_rows = 1000000;
   int pat_zwalk_T = 12; // GMG_PAT_ZWALK_T: planes per chain (288^3: 8 / 12 / 16 / 24 / 32 -> 149 / 114 / 120 / 118 / 155 us for the x-untouched form)
   int64_t pat_zwalk_rows = 9000000;   // the walk pays once r, r', x and the pattern ids (26 B per row) no longer fit the 256 MB Infinity Cache: 224^3 (1.09e7 rows) 8.13 -> 7.59 ms per solve,
                                       // 192^3 (7.0e6) 4.89 -> 5.23-5.50 with every chain length (profiles/r05_sizes.txt)
@@ -925,6 +904,7 @@ struct gmg_solver {
   bool prof_patch = false;      // the timed launches were `r -= A dx` mat-vecs of a patch-smoother sweep, not fused Jacobi sweeps
   std::vector<int> prof_w;     // sweeps bracketed by each event pair (1, or niter for a pass run as one launch)
   std::vector<int8_t> prof_xm; // variant (xmode 0 / 1 / 2) of the sweep each event pair brackets
+  std::vector<uint8_t> prof_pass;   // 1: the event pair brackets a pass run as one launch (set by smooth_persistent, cleared when the sample is read)
   double prof_ms_v[3] = {0, 0, 0}; int64_t prof_n_v[3] = {0, 0, 0};
 
   // ---- memory -------------------------------------------------------------
@@ -2286,76 +2266,6 @@ struct gmg_solver {
     const int nu = M.pat_k * M.pat_nruns;
     return (size_t)M.pat_np * nu * 16 + (size_t)M.pat_np * 8 + 16 <= 64 * 1024;
   }
-  // the tile form of that sweep (kernels.hpp: sells_tsweep_kernel): segments of r a tile of T slices needs, merged over the runs
-  bool launch_tsweep(const DevCSR &M, const SellSArgs &a, int nsl)
-  {
-    constexpr int WPB = 16, ROWS = 62, TMAX = 3 * WPB;
-    if (M.pat_nruns > 32 || nsl < opt_int("GMG_PAT_TILE_MIN", 512)) return false;
-    std::vector<int32_t> &off = M.h_run_off;
-    if (off.empty()) {
-      off.resize((size_t)M.pat_nruns);
-      HIP_CHECK(hipMemcpyAsync(off.data(), M.prun, sizeof(int32_t) * (size_t)M.pat_nruns, hipMemcpyDeviceToHost, stream));
-      HIP_CHECK(hipStreamSynchronize(stream));
-    }
-    const bool mk = pat_strict || !M.ptab8;
-    const int nu = M.pat_k * M.pat_nruns;
-    const size_t lds_cap = (size_t)opt_int("GMG_PAT_TILE_LDS", 78 * 1024);      // two workgroups of 16 waves per CU
-    std::vector<int> order((size_t)M.pat_nruns);
-    for (int r = 0; r < M.pat_nruns; ++r) order[(size_t)r] = r;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return off[(size_t)x] < off[(size_t)y]; });
-    // segments of r a tile of T slices needs: the runs' stretches [off, off + 62 T + 2), merged where they overlap or touch
-    auto geometry = [&](int T, SellTile &tl) -> size_t {
-      std::memset(&tl, 0, sizeof(tl));
-      tl.T = T;
-      const int RT = ROWS * T;
-      int nseg = 0;
-      int64_t elems = 0;
-      for (int k = 0; k < M.pat_nruns; ++k) {
-        const int r = order[(size_t)k];
-        const int64_t lo = off[(size_t)r], hi = (int64_t)off[(size_t)r] + RT + 2;
-        if (nseg > 0 && lo <= (int64_t)tl.seg_off[nseg - 1] + tl.seg_len[nseg - 1])
-          tl.seg_len[nseg - 1] = (int)std::max<int64_t>(tl.seg_len[nseg - 1], hi - tl.seg_off[nseg - 1]);
-        else {
-          if (nseg == 12) return 0;
-          tl.seg_off[nseg] = (int)lo; tl.seg_len[nseg] = (int)(hi - lo);
-          ++nseg;
-        }
-      }
-      for (int sg = 0; sg < nseg; ++sg) { tl.seg_base[sg] = (int)elems; elems += tl.seg_len[sg]; }
-      for (int r = 0; r < M.pat_nruns; ++r) {
-        int sg = 0;
-        while (!(off[(size_t)r] >= tl.seg_off[sg] && (int64_t)off[(size_t)r] + RT + 2 <= (int64_t)tl.seg_off[sg] + tl.seg_len[sg])) ++sg;
-        tl.run_lds[r] = tl.seg_base[sg] + (off[(size_t)r] - tl.seg_off[sg]);
-      }
-      tl.nseg = nseg; tl.elems = (int)elems;
-      return (size_t)M.pat_np * nu * (mk ? 16 : 8) + (size_t)elems * 8 + 16;
-    };
-    // the largest tile that fits the LDS budget, then the tile size that fills whole rounds of the resident workgroups
-    SellTile tl;
-    int tmax = opt_int("GMG_PAT_TILE_T", TMAX);
-    tmax = std::max(WPB, std::min(tmax, TMAX));
-    size_t lds = 0;
-    for (; tmax >= WPB; --tmax) { lds = geometry(tmax, tl); if (lds != 0 && lds <= lds_cap) break; }
-    if (tmax < WPB) return false;
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(2, (size_t)(160 * 1024) / (lds + 512)));
-    const int resident = per_cu * 256;
-    const int rounds = (nsl + resident * tmax - 1) / (resident * tmax);
-    const int T = std::max(WPB, (nsl + rounds * resident - 1) / (rounds * resident));
-    lds = geometry(T, tl);
-    if (lds == 0 || lds > lds_cap) return false;
-    const int ntiles = (nsl + T - 1) / T;
-    const int nwg = std::max(8, (std::min(ntiles, resident) / 8) * 8);          // a multiple of 8: one share per XCD
-    const dim3 g(nwg), b(64 * WPB);
-    // coefficients broadcast inside DPP rows (27-point operators), in the sweeps that leave x alone: 190.7 -> 184.8 us at 288^3; the sweeps
-    // that also update x have no registers to spare under the 64 the two resident workgroups allow (252.8 -> 282 us with it)
-    const bool bc = pat_bcast && M.pat_nruns == 9 && M.pat_k == 3 && a.xmode == 1;
-    M.note_sweep("sells_tsweep_kernel<XM=*,MK=%d,WPB=%d,FM=%d,BC=%d> T=%d tiles=%d wgs=%d segs=%d", mk ? 1 : 0, WPB, pat_fma ? 1 : 0, bc ? 1 : 0, T, ntiles, nwg, tl.nseg);
-    with_value<0, 1, 2>(a.xmode, [&](auto XM) { with_bools([&](auto MK, auto FM, auto BC) {
-      allow_lds<&sells_tsweep_kernel<XM(), MK(), WPB, FM(), BC()>>(96 * 1024);
-      hipLaunchKernelGGL((sells_tsweep_kernel<XM(), MK(), WPB, FM(), BC()>), g, b, lds, stream, a, tl); }, mk, pat_fma != 0, bc); });
-    HIP_CHECK(hipGetLastError());
-    return true;
-  }
   const std::vector<int32_t> &host_run_off(const DevCSR &M)
   {
     std::vector<int32_t> &off = M.h_run_off;
@@ -2385,153 +2295,19 @@ struct gmg_solver {
     g.nchains = (int)nch;
     return true;
   }
-  // geometry of the fused pair of sweeps (kernels.hpp: sells_z2sweep_kernel): the nine runs are the 3 x 3 neighbours (dz, dy) of a grid
-  // whose rows are numbered z P + y L + x, every plane has whole lines and the level whole planes
-  bool z2_geo(const DevCSR &M, Z2Geo &g)
-  {
-    if (M.pat_nruns != 9 || M.pat_k != 3 || !M.ptab) return false;
-    const std::vector<int32_t> &off = host_run_off(M);
-    const int64_t P = (int64_t)off[3] - off[0], L = (int64_t)off[1] - off[0];
-    if (L < 8 || P < 2 * L || P % L != 0 || M.nrows % P != 0 || M.nrows != M.ncols) return false;
-    for (int q = 0; q < 9; ++q) if ((int64_t)off[(size_t)q] != (int64_t)(q / 3 - 1) * P + (int64_t)(q % 3 - 1) * L - 1) return false;
-    g.P = (int)P; g.L = (int)L; g.ny = (int)(P / L); g.nz = (int)(M.nrows / P);
-    if (g.nz < 3 || g.ny < 3) return false;
-    g.whole = L <= 127 ? 1 : 0;
-    g.nxs = g.whole ? 1 : (int)((L + 123) / 124);
-    g.xlen = g.whole ? (int)L : (int)((L + g.nxs - 1) / g.nxs);
-    // W lines per workgroup (two of them rim lines), T planes per block: enough workgroups for two rounds of the chip, as little redundancy as that allows
-    int W = pat_fuse2_w > 0 ? pat_fuse2_w : (M.nrows >= 8000000 ? 16 : 8);
-    W = std::max(3, std::min(16, std::min(W, g.ny + 2)));
-    g.W = W;
-    g.nyt = (g.ny + W - 3) / (W - 2);
-    int T = pat_fuse2_t;
-    if (T <= 0) {
-      const int64_t per_plane_block = (int64_t)g.nyt * g.nxs;
-      const int64_t want = 2 * (int64_t)n_cus;
-      T = (int)std::max<int64_t>(4, std::min<int64_t>(16, (int64_t)g.nz * per_plane_block / std::max<int64_t>(1, want)));
-    }
-    g.T = std::max(1, std::min(T, g.nz));
-    g.nzb = (g.nz + g.T - 1) / g.T;
-    if ((((size_t)M.pat_np * 28 + 1) & ~(size_t)1) * 8 + (size_t)4 * g.W * kZ2Slot * 8 > (size_t)150 * 1024) return false;   // table + ring in one CU's LDS
-    if ((int64_t)g.nzb * g.nyt * g.nxs >= (int64_t)(1 << 30)) return false;
-    // constant-coefficient box?  The nine (plane class, line class) patterns from nine rows in the middle of their lines, then every
-    // row checked against them on the device (kernels.hpp: z2_box_check_kernel)
-    g.box = 0;
-    std::memset(g.coef, 0, sizeof(g.coef)); std::memset(g.cmask, 0, sizeof(g.cmask));
-    if (opt_int("GMG_PAT_FUSE2_BOX", 1) && g.L >= 3) {
-      std::vector<PatEntry> tab((size_t)M.pat_np * 27);
-      HIP_CHECK(hipMemcpyAsync(tab.data(), M.ptab, tab.size() * sizeof(PatEntry), hipMemcpyDeviceToHost, stream));
-      uint16_t pid[9];
-      const int zc[3] = {0, g.nz / 2, g.nz - 1}, yc[3] = {0, g.ny / 2, g.ny - 1};
-      for (int c = 0; c < 9; ++c) {
-        const int64_t row = (int64_t)zc[c / 3] * g.P + (int64_t)yc[c % 3] * g.L + g.L / 2;
-        HIP_CHECK(hipMemcpyAsync(&pid[c], M.rowpid + row, sizeof(uint16_t), hipMemcpyDeviceToHost, stream));
-      }
-      HIP_CHECK(hipStreamSynchronize(stream));
-      std::vector<double> hc(9 * 27);
-      std::vector<uint32_t> hm(9 * 27);
-      for (int c = 0; c < 9; ++c)
-        for (int j = 0; j < 27; ++j) {
-          const PatEntry &e = tab[(size_t)pid[c] * 27 + j];
-          g.coef[c][j] = e.v; g.cmask[c][j] = e.m; hc[(size_t)c * 27 + j] = e.v; hm[(size_t)c * 27 + j] = e.m;
-        }
-      double *d_c = nullptr; uint32_t *d_m = nullptr; int *d_bad = nullptr;
-      HIP_CHECK(hipMalloc((void **)&d_c, hc.size() * sizeof(double)));
-      HIP_CHECK(hipMalloc((void **)&d_m, hm.size() * sizeof(uint32_t)));
-      HIP_CHECK(hipMalloc((void **)&d_bad, sizeof(int)));
-      int bad = 0;
-      hipError_t e1 = hipMemcpyAsync(d_c, hc.data(), hc.size() * sizeof(double), hipMemcpyHostToDevice, stream);
-      hipError_t e2 = hipMemcpyAsync(d_m, hm.data(), hm.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
-      hipError_t e3 = hipMemsetAsync(d_bad, 0, sizeof(int), stream);
-      if (e1 == hipSuccess && e2 == hipSuccess && e3 == hipSuccess) {
-        hipLaunchKernelGGL(z2_box_check_kernel, dim3((unsigned)std::min<int64_t>(4096, (M.nrows + 255) / 256)), dim3(256), 0, stream, M.nrows, g.L, g.ny, g.nz, g.P,
-                           M.rowpid, M.ptab, d_c, d_m, d_bad);
-        e1 = hipGetLastError();
-        if (e1 == hipSuccess) e1 = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, stream);
-        if (e1 == hipSuccess) e1 = hipStreamSynchronize(stream);
-      }
-      (void)hipFree(d_c); (void)hipFree(d_m); (void)hipFree(d_bad);
-      HIP_CHECK(e1); HIP_CHECK(e2); HIP_CHECK(e3);
-      g.box = bad == 0 ? 1 : 0;
-    }
-    return true;
-  }
-  bool fuse2_level(const Level &L) const
-  {
-    return pat_fuse2 && pat_defer && comm.nranks == 1 && rsweep_level(L) && (pat_fuse2 >= 2 || L.A.nrows >= pat_fuse2_rows) && L.A.z2_ok > 0;
-  }
-  // sweeps k and k + 1 of a pass in one launch: r_k -> r_{k+2}, x += s_k + s_{k+1}
-  void launch_z2sweep(const DevCSR &M, const double *r_cur, double *r_next, double *x, bool x_zero, double omega)
-  {
-    SellSArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.rowpid = M.rowpid; a.tab = M.ptab; a.tab8 = M.ptab8; a.run_off = M.prun; a.np = M.pat_np; a.nruns = M.pat_nruns;
-    a.minoff = M.pat_minoff; a.maxoff = M.pat_maxoff; a.xmode = 2; a.pdinv = M.pdinv;
-    a.nrows = M.nrows; a.ncols = M.ncols; a.xcd_remap = xcd_remap;
-    a.x_zero = x_zero ? 1 : 0; a.x = r_cur; a.omega = omega; a.y = r_next; a.b = r_cur; a.x2 = x;
-    const Z2Geo &g = M.z2;
-    const bool mk = pat_strict || !M.ptab8;
-    const bool bc = g.box != 0;
-    const size_t lds = (bc ? 0 : (((size_t)M.pat_np * 28 + 1) & ~(size_t)1) * 8) + (size_t)4 * g.W * kZ2Slot * 8;
-    const dim3 gr((unsigned)(g.nzb * g.nyt * g.nxs)), b(64 * g.W);
-    M.note_sweep("sells_z2sweep_kernel<MK=%d,FM=%d,BC=%d> (two sweeps per launch) wgs=%u W=%d T=%d tiles=%dx%dx%d L=%d", mk ? 1 : 0, pat_fma ? 1 : 0, bc ? 1 : 0, gr.x, g.W, g.T, g.nxs, g.nyt, g.nzb, g.L);
-    REQUIRE(lds <= (size_t)150 * 1024, GMG_ERR_UNSUPPORTED, "sells_z2sweep_kernel: pattern table + ring exceed the LDS of a CU");
-    with_bools([&](auto BC, auto MK, auto FM) {
-      allow_lds<&sells_z2sweep_kernel<MK(), FM(), BC()>>(150 * 1024);
-      hipLaunchKernelGGL((sells_z2sweep_kernel<MK(), FM(), BC()>), gr, b, lds, stream, a, g); }, bc, mk, pat_fma != 0);
-    HIP_CHECK(hipGetLastError());
-  }
-  void ensure_z2(const DevCSR &M)
-  {
-    if (M.z2_ok >= 0) return;
-    M.z2_ok = z2_geo(M, M.z2) ? 1 : 0;
-    if (M.z2_ok > 0) {
-      // the single box sweep walks the same grid with chains of its own: segments of <= 126 rows, enough chains for ~4 waves per SIMD
-      Z2Geo &b = M.zbx;
-      b = M.z2;
-      b.nxs = b.whole ? 1 : (b.L + 125) / 126;
-      b.xlen = b.whole ? b.L : (b.L + b.nxs - 1) / b.nxs;
-      int T = pat_box_t;
-      if (T <= 0) T = (int)std::max<int64_t>(2, std::min<int64_t>(12, (int64_t)b.nz * b.ny * b.nxs / std::max(1, 16 * n_cus)));
-      b.T = std::max(1, std::min(T, b.nz));
-      b.nzb = (b.nz + b.T - 1) / b.T;
-    }
-  }
-  // (what box_level decided, for the byte counts: valid once a sweep of the level has been launched)
-  bool box_active(const DevCSR &M) const
-  {
-    return pat_box && pat_r2 && (pat_box >= 2 || (M.nrows >= pat_box_min_rows && M.nrows <= pat_box_max_rows)) && M.z2_ok > 0 && M.z2.box != 0;
-  }
-  bool box_level(const DevCSR &M)
-  {
-    if (!pat_box || !pat_r2) return false;
-    if (pat_box < 2 && (M.nrows < pat_box_min_rows || M.nrows > pat_box_max_rows)) return false;
-    ensure_z2(M);
-    return M.z2_ok > 0 && M.z2.box != 0;
-  }
   int sells_wpb(int nsl) const { return sell_block > 0 ? sell_block / 64 : (nsl >= 256 * 32 ? 4 : pat_small_wpb); }
-  // The form of the r-gather sweep of an operator -- the ONE place that decides it, in this order: tile (by option and size; the tile
-  // sweep may still decline), constant-coefficient box, z-walk (fills zg), pair sweep at one slice per wave or at resident workgroups,
-  // single-row sweep.  `from`: where the decisions start -- what follows a tile sweep that declined, or an x mode that tile and box lack.
-  enum class RSweepForm { Tile, Box, ZWalk, Pair8, Pair, Row };
-  RSweepForm rsweep_form(const DevCSR &M, ZWalkGeo &zg, RSweepForm from = RSweepForm::Tile)
+  // The form of the r-gather sweep of an operator -- the ONE place that decides it, in this order: z-walk (fills zg), pair sweep at one
+  // slice per wave or at resident workgroups, single-row sweep.  launch_rsweep() switches on the answer, and smooth() takes x from the
+  // next residual where it is not the single-row sweep (the only form without x mode 3).
+  enum class RSweepForm { ZWalk, Pair8, Pair, Row };
+  RSweepForm rsweep_form(const DevCSR &M, ZWalkGeo &zg)
   {
-    if (from == RSweepForm::Tile && (pat_tile >= 2 || (pat_tile == 1 && M.nrows >= pat_tile_rows))) return RSweepForm::Tile;
-    if (from <= RSweepForm::Box && box_level(M)) return RSweepForm::Box;
     if (pat_r2 && pat_zwalk && (pat_zwalk >= 2 || M.nrows >= pat_zwalk_rows) && zwalk_geo(M, zg)) return RSweepForm::ZWalk;
     if (!(pat_r2 && (M.pat_nruns == 9 || M.pat_nruns == 3))) return RSweepForm::Row;
     // one slice per wave: workgroups of eight waves stage the coefficient table once per eight slices (pat_r2_occ = 2)
     const int rows = 65 - M.pat_k;
     const bool occ8 = pat_r2_occ >= 2 && sells_wpb((int)((M.nrows + rows - 1) / rows)) == 4 && M.pat_nruns == 9 && M.nrows >= pat_tile_rows && pat_r2_wgs <= 0;
     return occ8 ? RSweepForm::Pair8 : RSweepForm::Pair;
-  }
-  // Does launch_rsweep() end in a kernel that has x mode 3 (x = (x + s_k) + s_{k+1}, the latter from the row's own r_{k+1} in
-  // registers) for this operator?  Only the z-walk and the pair sweep have it.  (Tile by option: no, whether or not the tile sweep then applies.)
-  bool xnext_kernel(const DevCSR &M)
-  {
-    ZWalkGeo zg;
-    const RSweepForm form = rsweep_form(M, zg);
-    return form == RSweepForm::ZWalk || form == RSweepForm::Pair8 || form == RSweepForm::Pair;
   }
   void launch_rsweep(const DevCSR &M, const double *r_cur, double *r_next, const double *r_prev, double *x, bool x_zero, double omega, int xmode)
   {
@@ -2544,29 +2320,13 @@ struct gmg_solver {
     a.nrows = M.nrows; a.ncols = M.ncols; a.nslices = nsl; a.xcd_remap = xcd_remap;
     a.x_zero = x_zero ? 1 : 0; a.x = r_cur; a.omega = omega; a.y = r_next; a.b = r_cur; a.x2 = x; a.s_out = const_cast<double *>(r_prev);
     ZWalkGeo zg;
-    // (xmode 3 is only asked for where xnext_kernel() has ruled the tile and the box out: the decisions then start after them)
-    RSweepForm form = rsweep_form(M, zg, xmode == 3 ? RSweepForm::ZWalk : RSweepForm::Tile);
-    if (form == RSweepForm::Tile) {
-      if (launch_tsweep(M, a, nsl)) return;
-      form = rsweep_form(M, zg, RSweepForm::Box);
-    }
+    const RSweepForm form = rsweep_form(M, zg);
     const int wpb = sells_wpb(nsl);
     const int nu = M.pat_k * M.pat_nruns;
     const dim3 b(64 * wpb);
     const size_t lds2 = (size_t)M.pat_np * nu * 16 + 16;
     const bool mk = pat_strict || !M.ptab8, fm = pat_fma != 0;
     switch (form) {
-    case RSweepForm::Tile: break;                            // (not reached)
-    case RSweepForm::Box: {
-      // constant-coefficient box: one coefficient set per wave from the kernel arguments, no pattern ids, no LDS
-      const Z2Geo &gb = M.zbx;
-      const int nch = gb.nzb * gb.ny * gb.nxs;
-      const dim3 gx((unsigned)((nch + 3) / 4)), bx(256);
-      M.note_sweep("sells_boxsweep_kernel<XM=*,MK=%d,FM=%d> chains=%d T=%d segs=%d L=%d", mk ? 1 : 0, pat_fma ? 1 : 0, nch, gb.T, gb.nxs, gb.L);
-      with_value<0, 1, 2>(xmode, [&](auto XM) { with_bools([&](auto MK, auto FM) {
-        hipLaunchKernelGGL((sells_boxsweep_kernel<XM(), MK(), FM()>), gx, bx, 0, stream, a, gb); }, mk, fm); });
-      break;
-    }
     case RSweepForm::ZWalk: {
       // the pair sweep as a walk along the slowest grid direction: three new windows per step instead of nine, one step of requests in flight
       const int wz = 4;
@@ -2606,7 +2366,7 @@ struct gmg_solver {
       break;
     }
     case RSweepForm::Row: {
-      REQUIRE(xmode != 3, GMG_ERR_STATE, "sells_rsweep_kernel has no x mode 3 (xnext_kernel() and launch_rsweep() disagree)");
+      REQUIRE(xmode != 3, GMG_ERR_STATE, "sells_rsweep_kernel has no x mode 3");
       const int nb = pat_nb > 0 ? pat_nb : (nsl >= 200000 ? 2 : 1);
       const int wg2 = std::max(1, std::min((nsl + wpb - 1) / wpb, nb >= 2 && pat_wgs == 2048 ? 1024 : pat_wgs));
       const dim3 g2(wg2);
@@ -3268,6 +3028,7 @@ struct gmg_solver {
       HIP_CHECK(hipEventRecord(prof_ev[prof_used + 1], stream));
       prof_w[prof_used / 2] = niter - a.close;
       prof_xm[prof_used / 2] = 0;
+      prof_pass[prof_used / 2] = 1;
       prof_used += 2;
     }
     return true;
@@ -3431,34 +3192,18 @@ struct gmg_solver {
             copy(L.rbuf[0], cur, n);                           // the exchange writes the ghost entries of r_k: never into a caller's vector
             cur = L.rbuf[0];
           }
-          if (pat_fuse2) ensure_z2(L.A);
-          const bool fuse2 = fuse2_level(L);
           // x from the NEXT residual: sweep k holds its rows' r_{k+1} in registers, so the pair's two increments can both be added
           // there -- x = (x + s_k) + s_{k+1} in sweeps 0, 2, ..., the same sums in the same order as x = (x + s_{k-1}) + s_k one sweep
           // later, without reading r_{k-1} back.  Needs an even number of sweeps and a level without halo (ghost_fix_* corrects the
-          // boundary rows of r_next AFTER the sweep: what the sweep had in registers was not r_{k+1} there).
-          const bool xnext = pat_xnext && !fuse2 && (nb & 1) == 0 && comm.nranks == 1 && xnext_kernel(L.A);
+          // boundary rows of r_next AFTER the sweep: what the sweep had in registers was not r_{k+1} there).  The z-walk and the pair
+          // sweep have that x mode (3), the single-row sweep does not.
+          ZWalkGeo zg;
+          const bool xnext = pat_xnext && (nb & 1) == 0 && comm.nranks == 1 && rsweep_form(L.A, zg) != RSweepForm::Row;
           L.A.xnext_used = xnext;
           // ... and then x is complete after sweep nb - 2: where r is dead, sweep nb - 1 (x untouched) has nothing left to do
           const int nsw = (xnext && r_dead) ? nb - 1 : nb;
           for (int it = 0; it < nsw; ++it) {
             double *next = (cur == L.rbuf[0]) ? L.rbuf[1] : L.rbuf[0];
-            if (fuse2 && (it & 1) == 0 && it + 1 < nb) {
-              // sweeps it (x untouched) and it + 1 (x += both increments) in ONE launch: r_k -> r_{k+2}, r_{k+1} never leaves the CUs
-              const bool prof = (l == prof_level) && (prof_seq++ % (uint64_t)prof_stride == 0) && prof_used + 2 <= prof_ev.size();
-              if (prof) HIP_CHECK(hipEventRecord(prof_ev[prof_used], stream));
-              launch_z2sweep(L.A, cur, next, x, xz0 && it == 0, S.omega);
-              if (prof) {
-                HIP_CHECK(hipEventRecord(prof_ev[prof_used + 1], stream));
-                prof_w[prof_used / 2] = 2;
-                prof_xm[prof_used / 2] = 2;
-                prof_used += 2;
-              }
-              prev = nullptr;
-              cur = next;
-              ++it;
-              continue;
-            }
             int xmode = 0;
             bool xz = xz0 && it == 0;
             if (xnext) xmode = (it & 1) ? 1 : 3;
@@ -4202,7 +3947,6 @@ struct gmg_solver {
       HIP_CHECK(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device));
       n_cus = std::max(1, v);
     }
-    pat_bcast = opt_int("GMG_PAT_BCAST", 1);
     red_fused = opt_int("GMG_RED_FUSED", 1);
     pat_r2 = opt_int("GMG_PAT_R2", 1);
     pat_r2_wgs = opt_int("GMG_PAT_R2_WGS", 0);
@@ -4213,14 +3957,6 @@ struct gmg_solver {
     pat_zwalk_wide = opt_int("GMG_PAT_ZWALK_WIDE", 1);
     pat_zwalk_wide_rows = opt_int("GMG_PAT_ZWALK_WIDE_ROWS", 1000000);
     pat_zwalk_rows = opt_int("GMG_PAT_ZWALK_ROWS", 9000000);
-    pat_fuse2 = opt_int("GMG_PAT_FUSE2", 0);
-    pat_fuse2_w = opt_int("GMG_PAT_FUSE2_W", 0);
-    pat_fuse2_t = opt_int("GMG_PAT_FUSE2_T", 0);
-    pat_fuse2_rows = opt_int("GMG_PAT_FUSE2_ROWS", 1000000);
-    pat_box = opt_int("GMG_PAT_BOX", 0);
-    pat_box_t = opt_int("GMG_PAT_BOX_T", 0);
-    pat_box_min_rows = opt_int("GMG_PAT_BOX_MIN_ROWS", 1000000);
-    pat_box_max_rows = opt_int("GMG_PAT_BOX_MAX_ROWS", 9000000);
     persist_wpb_min = opt_int("GMG_PERSIST_WPB", 1);
     pat_r2mv = opt_int("GMG_PAT_R2MV", 1);
     pat_pair_p = opt_int("GMG_PAT_PAIR_P", 1);
@@ -4242,7 +3978,6 @@ struct gmg_solver {
     persist_fold = opt_int("GMG_PERSIST_FOLD", 7);
     pat_strict = opt_int("GMG_PAT_STRICT", 1);
     pat_wide = opt_int("GMG_PAT_WIDE", 1);
-    pat_tile = opt_int("GMG_PAT_TILE", 0);
     pat_tile_rows = opt_int("GMG_PAT_TILE_ROWS", 3500000);
     gj_mfma = opt_int("GMG_GJ_MFMA", 1);
     persist_max_slices = opt_int("GMG_PERSIST_MAX_SLICES", 0);
@@ -4310,8 +4045,6 @@ struct gmg_solver {
       if (pat_dinv && A.pdinv) vec -= 8.0 * N;             // 1/diag from the pattern table
       if (pat_defer) vec -= 4.0 * N;                       // x touched every second sweep: (8+8+8)/2 instead of 8+8
       if (pat_defer && rsweep_level(L)) vec = A.xnext_used ? 24.0 * N : 28.0 * N;   // r-gather sweeps: r in + r out, (x in + x out [+ r_prev: not with pat_xnext]) every second sweep; no s, no 1/diag
-      if (fuse2_level(L)) vec = 16.0 * N;                  // sells_z2sweep_kernel, per sweep of the pair: (r_k in + r_{k+2} out + x in + x out) / 2
-      if (box_active(A)) mat = 0.0;                        // sells_boxsweep_kernel: no pattern ids either -- the coefficients are kernel arguments
     } else if (A.pat) mat = (A.rowbase ? 6.0 : 2.0) * N;
     else if (A.sell && A.opat) { mat = (A.sval32 ? 4.0 : 8.0) * (double)A.zpad + (A.orowbase ? 6.0 : 2.0) * N + 4.0 * N + 8.0 * (double)A.nslices; if (sell_defer && sell_un < 27) vec -= 4.0 * N; }
     else if (A.sell && (A.comp_idx || A.vdict)) mat = A.stream_bytes_per_nnz * (double)A.zpack + 4.0 * N + 4.0 * (double)(A.zpack / 64);
@@ -4332,7 +4065,7 @@ struct gmg_solver {
                      : (A.sell && A.opat) ? (sell_defer && sell_un < 27)
                      : (A.sell && (A.comp_idx || A.vdict)) ? false
                      : (A.sell) ? (sell_defer && sell_un >= 6 && sell_un < 9) : false;
-    if (!defer || fuse2_level(L)) return mean;              // (a fused pair is one form: half of the pair's bytes per sweep)
+    if (!defer) return mean;
     if (A.xnext_used && rsweep_level(L)) return mean - 8.0 * N + (xmode == 1 ? 0.0 : 16.0 * N);   // x in + x out on every second sweep, no r_prev
     return mean - 12.0 * N + (xmode == 1 ? 0.0 : xmode == 2 ? 24.0 * N : 16.0 * N);
   }
@@ -6709,17 +6442,17 @@ const OptionKey kOptionKeys[] = {
   {"GMG_PATCH_OPERATOR", false}, {"GMG_PATCH_OP_DEVICE", false}, {"GMG_PATCH_SOURCE_DEDUP", false}, {"GMG_PATTERN", false}, {"GMG_PAT_BATCHED", false},
   {"GMG_PAT_CODED_MIN_ROWS", false}, {"GMG_PAT_DEFER", false}, {"GMG_PAT_DINV", false}, {"GMG_PAT_EMIT", false}, {"GMG_PAT_NB", false},
   {"GMG_PAT_RB", false}, {"GMG_PAT_RSWEEP", false}, {"GMG_PAT_SHARED", false}, {"GMG_PAT_SMALL_WPB", false}, {"GMG_PAT_SMALL_WPB2", false},
-  {"GMG_PAT_STRICT", false}, {"GMG_PAT_TILE", false}, {"GMG_PAT_TILE_LDS", false}, {"GMG_PAT_TILE_MIN", false}, {"GMG_PAT_TILE_ROWS", false},
-  {"GMG_PAT_TILE_T", false}, {"GMG_PAT_UN", false}, {"GMG_PAT_WGS", false}, {"GMG_PAT_WIDE", false}, {"GMG_PAT_WIDE_LDS", false},
+  {"GMG_PAT_STRICT", false}, {"GMG_PAT_TILE_ROWS", false},
+  {"GMG_PAT_UN", false}, {"GMG_PAT_WGS", false}, {"GMG_PAT_WIDE", false}, {"GMG_PAT_WIDE_LDS", false},
   {"GMG_PAT_WIDE_ROUNDS", false}, {"GMG_PERSIST", false}, {"GMG_PERSIST_FENCED", false}, {"GMG_PERSIST_FOLD", false}, {"GMG_PERSIST_MAX_SLICES", false}, {"GMG_PERSIST_REGS", false},
   {"GMG_PERSIST_SHARED", false}, {"GMG_PROF_STRIDE", true}, {"GMG_REFRESH", true}, {"GMG_SELL", false}, {"GMG_SELL_BLOCK", false},
   {"GMG_SELL_DEFER", false}, {"GMG_SELL_MAXPAD", false}, {"GMG_SELL_UN", false}, {"GMG_SETUP_TIMING", true}, {"GMG_VDICT", false},
-  {"GMG_XCD_REMAP", false}, {"GMG_XCD_REMAP_BIG", false}, {"GMG_X0_ZERO", true}, {"GMG_HOST_POLL", true}, {"GMG_HOST_CHUNK_BYTES", true}, {"GMG_PAT_FMA", false}, {"GMG_PAT_R2", false}, {"GMG_RED_FUSED", false}, {"GMG_GMRES_FUSED", true}, {"GMG_FGMRES_FUSED", true}, {"GMG_NULLSPACE_FUSED", true}, {"GMG_PAT_R2MV", false}, {"GMG_PAT_R2_OCC", false}, {"GMG_PAT_PAIR_P", false}, {"GMG_PAT_R2MV_DOT", false}, {"GMG_PERSIST_WPB", false}, {"GMG_HOST_TIMELINE", true}, {"GMG_PAT_R2MV_MIN", false}, {"GMG_PAT_BCAST", false}, {"GMG_PAT_R2_WGS", false}, {"GMG_PAT_ZWALK", false}, {"GMG_PAT_ZWALK_T", false}, {"GMG_PAT_ZWALK_ROWS", false}, {"GMG_PAT_ZWALK_MV", false}, {"GMG_PAT_ZWALK_WIDE", false}, {"GMG_PAT_ZWALK_WIDE_ROWS", false}, {"GMG_PAT_FUSE2", false}, {"GMG_PAT_FUSE2_W", false}, {"GMG_PAT_FUSE2_T", false}, {"GMG_PAT_FUSE2_ROWS", false}, {"GMG_PAT_FUSE2_BOX", false}, {"GMG_PAT_BOX", false}, {"GMG_PAT_WIDE_GRID", false}, {"GMG_PAT_BOX_T", false}, {"GMG_PAT_BOX_MIN_ROWS", false}, {"GMG_PAT_BOX_MAX_ROWS", false},
+  {"GMG_XCD_REMAP", false}, {"GMG_XCD_REMAP_BIG", false}, {"GMG_X0_ZERO", true}, {"GMG_HOST_POLL", true}, {"GMG_HOST_CHUNK_BYTES", true}, {"GMG_PAT_FMA", false}, {"GMG_PAT_R2", false}, {"GMG_RED_FUSED", false}, {"GMG_GMRES_FUSED", true}, {"GMG_FGMRES_FUSED", true}, {"GMG_NULLSPACE_FUSED", true}, {"GMG_PAT_R2MV", false}, {"GMG_PAT_R2_OCC", false}, {"GMG_PAT_PAIR_P", false}, {"GMG_PAT_R2MV_DOT", false}, {"GMG_PERSIST_WPB", false}, {"GMG_HOST_TIMELINE", true}, {"GMG_PAT_R2MV_MIN", false}, {"GMG_PAT_R2_WGS", false}, {"GMG_PAT_ZWALK", false}, {"GMG_PAT_ZWALK_T", false}, {"GMG_PAT_ZWALK_ROWS", false}, {"GMG_PAT_ZWALK_MV", false}, {"GMG_PAT_ZWALK_WIDE", false}, {"GMG_PAT_ZWALK_WIDE_ROWS", false}, {"GMG_PAT_WIDE_GRID", false},
   {"GMG_PERSIST_FORCE_TIMEOUT", true}, {"GMG_PAT_XNEXT", false}, {"GMG_PAT_CLOSE", false}, {"GMG_CG_SPLIT", true}, {"GMG_GS_WIDE", true}, {"GMG_GS_PACK_FUSED", true}, {"GMG_CHEB_PACK_FUSED", true},
   {"GMG_PMULT_ONE_LAUNCH", true}, {"GMG_PMULT_ONE_LAUNCH_MAX", true},
   {"GMG_VALUES_F32", false}, {"GMG_VALUES_F32_NT", false},
 };
-// "pat_tile", "PAT_TILE" and "GMG_PAT_TILE" name the same option
+// "pat_r2", "PAT_R2" and "GMG_PAT_R2" name the same option
 const OptionKey *find_option(const char *key)
 {
   if (!key) return nullptr;
@@ -7626,6 +7359,7 @@ int gmg_profile_enable(gmg_handle_t h, int lev, int enable)
       h->prof_xm.assign(8192, 0);
       for (auto &ev : h->prof_ev) HIP_CHECK(hipEventCreate(&ev));
     }
+    h->prof_pass.assign(8192, 0);
     h->prof_level = lev;
     h->prof_stride = std::max(1, h->opt_int("GMG_PROF_STRIDE", 7));   // live: a caller picks the sampling density per measurement
     h->prof_seq = 0;
@@ -7647,7 +7381,7 @@ int gmg_get_kernel_stats(gmg_handle_t h, gmg_kernel_stats *out)
       HIP_CHECK(hipEventElapsedTime(&ms, h->prof_ev[i], h->prof_ev[i + 1]));
       h->prof_ms += ms;
       h->prof_launches += h->prof_w[i / 2];
-      if (h->prof_w[i / 2] > 2 && h->prof_xm[i / 2] >= 0) h->prof_fused += 1;   // (a weight of 2 is a fused PAIR of sweeps, sells_z2sweep_kernel: not a one-launch pass; -1: the launches of a Gauss-Seidel direction)
+      if (h->prof_pass[i / 2]) { h->prof_fused += 1; h->prof_pass[i / 2] = 0; }
       const int v = std::min(2, std::max(0, (int)h->prof_xm[i / 2]));
       h->prof_ms_v[v] += ms; h->prof_n_v[v] += h->prof_w[i / 2];
     }

@@ -357,196 +357,6 @@ __global__ __launch_bounds__(kBlock) void sell_kernel(SellArgs a)
   }
 }
 
-// ---------------------------------------------------------------------------
-// sell_kernel with the matrix stream kept in flight.  A lane's work is a chain  (col,val) load -> gather x[col] -> multiply-add
-// per batch of UN entries: in sell_kernel the next batch's stream loads are only issued after the current gathers have been
-// consumed, so per batch a wave exposes L_stream + L_gather and carries stream bytes in flight for L_stream of it.  Once the
-// gathered vector leaves the L2s (levels >= 256^3: L_gather roughly doubles) that share drops and with it the achieved
-// bandwidth (0.78 -> 0.64 of peak; HBM traffic stays at the algorithmic bytes, so it is latency, not re-reads).  Here the
-// stream loads of batch k+PD are issued BEFORE the gathers of batch k are waited for (loads return in order, so the wait for
-// the gathers -- vmcnt(2*UN*PD) -- leaves the younger stream loads in flight).  Same products, same left-to-right order:
-// bit-identical to sell_kernel.  Column / value indices past the slice width are clamped to its last column (masked by rowlen).
-// ---------------------------------------------------------------------------
-template <int EPI, bool ONEG, int UN, int PD, bool NT>
-__global__ __launch_bounds__(kBlock) void sell_pipe_kernel(SellArgs a)
-{
-  const int lane = threadIdx.x & 63;
-  const int slice = __builtin_amdgcn_readfirstlane((int)(remap_block(blockIdx.x, gridDim.x, a.xcd_remap) * (blockDim.x >> 6) + (threadIdx.x >> 6)));
-  if (slice >= a.nslices) return;
-  const int64_t base = a.soff[slice];
-  const int w = (int)((a.soff[slice + 1] - base) >> 6);
-  const int64_t row = (int64_t)slice * 64 + lane;
-  const bool valid = row < a.nrows;
-  const int64_t rc = valid ? row : a.nrows - 1;
-  const double *__restrict__ xg = a.x;
-  const double *__restrict__ dinv = a.dinv;
-  const double omega = a.omega;
-  const int32_t *cp = a.scol + base + lane;
-  const double *vp = a.sval + base + lane;
-  const int wl = w - 1;
-  int32_t c[PD + 1][UN];
-  double v[PD + 1][UN];
-  auto issue = [&](int slot, int j0) {
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      const int64_t o = (int64_t)min(j0 + u, wl) * 64;
-      if (NT) { c[slot][u] = __builtin_nontemporal_load(cp + o); v[slot][u] = __builtin_nontemporal_load(vp + o); }
-      else { c[slot][u] = cp[o]; v[slot][u] = vp[o]; }
-    }
-  };
-  // the first PD batches of the stream, then the row-wise operands (clamped addresses: no divergent loads)
-#pragma unroll
-  for (int p = 0; p < PD; ++p) issue(p, p * UN);
-  int len = a.rowlen[rc];
-  if (!valid) len = 0;
-  double e0 = 0.0, e1 = 0.0, e2 = 0.0, dinv_row = 0.0;
-  if (EPI == EPI_SUB) e0 = a.y[rc];
-  else if (EPI == EPI_RESID) e0 = a.b[rc];
-  else if (EPI == EPI_ADDTO) e0 = a.x2[rc];
-  else if (EPI == EPI_SWEEP) {
-    e0 = a.b[rc];
-    e1 = ONEG ? xg[rc] : dinv[rc];
-    { const double xl = a.x2[rc]; e2 = a.x_zero ? 0.0 : xl; }
-    if (ONEG) dinv_row = dinv[rc];
-  }
-  double s = 0.0;
-  // steady state: the stream loads of batch j/UN + PD are issued unconditionally inside the loop body (a conditional issue makes
-  // the compiler wait at the join as if they had not been issued: vmcnt(UN-1) instead of vmcnt(2*UN*PD + UN-1)); drain loop after
-  auto batch = [&](int j, bool more) {
-    double g[UN];
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      if (EPI == EPI_SWEEP && !ONEG) g[u] = omega * (dinv[c[0][u]] * xg[c[0][u]]);
-      else g[u] = xg[c[0][u]];
-    }
-    if (more) issue(PD, j + PD * UN);                      // stays in flight across the gather wait below
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      const double pr = v[0][u] * g[u];
-      s = (j + u < len) ? s + pr : s;                      // masked: padding is never added
-    }
-#pragma unroll
-    for (int p = 0; p < PD; ++p) {
-#pragma unroll
-      for (int u = 0; u < UN; ++u) { c[p][u] = c[p + 1][u]; v[p][u] = v[p + 1][u]; }
-    }
-  };
-  int j = 0;
-  for (; j + PD * UN < w; j += UN) batch(j, true);
-  for (; j < w; j += UN) batch(j, false);
-  if (valid) {
-    if (EPI == EPI_SET) a.y[row] = s;
-    else if (EPI == EPI_SUB) a.y[row] = e0 - s;
-    else if (EPI == EPI_RESID) a.y[row] = e0 - s;
-    else if (EPI == EPI_ADDTO) { const double t = a.omega != 0.0 ? a.omega * s : s; a.y[row] = t; a.x2[row] = e0 + t; }
-    else {
-      const double dxi = ONEG ? e1 : omega * (e1 * e0);
-      a.x2[row] = e2 + dxi;
-      const double rn = e0 - s;
-      a.y[row] = rn;
-      if (ONEG) a.s_out[row] = omega * (dinv_row * rn);
-    }
-  }
-}
-
-// Whole rows in flight: slices of width <= WMAX request every (col,val) pair of the lane's row at once, then every gather,
-// then sum left to right -- one stream latency + one gather latency per slice instead of one pair per batch, at the price of
-// ~3*WMAX registers (4 waves per SIMD at WMAX = 27).  Wider slices take the batched loop.  Bit-identical to sell_kernel.
-template <int EPI, bool ONEG, int WMAX, bool NT>
-__global__ __launch_bounds__(kBlock) void sell_row_kernel(SellArgs a)
-{
-  const int lane = threadIdx.x & 63;
-  const int slice = __builtin_amdgcn_readfirstlane((int)(remap_block(blockIdx.x, gridDim.x, a.xcd_remap) * (blockDim.x >> 6) + (threadIdx.x >> 6)));
-  if (slice >= a.nslices) return;
-  const int64_t base = a.soff[slice];
-  const int w = (int)((a.soff[slice + 1] - base) >> 6);
-  const int64_t row = (int64_t)slice * 64 + lane;
-  const bool valid = row < a.nrows;
-  const int64_t rc = valid ? row : a.nrows - 1;
-  const double *__restrict__ xg = a.x;
-  const double *__restrict__ dinv = a.dinv;
-  const double omega = a.omega;
-  const int32_t *cp = a.scol + base + lane;
-  const double *vp = a.sval + base + lane;
-  double s = 0.0;
-  int len;
-  double e0 = 0.0, e1 = 0.0, e2 = 0.0, dinv_row = 0.0;
-  auto head = [&]() {
-    len = a.rowlen[rc];
-    if (!valid) len = 0;
-    if (EPI == EPI_SUB) e0 = a.y[rc];
-    else if (EPI == EPI_RESID) e0 = a.b[rc];
-    else if (EPI == EPI_ADDTO) e0 = a.x2[rc];
-    else if (EPI == EPI_SWEEP) {
-      e0 = a.b[rc];
-      e1 = ONEG ? xg[rc] : dinv[rc];
-      { const double xl = a.x2[rc]; e2 = a.x_zero ? 0.0 : xl; }
-      if (ONEG) dinv_row = dinv[rc];
-    }
-  };
-  if (w <= WMAX) {
-    const int wl = w - 1;
-    int32_t c[WMAX];
-    double v[WMAX], g[WMAX];
-#pragma unroll
-    for (int u = 0; u < WMAX; ++u) {
-      const int64_t o = (int64_t)min(u, wl) * 64;
-      c[u] = NT ? __builtin_nontemporal_load(cp + o) : cp[o];
-    }
-#pragma unroll
-    for (int u = 0; u < WMAX; ++u) {
-      const int64_t o = (int64_t)min(u, wl) * 64;
-      v[u] = NT ? __builtin_nontemporal_load(vp + o) : vp[o];
-    }
-    head();
-#pragma unroll
-    for (int u = 0; u < WMAX; ++u) {
-      if (EPI == EPI_SWEEP && !ONEG) g[u] = omega * (dinv[c[u]] * xg[c[u]]);
-      else g[u] = xg[c[u]];
-    }
-#pragma unroll
-    for (int u = 0; u < WMAX; ++u) {
-      const double pr = v[u] * g[u];
-      s = (u < len) ? s + pr : s;
-    }
-  } else {
-    head();
-    constexpr int UN = 9;
-    for (int j = 0; j < w; j += UN) {
-      int32_t c[UN];
-      double v[UN], g[UN];
-#pragma unroll
-      for (int u = 0; u < UN; ++u) {
-        const int64_t o = (int64_t)min(j + u, w - 1) * 64;
-        c[u] = cp[o]; v[u] = vp[o];
-      }
-#pragma unroll
-      for (int u = 0; u < UN; ++u) {
-        if (EPI == EPI_SWEEP && !ONEG) g[u] = omega * (dinv[c[u]] * xg[c[u]]);
-        else g[u] = xg[c[u]];
-      }
-#pragma unroll
-      for (int u = 0; u < UN; ++u) {
-        const double pr = v[u] * g[u];
-        s = (j + u < len) ? s + pr : s;
-      }
-    }
-  }
-  if (valid) {
-    if (EPI == EPI_SET) a.y[row] = s;
-    else if (EPI == EPI_SUB) a.y[row] = e0 - s;
-    else if (EPI == EPI_RESID) a.y[row] = e0 - s;
-    else if (EPI == EPI_ADDTO) { const double t = a.omega != 0.0 ? a.omega * s : s; a.y[row] = t; a.x2[row] = e0 + t; }
-    else {
-      const double dxi = ONEG ? e1 : omega * (e1 * e0);
-      a.x2[row] = e2 + dxi;
-      const double rn = e0 - s;
-      a.y[row] = rn;
-      if (ONEG) a.s_out[row] = omega * (dinv_row * rn);
-    }
-  }
-}
-
 // x[byte offset]: uniform base + 32-bit lane offset (the saddr + voffset form of global_load)
 __device__ __forceinline__ double ld_off(const double *__restrict__ base, uint32_t byteoff)
 {
@@ -668,109 +478,6 @@ __global__ __launch_bounds__(kBlock) void sello_kernel(SellOArgs a)
       const double xn = XM == 2 ? (e2 + sp) + dxi : e2 + dxi;
       if (NT >= 2) { if (XM != 1) __builtin_nontemporal_store(xn, a.x2 + row); __builtin_nontemporal_store(rn, a.y + row); }
       else { if (XM != 1) a.x2[row] = xn; a.y[row] = rn; }
-      if (ONEG) a.s_out[row] = omega * (dinv_row * rn);
-    }
-  }
-}
-
-// sello_kernel with the next batch (values AND gathers: the offsets come from LDS, nothing depends on the stream) requested
-// before the current batch is consumed -- see sell_pipe_kernel.  WMAX > 0: slices of width <= WMAX request their whole row.
-template <int EPI, bool ONEG, int UN, int WMAX, bool NT>
-__global__ __launch_bounds__(kBlock) void sello_pipe_kernel(SellOArgs a)
-{
-  extern __shared__ double sp_smem[];
-  int32_t *s_off = reinterpret_cast<int32_t *>(sp_smem);
-  const int tot = a.np * a.W;
-  for (int i = threadIdx.x; i < tot; i += blockDim.x) s_off[i] = a.poff[i];
-  const int lane = threadIdx.x & 63;
-  const int slice = __builtin_amdgcn_readfirstlane((int)(remap_block(blockIdx.x, gridDim.x, a.xcd_remap) * (blockDim.x >> 6) + (threadIdx.x >> 6)));
-  const bool live = slice < a.nslices;
-  const int sc = live ? slice : a.nslices - 1;
-  const int64_t base = a.soff[sc];
-  const int w = (int)((a.soff[sc + 1] - base) >> 6);
-  const int64_t row = (int64_t)sc * 64 + lane;
-  const bool valid = live && row < a.nrows;
-  const int64_t rc = min(row, a.nrows - 1);
-  const int len = valid ? a.rowlen[rc] : 0;
-  const int pid = (int)a.rowpid[rc];
-  const uint32_t base8 = 8u * (uint32_t)(a.rowbase ? a.rowbase[rc] : (int32_t)rc);
-  const double *__restrict__ xg = a.x;
-  const double *__restrict__ dinv = a.dinv;
-  const double omega = a.omega;
-  const double *vp = a.sval + base + lane;
-  const int wl = w - 1;
-  // the value stream does not depend on the table: first batch (or the whole row) in flight while the table is staged
-  constexpr int NV = WMAX > 0 ? WMAX : UN;
-  double v0[NV];
-#pragma unroll
-  for (int u = 0; u < NV; ++u) {
-    const int64_t o = (int64_t)min(u, wl) * 64;
-    v0[u] = NT ? __builtin_nontemporal_load(vp + o) : vp[o];
-  }
-  double e0 = 0.0, e1 = 0.0, e2 = 0.0, dinv_row = 0.0;
-  if (EPI == EPI_SUB) e0 = a.y[rc];
-  else if (EPI == EPI_RESID) e0 = a.b[rc];
-  else if (EPI == EPI_ADDTO) e0 = a.x2[rc];
-  else if (EPI == EPI_SWEEP) {
-    e0 = a.b[rc];
-    e1 = ONEG ? xg[rc] : dinv[rc];
-    { const double xl = a.x2[rc]; e2 = a.x_zero ? 0.0 : xl; }
-    if (ONEG) dinv_row = dinv[rc];
-  }
-  __syncthreads();
-  const int32_t *to = s_off + pid * a.W;
-  auto gat = [&](int j) -> double {
-    const uint32_t c8 = base8 + (uint32_t)((j < a.W) ? to[j] : 0);
-    if (EPI == EPI_SWEEP && !ONEG) return omega * (ld_off(dinv, c8) * ld_off(xg, c8));
-    return ld_off(xg, c8);
-  };
-  double s = 0.0;
-  if (WMAX > 0 && w <= WMAX) {
-    double g[NV];
-#pragma unroll
-    for (int u = 0; u < NV; ++u) g[u] = gat(min(u, wl));
-#pragma unroll
-    for (int u = 0; u < NV; ++u) {
-      const double pr = v0[u] * g[u];
-      s = (u < len) ? s + pr : s;
-    }
-  } else {
-    double v[UN], g[UN];
-#pragma unroll
-    for (int u = 0; u < UN; ++u) { v[u] = v0[u]; g[u] = gat(min(u, wl)); }
-    int j = 0;
-    for (; j + UN < w; j += UN) {                            // steady state: the next batch is requested unconditionally
-      double vn[UN], gn[UN];
-#pragma unroll
-      for (int u = 0; u < UN; ++u) {
-        const int jj = min(j + UN + u, wl);
-        vn[u] = NT ? __builtin_nontemporal_load(vp + (int64_t)jj * 64) : vp[(int64_t)jj * 64];
-        gn[u] = gat(jj);
-      }
-#pragma unroll
-      for (int u = 0; u < UN; ++u) {
-        const double pr = v[u] * g[u];
-        s = (j + u < len) ? s + pr : s;
-      }
-#pragma unroll
-      for (int u = 0; u < UN; ++u) { v[u] = vn[u]; g[u] = gn[u]; }
-    }
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {                           // last batch
-      const double pr = v[u] * g[u];
-      s = (j + u < len) ? s + pr : s;
-    }
-  }
-  if (valid) {
-    if (EPI == EPI_SET) a.y[row] = s;
-    else if (EPI == EPI_SUB) a.y[row] = e0 - s;
-    else if (EPI == EPI_RESID) a.y[row] = e0 - s;
-    else if (EPI == EPI_ADDTO) { const double t = a.omega != 0.0 ? a.omega * s : s; a.y[row] = t; a.x2[row] = e0 + t; }
-    else {
-      const double dxi = ONEG ? e1 : omega * (e1 * e0);
-      a.x2[row] = e2 + dxi;
-      const double rn = e0 - s;
-      a.y[row] = rn;
       if (ONEG) a.s_out[row] = omega * (dinv_row * rn);
     }
   }
@@ -2294,376 +2001,6 @@ __global__ __launch_bounds__(kBlock, 4) void sells_zsweep_kernel(SellSArgs a, ZW
 }
 
 // ---------------------------------------------------------------------------
-// TWO sweeps per pass over the data (round 6).  RichardsonSmoothers.jl:90-97 is ten sweeps in a row over the same vectors; launched one
-// by one, every sweep reads r_k and writes r_{k+1} through memory (and every second one x).  On a level whose rows are the nodes of a
-// grid (row = z P + y L + x: the 3 x 3 grid of run offsets says so) sweep k + 1 of a tile needs r_{k+1} only one node further out
-// than the tile, so a workgroup can run BOTH sweeps on a tile with r_{k+1} never leaving the CU:
-//   workgroup = W consecutive grid lines (one per wave) x one segment of x x a block of T planes, walked upwards plane by plane;
-//   step z:  phase 1  every wave computes sweep k (the x-untouched form, XM = 1) for its line of plane z from r_k in memory and puts the
-//                     line of r_{k+1} into a ring of four planes in LDS (zeros where the grid has no node: absent taps need finite values)
-//            barrier
-//            phase 2  the W - 2 inner waves compute sweep k + 1 (the form that updates x with both increments, XM = 2) for their line of
-//                     plane z - 1 from the three planes z - 2, z - 1, z of the ring and store r_{k+2} and x.
-// The rim lines (first / last wave), the planes below / above the block and one node left / right of an x segment are computed
-// redundantly by the neighbouring workgroups -- W / (W - 2) x (T + 2) / T more arithmetic on sweep k, none on sweep k + 1 -- and per pair
-// of sweeps memory sees r_k in, r_{k+2} out, x in / out: 32 bytes per row instead of 16 + 40.
-// A ring of FOUR planes needs one barrier per step: phase 1 of step z + 1 writes the slot phase 2 of step z does not read.
-// Every row is summed exactly as sells_r2sweep_kernel / sells_zsweep_kernel sum it (same taps, same order, same strict-mask rule; the
-// rim rows are recomputed from the same inputs), so the pair is bit-identical to the two single sweeps -- except that a tap the row does
-// not store may meet 0.0 instead of a neighbouring line's value: its product is an exact zero either way.
-//   a.x = r_k ; a.y = r_{k+2} ; a.x2 = x (in / out) ; a.pdinv[0] = d ; a.x_zero: x is zero on entry
-// whole != 0 (L <= 127): one wave holds a whole grid line, lane l rows 2 l, 2 l + 1 in both sweeps.  Otherwise a segment of xlen <= 124
-// rows: sweep k on the segment and one node either side (lane l rows x0 - 1 + 2 l, x0 + 2 l; lane 63 only supplies windows), sweep k + 1
-// on rows x0 + 2 l, x0 + 2 l + 1.  The ring stores position p of a line at p - (first row of sweep k + 1) + 1.
-// ---------------------------------------------------------------------------
-// BC ("box, constant"): on a constant-coefficient operator every row of a grid line stores the SAME 27 numbers -- those of the line's
-// class (first / inner / last line of a plane) x (first / inner / last plane) -- except that the first / last row of the line does not
-// store the taps that would leave the line.  With exact zeros at those positions (the ring's pads in phase 2, a select on the window
-// values in phase 1) one set of coefficients serves the whole wave, and it comes out of the KERNEL ARGUMENTS through scalar loads
-// instead of 27 LDS reads per row: the sweeps of a row-pattern level are bound by LDS bandwidth (54 x 8 B per lane and step against
-// ~150 vector instructions), not by memory.  gmg_solver::z2_geo verifies the property row by row on the device (z2_box_check_kernel)
-// before it sets `box`; the sums are those of the general form except for the sign of an exact zero product.
-struct Z2Geo {
-  int P, L, ny, nz;       // rows per plane, per line ; lines per plane ; planes
-  int W, T;               // waves per workgroup (lines incl. the two rim lines) ; planes per block
-  int nyt, nzb, nxs;      // tiles in y, blocks in z, segments in x
-  int xlen, whole;
-  int box;                // 1: coef / cmask below describe every row (BC kernels)
-  double coef[9][27];     // class c = 3 * (plane class) + (line class), class 0 first / 1 inner / 2 last ; entry j = 3 * run + tap
-  uint32_t cmask[9][27];  // 0xffffffff stored, 0 absent
-};
-constexpr int kZ2Slot = 130;     // doubles per line slot of the ring (128 rows + one either side)
-
-// bad[0] != 0 afterwards: some row's pattern is not the class pattern with the taps that leave the line removed
-__global__ void z2_box_check_kernel(int64_t nrows, int L, int ny, int nz, int P, const uint16_t *__restrict__ rowpid, const PatEntry *__restrict__ tab,
-                                    const double *__restrict__ coef, const uint32_t *__restrict__ cmask, int *__restrict__ bad)
-{
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nrows; i += (int64_t)gridDim.x * blockDim.x) {
-    const int x = (int)(i % L), y = (int)((i / L) % ny), z = (int)(i / P);
-    const int c = 3 * (z == 0 ? 0 : z == nz - 1 ? 2 : 1) + (y == 0 ? 0 : y == ny - 1 ? 2 : 1);
-    const PatEntry *te = tab + (size_t)rowpid[i] * 27;
-    bool ok = true;
-    for (int j = 0; j < 27; ++j) {
-      const int dx = j % 3 - 1;
-      const bool inside = x + dx >= 0 && x + dx < L;
-      const unsigned long long want = inside ? (unsigned long long)__double_as_longlong(coef[c * 27 + j]) : 0ull;   // absent entries hold +0.0
-      const uint32_t wm = inside ? cmask[c * 27 + j] : 0u;
-      ok = ok && (unsigned long long)__double_as_longlong(te[j].v) == want && te[j].m == wm;
-    }
-    if (!ok) atomicOr(bad, 1);
-  }
-}
-
-template <bool MK, bool FM, bool BC = false>
-__global__ __launch_bounds__(1024) void sells_z2sweep_kernel(SellSArgs a, Z2Geo g)
-{
-  constexpr int K = 3, NR = 9, nu = K * NR, NUP = 28, SL = kZ2Slot;
-  extern __shared__ double sp_smem[];
-  const int tot = BC ? 0 : a.np * NUP;
-  double *s_tab8 = sp_smem;                                   // [np*NUP] coefficients (absent entries 0.0); the masks stay in global memory
-  double *ring = sp_smem + ((tot + 1) & ~1);                  // [4][W][SL] r_{k+1}
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int W = g.W;
-  const int blk = remap_block(blockIdx.x, gridDim.x, a.xcd_remap);
-  const int xs = blk % g.nxs, t2 = blk / g.nxs, yt = t2 % g.nyt, zb = t2 / g.nyt;
-  const int y = yt * (W - 2) - 1 + wave;
-  const bool vline = y >= 0 && y < g.ny;
-  const bool inner = wave >= 1 && wave <= W - 2 && vline;
-  const int x0 = g.whole ? 0 : xs * g.xlen;
-  const int len = g.whole ? g.L : min(g.xlen, g.L - x0);      // rows of sweep k + 1 in this segment
-  const int ka = g.whole ? 0 : x0 - 1;                        // x of lane 0's first row in sweep k
-  const int klo = g.whole ? 0 : max(0, x0 - 1), khi = g.whole ? g.L : min(g.L, x0 + len + 1);
-  const int xk = ka + 2 * lane;
-  const bool kvA = xk >= klo && xk < khi, kvB = xk + 1 >= klo && xk + 1 < khi;
-  const int xb = x0 + 2 * lane;
-  const bool nvA = xb < x0 + len, nvB = xb + 1 < x0 + len;
-  const int sidx = g.whole ? 2 * lane + 1 : 2 * lane;         // where the lane's two rows of sweep k sit in a line slot
-  const double *__restrict__ rg = a.x;
-  const double omega = a.omega, du = a.pdinv[0];
-  const int last = (int)a.ncols - 1, lastrow = (int)a.nrows - 1;
-  const bool xz = a.x_zero != 0;
-  int roff[NR];
-#pragma unroll
-  for (int q = 0; q < NR; ++q) roff[q] = __builtin_amdgcn_readfirstlane(a.run_off[q]);
-  auto conv = [&](gmg_d2 v) -> gmg_d2 { return gmg_d2{omega * (du * v.x), omega * (du * v.y)}; };   // s = omega * (Dinv * r)
-  // the 27 taps of the lane's two rows from nine converted windows: w0, w1 its own pair, w2, w3 = lane l + 1's (lane 63: 0.0)
-  // (BC: cls = the class of the wave's line and the step's plane, wave-uniform -- the coefficients are scalar loads from the arguments)
-  auto taps = [&](const gmg_d2 *C, const double *tvA, const double *tvB, int cls, double &sA, double &sB) {
-    sA = 0.0; sB = 0.0;
-#pragma unroll
-    for (int q = 0; q < NR; ++q) {
-      const double w0 = C[q].x, w1 = C[q].y;
-      const double w2 = wave_shl1(w0), w3 = wave_shl1(w1);
-      const double wa[3] = {w0, w1, w2}, wb[3] = {w1, w2, w3};
-#pragma unroll
-      for (int t = 0; t < K; ++t) {
-        const double ca = BC ? g.coef[cls][q * K + t] : tvA[q * K + t], cb = BC ? ca : tvB[q * K + t];
-        sA = FM ? __builtin_fma(ca, wa[t], sA) : sA + ca * wa[t];
-        sB = FM ? __builtin_fma(cb, wb[t], sB) : sB + cb * wb[t];
-      }
-    }
-  };
-  // strict form: a sum that is not finite is redone with the masks (a vector that already holds Inf / NaN: rare).  The windows are
-  // fetched again, run by run (getw(q): from memory in phase 1, from the ring in phase 2) -- indexing the register array of the fast
-  // path with a loop counter would move it into scratch memory for the whole kernel
-  auto taps_masked = [&](auto getw, int pidA, int pidB, int cls, double &sA, double &sB) {
-    sA = 0.0; sB = 0.0;
-    const double *tvA = s_tab8 + pidA * NUP, *tvB = s_tab8 + pidB * NUP;
-#pragma unroll 1
-    for (int q = 0; q < NR; ++q) {
-      const gmg_d2 c = conv(getw(q));
-      const double w0 = c.x, w1 = c.y;
-      const double w2 = wave_shl1(w0), w3 = wave_shl1(w1);
-      const double wa[3] = {w0, w1, w2}, wb[3] = {w1, w2, w3};
-#pragma unroll
-      for (int t = 0; t < K; ++t) {
-        const int j = q * K + t;
-        const int ma = BC ? (int)g.cmask[cls][j] : (int)a.tab[pidA * nu + j].m, mb = BC ? ma : (int)a.tab[pidB * nu + j].m;
-        const double ca = BC ? g.coef[cls][j] : tvA[j], cb = BC ? ca : tvB[j];
-        const double ga = __hiloint2double(__double2hiint(wa[t]) & ma, __double2loint(wa[t]));
-        const double gb = __hiloint2double(__double2hiint(wb[t]) & mb, __double2loint(wb[t]));
-        sA = FM ? __builtin_fma(ca, ga, sA) : sA + ca * ga;
-        sB = FM ? __builtin_fma(cb, gb, sB) : sB + cb * gb;
-      }
-    }
-  };
-  // BC, phase 1: window positions that leave the grid line read as exact zeros (lane l holds positions ka - 1 + 2 l and ka + 2 l)
-  const bool zx0 = BC && (ka - 1 + 2 * lane < 0 || ka - 1 + 2 * lane >= g.L), zx1 = BC && (ka + 2 * lane < 0 || ka + 2 * lane >= g.L);
-  const bool zx_any = BC && __any(zx0 || zx1);
-  const int cy = y <= 0 ? 0 : (y >= g.ny - 1 ? 2 : 1);
-  if (!BC)
-    for (int i = threadIdx.x; i < tot; i += blockDim.x) {
-      const int pq = i / NUP, j = i - pq * NUP;
-      s_tab8[i] = j < nu ? (a.tab8 ? a.tab8[pq * nu + j] : a.tab[pq * nu + j].v) : 0.0;
-    }
-  for (int i = threadIdx.x; i < 4 * W * SL; i += blockDim.x) ring[i] = 0.0;
-  __syncthreads();
-  const int zb0 = zb * g.T, zb1 = min(g.nz, zb0 + g.T);
-  typedef double d2a __attribute__((ext_vector_type(2), aligned(16)));
-  // Requests run ahead of the arithmetic (as in sells_zsweep_kernel): the nine windows of sweep k live in registers, converted, and walk
-  // up the planes with the wave -- a step fetches only the three windows of the plane above, and it asks for them, for the rows' own
-  // r_k and for the operands of phase 2 (x, r_k of plane z - 1) BEFORE the arithmetic of the step, so that a workgroup whose waves
-  // all sit in the same phase (one barrier per step) still has its memory requests in flight behind ~300 vector instructions.
-  // Every address is clamped into the vectors: one control path, the same number of requests in the first and last planes.
-  auto loadw = [&](int plane, int q) -> gmg_d2 {                // window q of the lane's rows taken at `plane` (any integer: clamped)
-    const int c = plane * g.P + y * g.L + ka + roff[q] + 2 * lane;
-    const gmg_d2 v = gmg_d2{rg[min(max(c, 0), last)], rg[min(max(c + 1, 0), last)]};
-    return zx_any ? gmg_d2{zx0 ? 0.0 : v.x, zx1 ? 0.0 : v.y} : v;
-  };
-  struct Own { gmg_d2 e0; int pidA, pidB; };
-  auto load_own = [&](int plane) -> Own {                       // sweep k: the rows' own r_k (and pattern ids)
-    Own o;
-    const int row = plane * g.P + y * g.L + ka + 2 * lane;
-    const int ra = min(max(row, 0), lastrow), rb = min(max(row + 1, 0), lastrow);
-    o.e0 = gmg_d2{rg[ra], rg[rb]};
-    o.pidA = BC ? 0 : (int)a.rowpid[ra]; o.pidB = BC ? 0 : (int)a.rowpid[rb];
-    return o;
-  };
-  struct Ops2 { gmg_d2 rp, e2; int pidA, pidB; };
-  auto load_ops2 = [&](int plane) -> Ops2 {                     // sweep k + 1: r_k and x of the rows, pattern ids
-    Ops2 o;
-    const int row = plane * g.P + y * g.L + x0 + 2 * lane;
-    const int ra = min(max(row, 0), lastrow), rb = min(max(row + 1, 0), lastrow);
-    o.rp = gmg_d2{rg[ra], rg[rb]};
-    o.e2 = gmg_d2{a.x2[ra], a.x2[rb]};
-    o.pidA = BC ? 0 : (int)a.rowpid[ra]; o.pidB = BC ? 0 : (int)a.rowpid[rb];
-    return o;
-  };
-  gmg_d2 C[NR];
-#pragma unroll
-  for (int q = 0; q < NR; ++q) C[q] = conv(loadw(zb0 - 1, q));
-  Own cur = load_own(zb0 - 1);
-#pragma unroll 1
-  for (int z = zb0 - 1; z <= zb1; ++z) {
-    // requests of this step: the three windows of plane z + 2 (run 6..8 of step z + 1), the rows' own r_k of plane z + 1, phase 2's operands
-    gmg_d2 N[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) N[q] = loadw(z + 1, 6 + q);
-    const Own nxt = load_own(z + 1);
-    const int zz = z - 1;
-    const Ops2 o2 = load_ops2(zz);
-    // ---- phase 1: sweep k, plane z, this wave's line -> ring slot z & 3
-    gmg_d2 rk1 = gmg_d2{0.0, 0.0};
-    if (vline && z >= 0 && z < g.nz) {                        // (wave-uniform)
-      const int cls1 = 3 * (z == 0 ? 0 : (z == g.nz - 1 ? 2 : 1)) + cy;
-      double sA, sB;
-      taps(C, s_tab8 + cur.pidA * NUP, s_tab8 + cur.pidB * NUP, cls1, sA, sB);
-      if (MK && !__all(__builtin_isfinite(sA) && __builtin_isfinite(sB)))
-        taps_masked([&](int q) -> gmg_d2 { const int c = z * g.P + y * g.L + ka + a.run_off[q] + 2 * lane;
-                                           const gmg_d2 v = gmg_d2{rg[min(max(c, 0), last)], rg[min(max(c + 1, 0), last)]};
-                                           return gmg_d2{zx0 ? 0.0 : v.x, zx1 ? 0.0 : v.y}; },
-                    cur.pidA, cur.pidB, cls1, sA, sB);
-      rk1 = gmg_d2{kvA ? cur.e0.x - sA : 0.0, kvB ? cur.e0.y - sB : 0.0};
-    }
-    {
-      double *slot = ring + ((z & 3) * W + wave) * SL;
-      slot[sidx] = rk1.x; slot[sidx + 1] = rk1.y;
-    }
-    __syncthreads();
-    // ---- phase 2: sweep k + 1, plane z - 1, inner lines, from the ring
-    if (inner && zz >= zb0 && zz < zb1) {                     // (wave-uniform)
-      const int cls2 = 3 * (zz == 0 ? 0 : (zz == g.nz - 1 ? 2 : 1)) + cy;
-      const double *tvA = s_tab8 + o2.pidA * NUP, *tvB = s_tab8 + o2.pidB * NUP;
-      double sA = 0.0, sB = 0.0;
-      gmg_d2 raw4 = gmg_d2{0.0, 0.0};
-#pragma unroll
-      for (int q = 0; q < NR; ++q) {
-        const int dz = q / 3 - 1, dy = q % 3 - 1;
-        const double *sl = ring + (((zz + dz) & 3) * W + wave + dy) * SL;
-        const gmg_d2 v = *reinterpret_cast<const d2a *>(sl + 2 * lane);
-        if (q == 4) raw4 = v;
-        const gmg_d2 c = conv(v);
-        const double w0 = c.x, w1 = c.y;
-        const double w2 = wave_shl1(w0), w3 = wave_shl1(w1);
-        const double wa[3] = {w0, w1, w2}, wb[3] = {w1, w2, w3};
-#pragma unroll
-        for (int t = 0; t < K; ++t) {
-          const double ca = BC ? g.coef[cls2][q * K + t] : tvA[q * K + t], cb = BC ? ca : tvB[q * K + t];
-          sA = FM ? __builtin_fma(ca, wa[t], sA) : sA + ca * wa[t];
-          sB = FM ? __builtin_fma(cb, wb[t], sB) : sB + cb * wb[t];
-        }
-      }
-      if (MK && !__all(__builtin_isfinite(sA) && __builtin_isfinite(sB)))
-        taps_masked([&](int q) -> gmg_d2 { const double *sl = ring + (((zz + q / 3 - 1) & 3) * W + wave + q % 3 - 1) * SL;
-                                           return *reinterpret_cast<const d2a *>(sl + 2 * lane); }, o2.pidA, o2.pidB, cls2, sA, sB);
-      const gmg_d2 e0 = gmg_d2{raw4.y, wave_shl1(raw4.x)};     // the rows' own r_{k+1}: positions x, x + 1 of the centre window
-      const gmg_d2 e2 = xz ? gmg_d2{0.0, 0.0} : o2.e2;
-      const gmg_d2 rn = gmg_d2{e0.x - sA, e0.y - sB};
-      const gmg_d2 sk = gmg_d2{omega * (du * e0.x), omega * (du * e0.y)};
-      const gmg_d2 xn = gmg_d2{(e2.x + omega * (du * o2.rp.x)) + sk.x, (e2.y + omega * (du * o2.rp.y)) + sk.y};
-      const int row = zz * g.P + y * g.L + x0 + 2 * lane;
-      if (nvA) { a.x2[row] = xn.x; a.y[row] = rn.x; }
-      if (nvB) { a.x2[row + 1] = xn.y; a.y[row + 1] = rn.y; }
-    }
-    // the walk: plane z's windows 3..8 are plane z + 1's windows 0..5
-#pragma unroll
-    for (int q = 0; q < 6; ++q) C[q] = C[q + 3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) C[6 + q] = conv(N[q]);
-    cur = nxt;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// The single sweep of a constant-coefficient box (round 6): what phase 1 of sells_z2sweep_kernel<.., BC> does, without the ring, the
-// barrier and the rim rows.  One wave = one grid line (a segment of <= 126 rows of it) walked up T planes: nine converted windows in
-// registers, three new ones per step requested a step ahead, the 27 coefficients of the line's class from the KERNEL ARGUMENTS (scalar
-// loads) -- no pattern ids, no coefficient table in LDS, no LDS at all.  Window positions that leave the line read as exact zeros, so
-// the line's first and last rows use the same coefficients as the rest.  Sums as in sells_r2sweep_kernel / sells_zsweep_kernel (same
-// taps, same order) up to the sign of an exact zero product; strict form: cmask of the class.
-//   a.x = r_k ; a.y = r_{k+1} ; a.x2 = x ; a.s_out = r_{k-1} (XM = 2) ; a.pdinv[0] = d ; g.T = planes per chain, g.W unused
-// ---------------------------------------------------------------------------
-template <int XM, bool MK, bool FM>
-__global__ __launch_bounds__(kBlock, 4) void sells_boxsweep_kernel(SellSArgs a, Z2Geo g)
-{
-  constexpr int K = 3, NR = 9;
-  const int lane = threadIdx.x & 63;
-  const int wpb = blockDim.x >> 6, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int blk = remap_block(blockIdx.x, gridDim.x, a.xcd_remap);
-  const int chain = blk * wpb + wave;                         // (zb, y, xs), xs fastest: neighbouring waves hold neighbouring lines of the same planes
-  const int per_zb = g.ny * g.nxs;
-  if (chain >= g.nzb * per_zb) return;
-  const int zb = chain / per_zb, c2 = chain - zb * per_zb, y = c2 / g.nxs, xs = c2 - y * g.nxs;
-  const int x0 = g.whole ? 0 : xs * g.xlen;
-  const int len = g.whole ? g.L : min(g.xlen, g.L - x0);
-  const double *__restrict__ rg = a.x;
-  const double omega = a.omega, du = a.pdinv[0];
-  const int last = (int)a.ncols - 1, lastrow = (int)a.nrows - 1;
-  const bool xz = a.x_zero != 0;
-  int roff[NR];
-#pragma unroll
-  for (int q = 0; q < NR; ++q) roff[q] = __builtin_amdgcn_readfirstlane(a.run_off[q]);
-  auto conv = [&](gmg_d2 v) -> gmg_d2 { return gmg_d2{omega * (du * v.x), omega * (du * v.y)}; };
-  // lane l: rows x0 + 2 l, x0 + 2 l + 1 ; window positions x0 - 1 + 2 l, x0 + 2 l (lane 63 of a segment only supplies windows)
-  const int xr = x0 + 2 * lane;
-  const bool vA = xr < x0 + len, vB = xr + 1 < x0 + len;
-  const bool zx0 = x0 - 1 + 2 * lane < 0 || x0 - 1 + 2 * lane >= g.L, zx1 = x0 + 2 * lane >= g.L;
-  const bool zx_any = __any(zx0 || zx1);
-  const int cy = y <= 0 ? 0 : (y >= g.ny - 1 ? 2 : 1);
-  const int z0 = zb * g.T, z1 = min(g.nz, z0 + g.T);
-  const int lbase = y * g.L + x0;
-  auto loadw = [&](int plane, int q) -> gmg_d2 {
-    const int c = plane * g.P + lbase + roff[q] + 2 * lane;
-    const gmg_d2 v = gmg_d2{rg[min(max(c, 0), last)], rg[min(max(c + 1, 0), last)]};
-    return zx_any ? gmg_d2{zx0 ? 0.0 : v.x, zx1 ? 0.0 : v.y} : v;
-  };
-  struct Own { gmg_d2 e0, e2, rp; };
-  auto load_own = [&](int plane) -> Own {
-    Own o;
-    const int row = plane * g.P + lbase + 2 * lane;
-    const int ra = min(max(row, 0), lastrow), rb = min(max(row + 1, 0), lastrow);
-    o.e0 = gmg_d2{rg[ra], rg[rb]};
-    o.e2 = gmg_d2{0.0, 0.0}; o.rp = gmg_d2{0.0, 0.0};
-    if (XM != 1) o.e2 = gmg_d2{a.x2[ra], a.x2[rb]};
-    if (XM == 2) o.rp = gmg_d2{a.s_out[ra], a.s_out[rb]};
-    return o;
-  };
-  gmg_d2 C[NR];
-#pragma unroll
-  for (int q = 0; q < NR; ++q) C[q] = conv(loadw(z0, q));
-  Own cur = load_own(z0);
-#pragma unroll 1
-  for (int z = z0; z < z1; ++z) {
-    gmg_d2 N[3];
-    const int zn = min(z + 1, z1 - 1);                        // (past the end of the chain: the last step again, unused)
-#pragma unroll
-    for (int q = 0; q < 3; ++q) N[q] = loadw(zn, 6 + q);
-    const Own nxt = load_own(zn);
-    const int cls = 3 * (z == 0 ? 0 : (z == g.nz - 1 ? 2 : 1)) + cy;
-    double sA = 0.0, sB = 0.0;
-#pragma unroll
-    for (int q = 0; q < NR; ++q) {
-      const double w0 = C[q].x, w1 = C[q].y;
-      const double w2 = wave_shl1(w0), w3 = wave_shl1(w1);
-      const double wa[3] = {w0, w1, w2}, wb[3] = {w1, w2, w3};
-#pragma unroll
-      for (int t = 0; t < K; ++t) {
-        const double c = g.coef[cls][q * K + t];
-        sA = FM ? __builtin_fma(c, wa[t], sA) : sA + c * wa[t];
-        sB = FM ? __builtin_fma(c, wb[t], sB) : sB + c * wb[t];
-      }
-    }
-    if (MK && !__all(__builtin_isfinite(sA) && __builtin_isfinite(sB))) {
-      sA = 0.0; sB = 0.0;
-#pragma unroll 1
-      for (int q = 0; q < NR; ++q) {
-        const int cc = z * g.P + lbase + a.run_off[q] + 2 * lane;
-        gmg_d2 v = gmg_d2{rg[min(max(cc, 0), last)], rg[min(max(cc + 1, 0), last)]};
-        v = conv(gmg_d2{zx0 ? 0.0 : v.x, zx1 ? 0.0 : v.y});
-        const double w0 = v.x, w1 = v.y;
-        const double w2 = wave_shl1(w0), w3 = wave_shl1(w1);
-        const double wa[3] = {w0, w1, w2}, wb[3] = {w1, w2, w3};
-#pragma unroll
-        for (int t = 0; t < K; ++t) {
-          const int j = q * K + t;
-          const int m = (int)g.cmask[cls][j];
-          const double c = g.coef[cls][j];
-          const double ga = __hiloint2double(__double2hiint(wa[t]) & m, __double2loint(wa[t]));
-          const double gb = __hiloint2double(__double2hiint(wb[t]) & m, __double2loint(wb[t]));
-          sA = FM ? __builtin_fma(c, ga, sA) : sA + c * ga;
-          sB = FM ? __builtin_fma(c, gb, sB) : sB + c * gb;
-        }
-      }
-    }
-    const gmg_d2 rn = gmg_d2{cur.e0.x - sA, cur.e0.y - sB};
-    const gmg_d2 sk = gmg_d2{omega * (du * cur.e0.x), omega * (du * cur.e0.y)};
-    const gmg_d2 e2 = xz ? gmg_d2{0.0, 0.0} : cur.e2;
-    gmg_d2 xn = gmg_d2{0.0, 0.0};
-    if (XM == 0) xn = gmg_d2{e2.x + sk.x, e2.y + sk.y};
-    else if (XM == 2) xn = gmg_d2{(e2.x + omega * (du * cur.rp.x)) + sk.x, (e2.y + omega * (du * cur.rp.y)) + sk.y};
-    const int row = z * g.P + lbase + 2 * lane;
-    if (vA) { if (XM != 1) a.x2[row] = xn.x; a.y[row] = rn.x; }
-    if (vB) { if (XM != 1) a.x2[row + 1] = xn.y; a.y[row + 1] = rn.y; }
-#pragma unroll
-    for (int q = 0; q < 6; ++q) C[q] = C[q + 3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) C[6 + q] = conv(N[q]);
-    cur = nxt;
-  }
-}
-
-// ---------------------------------------------------------------------------
 // Wide rows (Q2: 25 runs of 5 consecutive offsets, 125 entries per row) in the z-walk form (round 5).  The runs are a 5 x 5 grid,
 // run q = 5 (dz + 2) + (dy + 2) at dz P + dy L - 2, so 20 of the 25 windows of the slice at r0 + P are windows of the slice at r0:
 // a wave keeps an interval of <= 60 rows of a grid plane, walks T planes upwards and gathers FIVE new windows per step instead of
@@ -3067,176 +2404,6 @@ __global__ __launch_bounds__(OCC == 2 ? 2 * kBlock : kBlock, OCC == 2 ? 4 : 1) v
     __shared__ double sh[4];
     const double t = block_sum(dsum, sh);
     if (threadIdx.x == 0) a.s_out[blockIdx.x] = t;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// The r-gather sweep with the gathers shared through LDS ("tile sweep").  sells_rsweep_kernel fetches every r value nine times out of
-// L2 (once per run: 3 x 3 neighbouring grid lines; only the three taps of a run are shared inside the wave) -- at 128^3 that is
-// 150 MB of L2 -> L1 traffic per sweep on top of the 61 MB the sweep has to move, and neither fewer instructions nor another launch
-// geometry changes its 21-22 us (profiles/r03_tuning.md section 10).  Here a workgroup of WPB waves takes TILES of T <= 3 WPB
-// consecutive slices (62 T rows; T is chosen by the launcher so that the tiles fill whole rounds of resident workgroups).  The windows of all slices of a tile for one run are one contiguous stretch of r (62 T + 2 values),
-// and the stretches of runs whose offsets differ by less than that -- the three lines of a plane -- overlap: the host merges them
-// into segments (SellTile), the workgroup loads each segment ONCE, coalesced, converts it (s = omega*(d*r): two multiplies per loaded
-// value instead of per gathered value) and keeps it in LDS; a slice then reads its nine windows from LDS.  2.7 x fewer values fetched
-// at 128^3, none of them a gather.  Same taps in the same order on the same values: bit-identical to sells_rsweep_kernel.
-// ---------------------------------------------------------------------------
-struct SellTile {
-  int T;                    // slices per tile
-  int nseg;                 // merged stretches of r per tile
-  int seg_off[12];          // first column of the stretch relative to the tile's first row
-  int seg_len[12];
-  int seg_base[12];         // its place in the LDS staging array (elements)
-  int run_lds[32];          // window of run r for the tile's first slice: staging index of its lane 0
-  int elems;                // staged values per tile
-};
-
-// BC: coefficients broadcast inside DPP rows.  27 of the 36 LDS reads of a slice are coefficient reads (216 of 290 B per row: at 288^3
-// the LDS pipes are busy for 99 us of a 203 us sweep).  When the 16 lanes of every DPP row of the slice carry ONE pattern (no grid-line
-// end inside the slice: 4 of 5 slices at 288^3) the lanes of a row load that pattern's 27 coefficients ONCE -- lane l the entries
-// l % 16 and 16 + l % 16 -- and a tap takes its coefficient from lane j of the row with ONE `v_mov_b64_dpp row_newbcast:j` (gfx950 has
-// no DPP form of the 64-bit multiply): a vector instruction on one of four SIMDs instead of a 512-byte read on the CU's one LDS pipe.
-// Same coefficient values, same products, same order: bit-identical.  Other slices keep the per-lane LDS reads.
-template <int J>
-__device__ __forceinline__ double row_bcast(double v)        // lane J of the caller's DPP row (16 lanes) to every lane of that row
-{
-  double r;
-  asm("v_mov_b64_dpp %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(v), "n"(J));
-  return r;
-}
-// the three taps of run Q of a 27-point slice with coefficients c0 (entries 0..15 in lanes 0..15 of every DPP row) and c1 (entries 16..26)
-template <bool FM, int Q>
-__device__ __forceinline__ double taps_bcast_run(double s, double c, double c0, double c1)
-{
-  constexpr int J0 = 3 * Q, J1 = 3 * Q + 1, J2 = 3 * Q + 2;
-  const double k0 = row_bcast<J0 & 15>(J0 < 16 ? c0 : c1), k1 = row_bcast<J1 & 15>(J1 < 16 ? c0 : c1), k2 = row_bcast<J2 & 15>(J2 < 16 ? c0 : c1);
-  s = FM ? __builtin_fma(k0, c, s) : s + k0 * c;
-  c = wave_shl1(c);
-  s = FM ? __builtin_fma(k1, c, s) : s + k1 * c;
-  c = wave_shl1(c);
-  s = FM ? __builtin_fma(k2, c, s) : s + k2 * c;
-  return s;
-}
-template <int XM, bool MK, int WPB, bool FM = false, bool BC = false>
-__global__ __launch_bounds__(64 * WPB, 8) void sells_tsweep_kernel(SellSArgs a, SellTile tl)   // 8 waves per SIMD = two resident workgroups of 16 waves per CU: <= 64 VGPRs
-{
-  constexpr int K = 3, ROWS = 65 - K, RB = 3, SPW = 3;       // T <= SPW * WPB slices per tile: slice j of the tile belongs to wave j % WPB
-  const int T = tl.T;
-  extern __shared__ double sp_smem[];
-  const int nu = K * a.nruns;
-  const int tot = a.np * nu;
-  // LDS: [np*nu] coefficients, dense | strict form (MK): [np*nu] high-word masks (only read by batches holding a non-finite value) | stage
-  double *s_tab8 = sp_smem;
-  uint32_t *s_msk = reinterpret_cast<uint32_t *>(sp_smem + tot);
-  double *s_stage = sp_smem + (MK ? 2 : 1) * (size_t)tot;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int ntiles = (a.nslices + T - 1) / T;
-  const double *__restrict__ rg = a.x;
-  const double omega = a.omega;
-  const double du = a.pdinv[0];
-  const int last = (int)a.ncols - 1;
-  const int lastrow = (int)a.nrows - 1;
-  const bool xz = a.x_zero != 0;
-  if (MK) { for (int i = threadIdx.x; i < tot; i += blockDim.x) { const PatEntry en = a.tab[i]; s_tab8[i] = en.v; s_msk[i] = en.m; } }
-  else { for (int i = threadIdx.x; i < tot; i += blockDim.x) s_tab8[i] = a.tab8[i]; }
-  // (requesting the next tile's stretches and row-wise operands a tile ahead was tried: the registers it takes leave ONE workgroup
-  // per CU instead of two, and the sweep got slower -- 223 instead of 210 us at 288^3; two resident workgroups overlap their phases)
-  // Workgroups are dealt to the eight XCDs round-robin; each XCD walks its own contiguous eighth of the tiles with all its workgroups
-  // side by side, so the stretches of the planes above and below (the own stretches of tiles one plane away) are in that XCD's L2.
-  // gridDim.x is a multiple of 8.
-  const int wpx = gridDim.x >> 3, xcd = blockIdx.x & 7, wq = blockIdx.x >> 3;
-  const int tpx = (ntiles + 7) >> 3;
-  const int t_hi = min(ntiles, (xcd + 1) * tpx);
-  for (int tile = xcd * tpx + wq; tile < t_hi; tile += wpx) {
-    const int ts = tile * T;                                 // first slice of the tile
-    const int R0 = ts * ROWS;
-    // row-wise operands of this wave's slices: requested before the staging loads, used after the taps
-    int pid[SPW], row[SPW];
-    bool live[SPW];
-    double e0[SPW], e2[SPW], rp[SPW];
-#pragma unroll
-    for (int i = 0; i < SPW; ++i) {
-      const int slice = ts + wave + i * WPB;
-      live[i] = wave + i * WPB < T && slice < a.nslices;
-      row[i] = min(slice, a.nslices - 1) * ROWS + lane;
-      const int rc = min(row[i], lastrow);
-      pid[i] = (int)a.rowpid[rc];
-      e0[i] = rg[rc];
-      e2[i] = 0.0; rp[i] = 0.0;
-      if (XM != 1) { const double xl = a.x2[rc]; e2[i] = xz ? 0.0 : xl; }
-      if (XM == 2) rp[i] = a.s_out[rc];
-    }
-    __syncthreads();                                         // the previous tile's windows have been read (first tile: the table is complete)
-    for (int sg = 0; sg < tl.nseg; ++sg) {
-      const int c0 = R0 + tl.seg_off[sg];
-      double *dst = s_stage + tl.seg_base[sg];
-      for (int p = threadIdx.x; p < tl.seg_len[sg]; p += blockDim.x) dst[p] = omega * (du * rg[min(max(c0 + p, 0), last)]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < SPW; ++i) {
-      if (!live[i]) continue;                                // uniform in the wave
-      const int rel = (wave + i * WPB) * ROWS + lane;
-      const uint32_t *tm = s_msk + pid[i] * nu;
-      const double *tv = s_tab8 + pid[i] * nu;
-      double s = 0.0;
-      bool done = false;
-      if (BC) {                                              // (the launcher sets BC only for nine runs of three)
-        // the pattern of the DPP row's first lane; the two halo lanes (no row of their own) follow their row
-        const int lead = __builtin_amdgcn_update_dpp(0, pid[i], 0x150, 0xf, 0xf, true);
-        if (__all(lane >= ROWS || pid[i] == lead)) {
-          const double *tl16 = s_tab8 + lead * nu + (lane & 15);
-          const double c0 = tl16[0], c1 = (lane & 15) < 11 ? tl16[16] : 0.0;
-          // (three windows in flight at a time: more would cost the second resident workgroup its registers)
-          double w0 = s_stage[tl.run_lds[0] + rel], w1 = s_stage[tl.run_lds[1] + rel], w2 = s_stage[tl.run_lds[2] + rel];
-          double v0 = s_stage[tl.run_lds[3] + rel], v1 = s_stage[tl.run_lds[4] + rel], v2 = s_stage[tl.run_lds[5] + rel];
-          s = taps_bcast_run<FM, 0>(s, w0, c0, c1); s = taps_bcast_run<FM, 1>(s, w1, c0, c1); s = taps_bcast_run<FM, 2>(s, w2, c0, c1);
-          w0 = s_stage[tl.run_lds[6] + rel]; w1 = s_stage[tl.run_lds[7] + rel]; w2 = s_stage[tl.run_lds[8] + rel];
-          s = taps_bcast_run<FM, 3>(s, v0, c0, c1); s = taps_bcast_run<FM, 4>(s, v1, c0, c1); s = taps_bcast_run<FM, 5>(s, v2, c0, c1);
-          s = taps_bcast_run<FM, 6>(s, w0, c0, c1); s = taps_bcast_run<FM, 7>(s, w1, c0, c1); s = taps_bcast_run<FM, 8>(s, w2, c0, c1);
-          done = true;
-        }
-      }
-      if (!done)
-      for (int r0 = 0; r0 < a.nruns; r0 += RB) {
-        double cur[RB];
-#pragma unroll
-        for (int q = 0; q < RB; ++q) cur[q] = s_stage[tl.run_lds[r0 + q] + rel];
-#pragma unroll
-        for (int q = 0; q < RB; ++q) {
-          double c = cur[q];
-#pragma unroll
-          for (int t = 0; t < K; ++t) {
-            if (t > 0) c = wave_shl1(c);
-            const int j = (r0 + q) * K + t;
-            s = FM ? __builtin_fma(tv[j], c, s) : s + tv[j] * c;
-          }
-        }
-      }
-      // strict form: "every sum of the slice finite" proves that no mask was needed (see sells_r2sweep_kernel); otherwise the slice
-      // is redone from the staged windows with the masks
-      if (MK && !__all(__builtin_isfinite(s))) {
-        s = 0.0;
-        for (int r0 = 0; r0 < a.nruns; ++r0) {
-          double c = s_stage[tl.run_lds[r0] + rel];
-#pragma unroll
-          for (int t = 0; t < K; ++t) {
-            if (t > 0) c = wave_shl1(c);
-            const int j = r0 * K + t;
-            const double g = __hiloint2double(__double2hiint(c) & (int)tm[j], __double2loint(c));
-            s = FM ? __builtin_fma(tv[j], g, s) : s + tv[j] * g;
-          }
-        }
-      }
-      if (lane < ROWS && row[i] <= lastrow) {
-        const int r = row[i];
-        const double rn = e0[i] - s;
-        const double sk = omega * (du * e0[i]);              // the row's own s_k
-        if (XM == 0) a.x2[r] = e2[i] + sk;
-        else if (XM == 2) a.x2[r] = (e2[i] + omega * (du * rp[i])) + sk;
-        a.y[r] = rn;
-      }
-    }
   }
 }
 

@@ -139,7 +139,7 @@ struct HipGMGLinearSolver{A,B,C,D,E,F} <: Gridap.Algebra.LinearSolver
 end
 
 # Same keyword surface as GMGLinearSolver(smatrices,interp,restrict;...) GMGLinearSolvers.jl:48-69, plus keywords the
-# reference has no use for: `cycle_values` (:float64 / :float32, below), `device`, `options` (layout / schedule policy of THIS solver: e.g. Dict("pat_tile"=>2, "persist"=>0,
+# reference has no use for: `cycle_values` (:float64 / :float32, below), `device`, `options` (layout / schedule policy of THIS solver: e.g. Dict("pat_zwalk"=>2, "persist"=>0,
 # "x0_zero"=>1); unknown keys are rejected by the library) and `pin_vectors` (default false; true: the vectors solve! sees are page-locked
 # once and then move over PCIe by DMA at the link rate -- 3.6 ms instead of 4.7 ms per config-2 solve; the setup keeps them alive.
 # For a top-level solve! that is called again and again with the SAME x and b; not for a preconditioner applied to rotating work vectors)

@@ -482,7 +482,7 @@ GMG_API int gmg_set_options(gmg_handle_t h, int mode, int cycle, int maxiter, do
 
 /* Layout / schedule policy of ONE handle.  The reference configures a solver by constructor keywords only
  * (GMGLinearSolvers.jl:48-58); every switch this library used to read from the environment is therefore a per-handle option:
- *     gmg_set_option(h, "pat_tile", 2)        ("PAT_TILE", "GMG_PAT_TILE" name the same option; unknown keys -> GMG_ERR_INVALID)
+ *     gmg_set_option(h, "pat_r2", 0)          ("PAT_R2", "GMG_PAT_R2" name the same option; unknown keys -> GMG_ERR_INVALID)
  * Options take effect at the next gmg_setup (setting one after a setup invalidates it, like a new operator would), except the
  * "live" ones marked (*) which act at the next call.  The environment variable GMG_<KEY>, when set, still OVERRIDES the handle's
  * value -- a debugging / A-B device, not the configuration interface.  Keys (default):
@@ -492,8 +492,9 @@ GMG_API int gmg_set_options(gmg_handle_t h, int mode, int cycle, int maxiter, do
  *                    loads of the float stream by its size, with the thresholds of the fp64 stream; 0 never; 1 always; 2 always, the
  *                    row-wise operands too -- float32 launches only, same bits in every setting)
  *   measurement      prof_stride (7: HIP events on every n-th sweep launch of the profiled level)
- *   sweep kernels    pat_rsweep (1) pat_r2 (1: two rows per lane in the r-gather sweep) pat_r2_occ (2: its 64-register form, eight waves per SIMD, in workgroups of eight waves on big levels; 1: four waves; 0: off) pat_r2_wgs (0 = one round of workgroups) pat_tile (0: never -- levels >= pat_tile_rows (3500000) take the pair sweep with one slice per wave; 1: tile sweep on those levels; 2: wherever it applies) pat_tile_min (512)
- *                    pat_tile_t (48) pat_tile_lds (79872) pat_strict (1) pat_fma (0: products and sums rounded separately, as the
+ *   sweep kernels    pat_rsweep (1) pat_r2 (1: two rows per lane in the r-gather sweep) pat_r2_occ (2: its 64-register form, eight waves per SIMD, in workgroups of eight waves on big levels; 1: four waves; 0: off) pat_r2_wgs (0 = one round of workgroups)
+ *                    pat_tile_rows (3500000: the size, in rows, from which the pair sweep and the pair mat-vec take that eight-wave form, one slice per wave)
+ *                    pat_strict (1) pat_fma (0: products and sums rounded separately, as the
  *                    reference's mul!; 1: fused multiply-add taps in the row-pattern sweeps -- not bit-identical)
  *                    pat_xnext (1: per-sweep passes of an even number of r-gather sweeps on one rank add s_k and s_{k+1} to x in sweeps
  *                    0, 2, ... -- s_{k+1} from the r_{k+1} the sweep holds in registers, no r_{k-1} re-read; 0: x = (x + s_{k-1}) + s_k in
@@ -511,13 +512,6 @@ GMG_API int gmg_set_options(gmg_handle_t h, int mode, int cycle, int maxiter, do
  *                    pat_zwalk (1: levels of >= pat_zwalk_rows (9000000: where the vectors of a sweep outgrow the 256 MB Infinity Cache) rows sweep as a walk up the grid planes -- an interval of a plane
  *                    per wave, three new windows per step, pat_zwalk_t (12) planes per chain; 2: every level; 0: off) pat_zwalk_mv (1: their
  *                    mat-vecs too) pat_zwalk_wide (1: the wide-row (Q2) operator applications of levels of >= pat_zwalk_wide_rows (1000000) rows in the same form, 25 windows in registers)
- *                    pat_fuse2 (0: opt-in.  1: on grid levels of >= pat_fuse2_rows (1000000) rows of one GPU a smoothing pass runs TWO sweeps per launch -- r_k in,
- *                    r_{k+2} out, r_{k+1} in LDS only, sells_z2sweep_kernel; 2: every level that qualifies.  Bit-identical to the single sweeps; measured slower
- *                    than them on MI355X, see profiles/r06_ab_fuse2.txt) pat_fuse2_w / pat_fuse2_t (0 = chosen from the size: grid lines per workgroup, planes
- *                    per block) pat_fuse2_box (1: constant-coefficient boxes read one coefficient set per wave from the kernel arguments)
- *                    pat_box (0: opt-in, measured slower -- profiles/r06_ab_box.txt.  1: levels of pat_box_min_rows (1000000) .. pat_box_max_rows (9000000) rows whose operator is a constant-coefficient stencil on a box --
- *                    verified row by row at setup -- sweep with one coefficient set per wave read from the kernel arguments: no pattern ids, no LDS,
- *                    sells_boxsweep_kernel; 2: every level that qualifies; 0: off) pat_box_t (0: planes per chain from the level's size)
  *   reductions       red_fused (1: inside CG the second stage of every dot is done by the kernel that consumes the scalar and the
  *                    norm is reduced + posted to the host by one launch; 0: one reduce launch per dot.  Same bits either way)
  *                    cg_split* (0: measured equal, profiles/xnext_ab_128.md; where red_fused applies: 1 = CG's x += alpha p runs in a kernel of its own behind the launch that posts

@@ -35,7 +35,7 @@ def test_plane_rows_is_the_block_row_blocks_yields(po, make):
 
 def test_ragged_problem_lands_in_the_gate_bands(po):
     """Q1 (240, 232, 200) cells, 4 levels: level 0 >= pat_zwalk_rows (9e6; walk sweeps, above big_rows 4e6: XCD remap), level 1
-    between pat_fuse2_rows / pat_box_min_rows (1e6) and pat_tile_rows (3.5e6), level 2 between pat_r2mv_min (1e5) and
+    between 1e6 rows and pat_tile_rows (3.5e6: the pair sweep in its four-wave form), level 2 between pat_r2mv_min (1e5) and
     pat_coded_min_rows (5e5), the coarsest between GMG_GJ_WIDE_MIN (4096) and coarse_auto_cg_min (20 000): the device 64-wide
     Gauss-Jordan inverse with a ragged last panel (n % 64 = 32) and n not a multiple of 128; 199 node planes = 16 chains of 12 + 7;
     no axis a multiple of 64."""

@@ -33,8 +33,8 @@ def setup(S, solver, A):
 
 # the sweep kernel family the default options pick per level (include/gmg_amd.h gates; the bands are checked by
 # tests/test_fullsize_reference.py::test_ragged_problem_lands_in_the_gate_bands): level 0, 1.1e7 rows >= pat_zwalk_rows (9e6) -> the
-# walk; level 1, 1.35e6 rows < pat_tile_rows (3.5e6) and above the one-launch pass (~5e5 rows) -> the pair sweep, four waves per
-# workgroup; level 2 runs one-launch passes (no sweep signature)
+# walk; level 1, 1.35e6 rows < pat_tile_rows (3.5e6: the pair sweep's eight-wave form starts there) and above the one-launch pass
+# (~5e5 rows) -> the pair sweep, four waves per workgroup; level 2 runs one-launch passes (no sweep signature)
 RAGGED_FAMILIES = {0: "sells_zsweep_kernel", 1: ("sells_r2sweep_kernel<", "OCC=1")}
 
 

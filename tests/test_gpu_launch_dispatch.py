@@ -14,8 +14,8 @@ A pass of four sweeps (pre slot) and one of three (post slot) per handle: x mode
 sweep), 1 and 2 elsewhere, and 1, 2, 0 in the odd pass.
 
 Operators: the 27-point one of hierarchy((24, 24, 24), 3) (12 167 rows: 97 slices of 126 rows, the last one ragged) and the 9-point
-one of hierarchy((130, 66), 2) (NR = 3).  Pairs that do not exist: the z-walk and the box sweep need nine runs (3 x 3 offsets a plane
-apart), so the 9-point operator has neither, nor the eight-wave pair mat-vec.  The mat-vec kernels leave no signature: (c) is for the
+one of hierarchy((130, 66), 2) (NR = 3).  Pairs that do not exist: the z-walk needs nine runs (3 x 3 offsets a plane
+apart), so the 9-point operator does not have it, nor the eight-wave pair mat-vec.  The mat-vec kernels leave no signature: (c) is for the
 sweeps.  sells_sweep_kernel (the form that takes TD) has no FM argument: pat_fma = 0 only."""
 import numpy as np
 import pytest
@@ -33,10 +33,8 @@ SWEEP_FORMS = {
     "zwalk": ({"pat_zwalk": 2}, "sells_zsweep_kernel"),
     "pair": ({"pat_zwalk": 0}, "sells_r2sweep_kernel"),
     "row": ({"pat_r2": 0}, "sells_rsweep_kernel"),
-    "tile": ({"pat_tile": 2}, "sells_tsweep_kernel"),
-    "box": ({"pat_box": 2}, "sells_boxsweep_kernel"),
 }
-SWEEP_CASES = [("27pt", f) for f in SWEEP_FORMS] + [("9pt", f) for f in ("pair", "row", "tile")]
+SWEEP_CASES = [("27pt", f) for f in SWEEP_FORMS] + [("9pt", f) for f in ("pair", "row")]
 
 MV_FORMS = {
     "r2mv": {"pat_zwalk": 0, "pat_r2mv_min": 1, "pat_r2mv_dot": 0},
@@ -90,8 +88,7 @@ def check(out, ref, fma, what):
 
 
 @pytest.mark.parametrize("shape,form", SWEEP_CASES)
-def test_gather_sweep_forms_take_their_options(S, hierarchy, monkeypatch, shape, form):
-    monkeypatch.setenv("GMG_PAT_TILE_MIN", "0")               # (the tile sweep declines levels of < 512 slices)
+def test_gather_sweep_forms_take_their_options(S, hierarchy, shape, form):
     H = hierarchy(*SHAPES[shape])
     ref = reference(S, hierarchy, shape)
     opts, family = SWEEP_FORMS[form]

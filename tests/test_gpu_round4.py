@@ -59,6 +59,10 @@ def test_options_choose_the_layout_per_handle(S, po, orc):
     with pytest.raises(abi.GmgError) as e:
         n1.P_ns.set_option("no_such_option", 1)
     assert e.value.code == abi.ERR_INVALID
+    for retired in ("pat_tile", "pat_fuse2", "pat_box"):      # the retired sweeps' options are unknown keys like any other
+        with pytest.raises(abi.GmgError) as e:
+            n1.P_ns.set_option(retired, 1)
+        assert e.value.code == abi.ERR_INVALID
     # a layout option after the setup: the handle asks for a new gmg_setup instead of silently keeping the old layout
     n1.P_ns.set_option("pattern", 0)
     with pytest.raises(abi.GmgError) as e:
@@ -271,19 +275,17 @@ def test_pair_sweep_is_bitwise_the_single_row_sweep(S, po, orc, nc, nlev, niter)
     assert rel_err(res[1][-2], xo) <= 1e-10
 
 
-@pytest.mark.parametrize("nc,nlev,tile", [((32, 32, 32), 4, 0), ((64, 64), 3, 0), ((40, 36, 28), 2, 2)])
-def test_fused_multiply_add_taps_stay_inside_the_parity_gates(S, po, orc, nc, nlev, tile, monkeypatch):
+@pytest.mark.parametrize("nc,nlev", [((32, 32, 32), 4), ((64, 64), 3)])
+def test_fused_multiply_add_taps_stay_inside_the_parity_gates(S, po, orc, nc, nlev):
     """Option pat_fma = 1 (one rounding per tap instead of the two of the reference's mul!: RichardsonSmoothers.jl:94 through
     SparseArrays): NOT bit-identical, so it is an opt-in -- but it must stay inside the gates SURVEY 8(c) states for the HIP path:
     a smoothing pass <= 1e-13 of the oracle's (max-norm relative), CG iteration count identical, residual history <= 1e-8 per entry,
     solution <= 1e-10."""
-    if tile:
-        monkeypatch.setenv("GMG_PAT_TILE_MIN", "0")
     H = po.build_hierarchy(nc, nlev, 1)
     n = H["mats"][0].shape[0]
     b = po.dirichlet_lift_rhs(nc, 1)
     # pat_r2mv_min = 1: the pair mat-vec kernels (FM variants of sells_r2mv_kernel, with the fused dot) on these small levels too
-    solver = S.CGSolver(make_gmg(S, H, options={"pat_fma": 1, "persist": 0, "pat_tile": tile, "pat_r2mv_min": 1}), maxiter=20, atol=1e-14, rtol=1e-6)
+    solver = S.CGSolver(make_gmg(S, H, options={"pat_fma": 1, "persist": 0, "pat_r2mv_min": 1}), maxiter=20, atol=1e-14, rtol=1e-6)
     ns = setup(S, solver, H["mats"][0])
     assert "FM=1" in (ns.P_ns.sweep_signature(0) or "FM=1")
     from gridapsolvers_jl_amd.abi import OP_A

@@ -92,6 +92,23 @@ def test_epochs_keep_advancing(S, po, hierarchy, regs):
     g.close()
 
 
+def test_a_one_launch_pass_of_two_sweeps_counts_as_fused(S, hierarchy):
+    """gmg_get_kernel_stats counts the one-launch passes from the mark smooth_persistent leaves on the sample, not from the sample's
+    weight: a pass of two sweeps (weight 2, or 1 when its last sweep is closed) is a one-launch pass like any longer one."""
+    nc, nlev, _ = SHAPES["9pt"]
+    H = hierarchy(nc, nlev)
+    n = H["mats"][0].shape[0]
+    g = setup(S, make_gmg(S, H, pre_smoothers=jac(S, nlev, 2), options={"prof_stride": 1}), H["mats"][0])
+    g.profile(0, True)
+    x, r = np.zeros(n), np.random.default_rng(50).uniform(-1, 1, n)
+    g.smooth(0, x, r)
+    st = g.kernel_stats()
+    g.profile(0, False)
+    assert "sells_smooth_kernel" in g.sweep_signature(0), g.sweep_signature(0)
+    assert st["fused_passes"] > 0, st
+    g.close()
+
+
 @pytest.mark.parametrize("name", ["27pt", "9pt"])
 def test_default_options_reproduce_the_oracle(S, po, orc, hierarchy, name):
     nc, nlev, sig = SHAPES[name]
